@@ -1,7 +1,20 @@
 #!/usr/bin/env python3
 """Headline benchmark: Mrays/s rendering the 100k-triangle synthetic soup at 1920x1080, 1 spp.
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
+
+A plain run does what the headline figure needs and no more: it sets up the engine, runs the
+warm-up and the K timed steps, writes the last step's frames when --dump-outputs is given, and
+prints the result line (metric, value, ms_per_step, config, the whole-frame figure; at N > 1 the
+timed run's exchange statistics). --full adds every measurement and check that takes runs of its
+own: the bit-for-bit verification against another kernel, the roofline and stage passes, the
+secondary legs, the ml* API rates and the CPU baseline (their switches --no-extras, --no-e2e,
+--no-cpu-baseline, --brute-steps, --cpu-seconds apply to a --full run).
+
+--dump-outputs DIR: after the timed steps, frames of the last timed step as the engine's caller
+reads them back (srtEngineReadFrame), as float .npy files of at most 64 MB in all (dump_outputs).
+The scene, the sample offsets and the sampled frames and rows are seeded, so two builds run with
+the same arguments can be compared file by file.
 
 Runs with or without a launcher:
   * no WORLD_SIZE (or WORLD_SIZE=1): one process drives all N GPUs (devices 0..N-1) through the
@@ -28,8 +41,8 @@ bands go to the compositors over RCCL (the batch's N gathers fused into one nccl
 group), and each compositor shades its frames' received rows in one launch (deferred shading,
 bit-identical). value = frames x W x H / the max-over-ranks time
 of the timed steps: "scaling": "strong". --mode frames: every GPU renders whole frames of its own
-(no exchange): "scaling": "weak" (a leg of the N > 1 line). After the timed steps every compositor
-compares its last batches' frames with a single-GPU render by another kernel, bit for bit
+(no exchange): "scaling": "weak" (a leg of the N > 1 line). With --full, after the timed steps every
+compositor compares its last batches' frames with a single-GPU render by another kernel, bit for bit
 ("verified").
 
 Prints ONE JSON line on rank 0 (fields in DESIGN.md section 6).
@@ -98,6 +111,11 @@ def parse():
     p.add_argument("--no-cpu-baseline", action="store_true")
     p.add_argument("--no-e2e", action="store_true", help="skip the PCIe-inclusive ml* API measurement")
     p.add_argument("--no-extras", action="store_true", help="only the main line (no secondary legs)")
+    p.add_argument("--full", action="store_true",
+                   help="also verify the frames, take the roofline and stage passes, and run the secondary legs, the "
+                        "ml* API rates and the CPU baseline (module doc)")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write frames of the last timed step to DIR as float .npy files (module doc)")
     a = p.parse_args()
     if a.exchange == "auto":
         # Even framebuffer tiling (north_star: tiles over the GPUs + a gather): every frame split into
@@ -256,6 +274,71 @@ def run_leg(job, a, path, inputs, steps, warmup, **kw):
                 "frames_per_step": eng.batch}
     finally:
         eng.close()
+
+
+DUMP_BYTES = 64_000_000  # --dump-outputs: all files together stay below this
+DUMP_SEED = 0x5EED
+
+
+def dump_plan(H, W, per_batch):
+    """What dump_outputs writes of a step of `per_batch` H x W frames: (rows of the step's first frame,
+    the further frames' indices within the step, each one's rows), ascending, from DUMP_SEED."""
+    import numpy as np
+
+    rng = np.random.default_rng(DUMP_SEED)
+    row_bytes = W * 4 * 4
+    rows0 = min(H, max(1, (DUMP_BYTES * 3 // 4) // row_bytes))
+    frame_rows = np.arange(H) if rows0 == H else np.sort(rng.choice(H, rows0, replace=False))
+    rows1 = min(H, 16)
+    n = min(15, per_batch - 1, (DUMP_BYTES - rows0 * row_bytes) // (rows1 * row_bytes))
+    others = 1 + np.sort(rng.choice(per_batch - 1, n, replace=False)) if n > 0 else []
+    return frame_rows, others, [np.sort(rng.choice(H, rows1, replace=False)) for _ in others]
+
+
+def dump_outputs(job, eng, a, directory):
+    """--dump-outputs: frames of the last timed step (batch warmup + steps - 1, still resident in its
+    queue), read back as a caller of the engine reads them (srtEngineReadFrame: H x W x 4 float32, the
+    colour and the hit triangle's index, -1 for a miss), written as float32:
+
+      frame.npy   (R0, W, 4)     the step's first frame: every row (R0 = H) when that fits three quarters
+                                 of the 64 MB, else R0 seeded rows of it
+      sample.npy  (n, 16, W, 4)  16 seeded rows of each of n <= 15 further frames of the step, drawn with
+                                 the same seed (absent when the step has one frame)
+
+    The frames and rows depend on the arguments and DUMP_SEED alone (dump_plan). One rank per GPU: every
+    rank writes the frames composited on its own GPU, as <name>.rank<r>.npy. Returns the line's "outputs"
+    field."""
+    import numpy as np
+
+    from simpleraytracer_amd.device import SrtError
+
+    out = Path(directory)
+    out.mkdir(parents=True, exist_ok=True)
+    per_batch = eng.batch * (job.world if eng.options["split"] == "frames" else 1)
+    first = (a.warmup + a.steps - 1) * per_batch
+    frame_rows, others, sample_rows = dump_plan(eng.height, eng.width, per_batch)
+
+    def read(k, rows):
+        try:
+            return eng.read_frame(first + int(k))[rows]
+        except SrtError:
+            if job.ranked:  # composited on another rank's GPU
+                return None
+            raise
+
+    arrays = {}
+    whole = read(0, frame_rows)
+    if whole is not None:
+        arrays["frame"] = whole
+    got = [x for x in (read(k, r) for k, r in zip(others, sample_rows)) if x is not None]
+    if got:
+        arrays["sample"] = np.stack(got)
+    suffix = f".rank{job.rank}" if job.ranked else ""
+    for name, arr in arrays.items():
+        np.save(out / f"{name}{suffix}.npy", arr)
+    return {"dir": str(out), "step": a.steps - 1, "frames": [0] + [int(k) for k in others],
+            "files": {f"{name}{suffix}.npy": list(arr.shape) for name, arr in arrays.items()},
+            "bytes": int(sum(arr.nbytes for arr in arrays.values()))}
 
 
 def c5_leg(job, a, steps=10, warmup=2, batch=64, queues=1, launch=64):
@@ -687,7 +770,8 @@ def main():
     path = job.scene_path(a.scene, a.triangles if a.scene == "soup" else None)
     wl = workload_name(a)
     W, H = a.width, a.height
-    extras = not a.no_extras
+    full = a.full
+    extras = full and not a.no_extras
     inputs = make_offsets(a, a.offsets, max(1, a.inputs))
 
     # value: the timed steps on the main engine
@@ -698,20 +782,23 @@ def main():
     eng.set_inputs(inputs)
     elapsed, mrays = timed(job, eng, a.steps, a.warmup)
     frames = a.steps * a.frames_per_step
-    bad, checked = eng.verify()
-    verified = job.gather([bad, checked])
-    # The dominant kernel as the timed run launches it (launch_frames frames per launch), one launch
-    # in flight: the roofline's kernel time (HIP events bound to the kernels' dispatches).
+    # before the stage passes below, which reuse queue 0's frames
+    outputs = dump_outputs(job, eng, a, a.dump_outputs) if a.dump_outputs else None
     launch_frames = frames_per_launch(a, world)
-    n_launch = max(20, min(250, frames // launch_frames))
-    st_launch = eng.stage_times(0, n_launch, launch_frames)
-    # stage times of every rank's band (single-frame launches, events on the dispatches)
-    n_stage = min(1000, max(20, frames))
-    st = eng.stage_times(0, n_stage)
-    if job.ranked:
-        ranks_stages = job.gather(list(st))
-    else:  # every device of this process, in band order
-        ranks_stages = [list(st)] + [list(eng.stage_times(i, n_stage)) for i in range(1, info["local_devices"])]
+    if full:
+        bad, checked = eng.verify()
+        verified = job.gather([bad, checked])
+        # The dominant kernel as the timed run launches it (launch_frames frames per launch), one launch
+        # in flight: the roofline's kernel time (HIP events bound to the kernels' dispatches).
+        n_launch = max(20, min(250, frames // launch_frames))
+        st_launch = eng.stage_times(0, n_launch, launch_frames)
+        # stage times of every rank's band (single-frame launches, events on the dispatches)
+        n_stage = min(1000, max(20, frames))
+        st = eng.stage_times(0, n_stage)
+        if job.ranked:
+            ranks_stages = job.gather(list(st))
+        else:  # every device of this process, in band order
+            ranks_stages = [list(st)] + [list(eng.stage_times(i, n_stage)) for i in range(1, info["local_devices"])]
     # the timed run's exchange, per device (HIP events on each device's exchange stream)
     xstats = [eng.exchange_stats(i) for i in range(info["local_devices"])] if world > 1 else []
     if job.ranked:
@@ -840,14 +927,15 @@ def main():
         launch_rays = rows0 * W
         key = profile_key(wl, a.variant, world if band else 1, a.rows, launch_frames)
         offsets_read = a.offsets != "uniform"
-        roof, valu, bfe = roofline_fields(
-            wl, a.variant, launch_rays, launch_frames, n_tri, st_launch[3], band, rows0 / H, key, offsets_read,
-            f"the timed run's launch shape ({launch_frames} frames per launch), one launch in flight, "
-            f"{st_launch[0]} launches, HIP events bound to the kernel's dispatch")
-        roof1, _, _ = roofline_fields(
-            wl, a.variant, launch_rays, 1, n_tri, st[3], band, rows0 / H, profile_key(wl, a.variant, world if band
-                                                                                      else 1, a.rows, 1),
-            offsets_read, f"latency pass: one frame per launch, one in flight, {st[0]} launches")
+        if full:
+            roof, valu, bfe = roofline_fields(
+                wl, a.variant, launch_rays, launch_frames, n_tri, st_launch[3], band, rows0 / H, key, offsets_read,
+                f"the timed run's launch shape ({launch_frames} frames per launch), one launch in flight, "
+                f"{st_launch[0]} launches, HIP events bound to the kernel's dispatch")
+            roof1, _, _ = roofline_fields(
+                wl, a.variant, launch_rays, 1, n_tri, st[3], band, rows0 / H, profile_key(wl, a.variant, world if band
+                                                                                          else 1, a.rows, 1),
+                offsets_read, f"latency pass: one frame per launch, one in flight, {st[0]} launches")
         ms_frame = elapsed / frames * 1e3
         if band:
             par = (f"bands x{world} ({a.rows} rows) + {'RCCL' if info['rccl'] else 'device-copy'} "
@@ -886,27 +974,34 @@ def main():
                 "offsets": a.offsets,
             },
             "ms_per_frame": round(ms_frame, 6),
-            "roofline": roof,
-            "roofline_single_frame": roof1,
-            "whole_frame": whole_frame_fields(W, H, n_tri, ms_frame, world if a.mode == "bands" else 1),
-            "stages_ms": {"prepare": round(st[1], 5), "bin": round(st[2], 5), "trace_kernel": round(st[3], 5),
-                          "timed_launches": st[0],
-                          "note": "single-frame launches of rank 0's band, HIP events bound to the kernels' dispatches: "
-                                  "prepare = TileInfoKernel (0 for a full frame: its tile info runs inside the bin "
-                                  "launch), bin = PrepareBinKernel (record setup + bins [+ tile info]) + "
-                                  "WorkOrderKernel, trace_kernel = TraceCullKernel"},
+            "full": full,
         }
-        if valu is not None:
-            line["valu_issue"] = valu
-        line["brute_force_equivalent"] = bfe
-        line["verified"] = all(v[0] == 0 and v[1] > 0 for v in verified)
-        line["verify"] = {"frames_checked": sum(v[1] for v in verified), "mismatches": sum(v[0] for v in verified),
-                          "note": "up to 4 frames composited in each queue's last batch, on every GPU, vs a single-GPU "
-                                  "full-frame render of their inputs by another trace kernel (lds for cull), bit for "
-                                  "bit"}
+        if outputs is not None:
+            line["outputs"] = outputs
+        if full:
+            line["roofline"] = roof
+            line["roofline_single_frame"] = roof1
+        line["whole_frame"] = whole_frame_fields(W, H, n_tri, ms_frame, world if a.mode == "bands" else 1)
+        if full:
+            line["stages_ms"] = {
+                "prepare": round(st[1], 5), "bin": round(st[2], 5), "trace_kernel": round(st[3], 5),
+                "timed_launches": st[0],
+                "note": "single-frame launches of rank 0's band, HIP events bound to the kernels' dispatches: "
+                        "prepare = TileInfoKernel (0 for a full frame: its tile info runs inside the bin "
+                        "launch), bin = PrepareBinKernel (record setup + bins [+ tile info]) + "
+                        "WorkOrderKernel, trace_kernel = TraceCullKernel"}
+            if valu is not None:
+                line["valu_issue"] = valu
+            line["brute_force_equivalent"] = bfe
+            line["verified"] = all(v[0] == 0 and v[1] > 0 for v in verified)
+            line["verify"] = {"frames_checked": sum(v[1] for v in verified), "mismatches": sum(v[0] for v in verified),
+                              "note": "up to 4 frames composited in each queue's last batch, on every GPU, vs a "
+                                      "single-GPU full-frame render of their inputs by another trace kernel (lds for "
+                                      "cull), bit for bit"}
         if world > 1:
-            line["ranks_stages_ms"] = [{"rank": i, "prepare": round(s[1], 5), "bin": round(s[2], 5),
-                                        "trace_kernel": round(s[3], 5)} for i, s in enumerate(ranks_stages)]
+            if full:
+                line["ranks_stages_ms"] = [{"rank": i, "prepare": round(s[1], 5), "bin": round(s[2], 5),
+                                            "trace_kernel": round(s[3], 5)} for i, s in enumerate(ranks_stages)]
             if band:
                 from simpleraytracer_amd import _native
 
@@ -962,7 +1057,7 @@ def main():
                 line["ml_multi"] = ml_multi_child(path, W, H, list(range(world)))
             else:
                 line["ml_multi"] = ml_multi_fields(path, W, H, job.devices, job.one_device)
-        if not a.no_cpu_baseline:  # on every line, from rank 0 (the other ranks wait at the barrier below)
+        if full and not a.no_cpu_baseline:  # from rank 0 (the other ranks wait at the barrier below)
             line["cpu_baseline"] = cpu_baseline(path, a)
         print(json.dumps(line), flush=True)
     job.barrier()

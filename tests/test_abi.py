@@ -7,6 +7,8 @@ asserted as such.
 from __future__ import annotations
 
 import ctypes
+import json
+import os
 import re
 import subprocess
 from pathlib import Path
@@ -108,7 +110,11 @@ def test_header_is_valid_c_with_reference_layout(tmp_path):
     ours = _probe(tmp_path, "gcc", "c", REPO / "include")
     assert ours == ["24", "32", "0", "8", "24", "0", "1", "0", "1"]
     assert ctypes.sizeof(ImageInfo) == 32 and ctypes.sizeof(ModelParams) == 24
-    if REFERENCE.exists():  # the reference header only compiles as C++ (model_runner.h:102)
+    # the same probe against the reference's header, as recorded (tests/golden/reference_layout.json) ...
+    recorded = json.loads((REPO / "tests" / "golden" / "reference_layout.json").read_text())["probe"]
+    assert ours == recorded
+    # ... and afresh where its sources can be read (they are optional: absent or unreadable elsewhere)
+    if os.access(REFERENCE / "model_runner.h", os.R_OK):  # it only compiles as C++ (model_runner.h:102)
         ref = _probe(tmp_path, "g++", "cpp", REFERENCE)
         assert ours == ref
 

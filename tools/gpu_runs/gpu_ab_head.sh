@@ -9,7 +9,7 @@ for rep in 1 2; do
         grep '^{"P"' gpurun_out/hrs_${v}_$rep.log | python3 -c "import sys,json
 for l in sys.stdin:
     d=json.loads(l); print('$v#$rep', d['P'], d['slowest_us'])"
-        SRT_LIB=$lib run hb_${v}_$rep 200 python3 bench.py --steps 100 --warmup 5 --no-cpu-baseline --no-e2e --brute-steps 0 --no-extras
+        SRT_LIB=$lib run hb_${v}_$rep 200 python3 bench.py --full --steps 100 --warmup 5 --no-cpu-baseline --no-e2e --brute-steps 0 --no-extras
         echo "$v#$rep $(grep -o '"value": [0-9.]*\|"kernel_ms": [0-9.]*' gpurun_out/hb_${v}_$rep.log | tr '\n' ' ')"
     done
 done

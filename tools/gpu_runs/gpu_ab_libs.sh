@@ -4,7 +4,7 @@
 source "$(dirname "$0")/gpu_lib.sh"
 for name in $LIBS; do
     SRT_LIB=simpleraytracer_amd/lib_ab/$name/libModelRunner.so run ab_$name 300 \
-        python bench.py --no-extras --no-cpu-baseline --steps ${STEPS:-50} ${BENCH_ARGS:-}
+        python bench.py --full --no-extras --no-cpu-baseline --steps ${STEPS:-50} ${BENCH_ARGS:-}
 done
 for name in $LIBS; do
     echo "== $name"; python3 tools/bench_summary.py gpurun_out/ab_$name.log

@@ -15,7 +15,7 @@ for rep in 1 2; do
             lib=simpleraytracer_amd/lib_ab/old/libModelRunner.so
             mode=auto
         fi
-        SRT_LIB=$lib SRT_WORK_PLAN=$mode run ab_${v}_$rep 200 python3 bench.py --steps ${STEPS:-200} --warmup 10 \
+        SRT_LIB=$lib SRT_WORK_PLAN=$mode run ab_${v}_$rep 200 python3 bench.py --full --steps ${STEPS:-200} --warmup 10 \
             --no-cpu-baseline --no-e2e --brute-steps 0
         echo "$v#$rep $(grep -o '"value": [0-9.]*\|"single_queue": {"mrays_per_s": [0-9.]*\|"kernel_ms": [0-9.]*\|"bin": [0-9.]*' gpurun_out/ab_${v}_$rep.log | tr '\n' ' ')"
     done

@@ -11,7 +11,7 @@ for rep in $(seq 1 ${REPS:-2}); do
     for v in ${VARIANTS:-head product}; do
         lib=""; [ $v != product ] && lib=simpleraytracer_amd/lib_ab/$v/libModelRunner.so
         SRT_LIB=$lib run ar_rank_${v}_$rep 300 python3 tools/rank_sim.py --ranks 2,4,8
-        SRT_LIB=$lib run ar_bench_${v}_$rep 200 python3 bench.py --steps 100 --warmup 5 --no-cpu-baseline --no-e2e --brute-steps 0 --no-extras
+        SRT_LIB=$lib run ar_bench_${v}_$rep 200 python3 bench.py --full --steps 100 --warmup 5 --no-cpu-baseline --no-e2e --brute-steps 0 --no-extras
         echo "$v#$rep $(grep '^{"P"' gpurun_out/ar_rank_${v}_$rep.log | python3 -c "import sys,json
 print(' '.join('P%d=%s' % (d['P'], d['slowest_us']) for d in map(json.loads, sys.stdin)))") bench $(grep -o '"value": [0-9.]*' gpurun_out/ar_bench_${v}_$rep.log)"
     done

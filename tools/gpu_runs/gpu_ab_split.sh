@@ -9,13 +9,13 @@ SRT_LIB=$A run atomic_tests 300 python -u -m pytest tests/test_gpu_parity.py tes
 for v in product atomic; do
     lib=""; [ $v = atomic ] && lib=$A
     SRT_LIB=$lib run q1_$v 300 rocprofv3 --kernel-trace --stats -d gpurun_out/q1_$v -o run --output-format csv -- \
-        python3 bench.py --steps 300 --warmup 20 --queues 1 --frames-per-step 1 --no-extras --no-cpu-baseline
+        python3 bench.py --full --steps 300 --warmup 20 --queues 1 --frames-per-step 1 --no-extras --no-cpu-baseline
     python3 tools/kernel_stats.py gpurun_out/q1_$v | grep -E "TraceCull|PrepareBin|WorkOrder"
 done
 for rep in 1 2; do
     for v in product atomic; do
         lib=""; [ $v = atomic ] && lib=$A
-        SRT_LIB=$lib run ab_${v}_$rep 200 python3 bench.py --steps 200 --warmup 10 --no-cpu-baseline --no-e2e --brute-steps 0
+        SRT_LIB=$lib run ab_${v}_$rep 200 python3 bench.py --full --steps 200 --warmup 10 --no-cpu-baseline --no-e2e --brute-steps 0
         echo "$v#$rep $(grep -o '"value": [0-9.]*\|"single_queue": {"mrays_per_s": [0-9.]*\|"kernel_ms": [0-9.]*' gpurun_out/ab_${v}_$rep.log | tr '\n' ' ')"
     done
 done

@@ -9,13 +9,13 @@ if [[ $STEPS == *tests* ]]; then
 fi
 if [[ $STEPS == *q1* ]]; then
     run prof_q1 300 rocprofv3 --kernel-trace --stats -d gpurun_out/prof_q1 -o run --output-format csv -- \
-        python3 bench.py --steps 300 --warmup 20 --queues 1 --frames-per-step 1 --no-extras --no-cpu-baseline
+        python3 bench.py --full --steps 300 --warmup 20 --queues 1 --frames-per-step 1 --no-extras --no-cpu-baseline
     python3 tools/kernel_stats.py gpurun_out/prof_q1
 fi
 if [[ $STEPS == *ranks* ]]; then
     run rank_sim 300 python tools/rank_sim.py --ranks 1,8
 fi
 if [[ $STEPS == *bench* ]]; then
-    run bench 300 python bench.py --no-cpu-baseline --no-e2e --brute-steps 0
+    run bench 300 python bench.py --full --no-cpu-baseline --no-e2e --brute-steps 0
     python3 tools/bench_summary.py gpurun_out/bench.log
 fi

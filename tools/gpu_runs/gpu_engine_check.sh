@@ -11,12 +11,12 @@ if [[ $STEPS == *tests* ]]; then
     run pytest_gpu 900 python -u -m pytest tests -m gpu -x -q --timeout 120 --timeout-method thread
 fi
 if [[ $STEPS == *bench* ]]; then
-    run bench_driver 300 python bench.py --gpus 1 --steps 20 --warmup 5
-    run bench_long 300 python bench.py --no-extras --no-cpu-baseline
+    run bench_driver 300 python bench.py --full --gpus 1 --steps 20 --warmup 5
+    run bench_long 300 python bench.py --full --no-extras --no-cpu-baseline
 fi
 if [[ $STEPS == *rehearse* ]]; then
     for n in 2 4 8; do
-        SRT_BENCH_ONE_DEVICE=1 run rehearse$n 300 python bench.py --gpus $n --steps 20 --warmup 3 --no-e2e
+        SRT_BENCH_ONE_DEVICE=1 run rehearse$n 300 python bench.py --full --gpus $n --steps 20 --warmup 3 --no-e2e
     done
 fi
 echo done

@@ -5,7 +5,7 @@ source "$(dirname "$0")/gpu_lib.sh"
 for cfg in $CFGS; do
   name=${cfg%%:*}; rest=${cfg#*:}; envs=${rest%%:*}; args=""
   [[ $rest == *:* ]] && args=${rest#*:}
-  env $(echo "$envs" | tr ',' ' ') timeout -k 10 200 python bench.py --no-extras --no-cpu-baseline --steps ${STEPS:-100} ${args//,/ } \
+  env $(echo "$envs" | tr ',' ' ') timeout -k 10 200 python bench.py --full --no-extras --no-cpu-baseline --steps ${STEPS:-100} ${args//,/ } \
       > gpurun_out/sw_$name.log 2>&1; rc=$?
   echo "$name rc=$rc"; [ $rc -ne 0 ] && [ $rc -ne 1 ] && exit $rc
 done

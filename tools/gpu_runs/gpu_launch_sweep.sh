@@ -7,7 +7,7 @@ if [ "${TESTS:-1}" = 1 ]; then
 fi
 for l in ${LAUNCHES:-8 16 32 64}; do
     run rs_l$l 300 python tools/rank_sim.py --ranks ${RANKS:-1,8} --launch $l
-    run bench_l$l 300 python bench.py --no-extras --no-cpu-baseline --launch $l
+    run bench_l$l 300 python bench.py --full --no-extras --no-cpu-baseline --launch $l
 done
 for l in ${LAUNCHES:-8 16 32 64}; do
     echo "== launch $l"; grep '"P"' gpurun_out/rs_l$l.log

@@ -3,6 +3,6 @@
 source "$(dirname "$0")/gpu_lib.sh"
 for sh in ${SHAPES:-3:8}; do
     q=${sh%%:*}; b=${sh#*:}
-    run pipe_q${q}_b${b} 200 python bench.py --no-extras --no-cpu-baseline --queues $q --batch $b
+    run pipe_q${q}_b${b} 200 python bench.py --full --no-extras --no-cpu-baseline --queues $q --batch $b
 done
 echo done

@@ -3,7 +3,7 @@
 # launch; the largest grid of the bench run), one --pmc pass each, merged into
 # profiles/pmc_traffic.json / pmc_sq.json under the bench's launch8 profile key.
 source "$(dirname "$0")/gpu_lib.sh"
-B="python3 bench.py --steps 3 --warmup 1 --no-extras --no-cpu-baseline --no-e2e --brute-steps 0"
+B="python3 bench.py --full --steps 3 --warmup 1 --no-extras --no-cpu-baseline --no-e2e --brute-steps 0"
 K="--kernel-include-regex TraceCullKernel"
 KEY="soup-100k 1920x1080 1spp|cull|launch8"
 run l8_fetch 150 timeout -s KILL 140 rocprofv3 --pmc FETCH_SIZE $K -d gpurun_out/l8_fetch -o run --output-format csv -- $B

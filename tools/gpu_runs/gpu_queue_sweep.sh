@@ -3,7 +3,7 @@
 # queue count in $QS.
 source "$(dirname "$0")/gpu_lib.sh"
 for q in ${QS:-1 2 3}; do
-    run qb_q$q 300 python bench.py --no-extras --no-cpu-baseline --queues $q
-    run qd_q$q 200 python bench.py --no-extras --no-cpu-baseline --queues $q --steps 20 --warmup 5
+    run qb_q$q 300 python bench.py --full --no-extras --no-cpu-baseline --queues $q
+    run qd_q$q 200 python bench.py --full --no-extras --no-cpu-baseline --queues $q --steps 20 --warmup 5
 done
 echo done

@@ -3,7 +3,7 @@
 # largest grid), plus a kernel trace of the same bench command whose 8-frame dispatches give the
 # roofline's rocprof mean (tools/trace_shapes.py), and the two HBM traffic passes again.
 source "$(dirname "$0")/gpu_lib.sh"
-B="python3 bench.py --steps 3 --warmup 1 --no-extras --no-cpu-baseline --no-e2e --brute-steps 0"
+B="python3 bench.py --full --steps 3 --warmup 1 --no-extras --no-cpu-baseline --no-e2e --brute-steps 0"
 K="--kernel-include-regex TraceCullKernel"
 run list 60 rocprofv3 -L
 run l8_trace 200 timeout -s KILL 190 rocprofv3 --kernel-trace --stats -d gpurun_out/l8_trace -o run --output-format csv -- $B

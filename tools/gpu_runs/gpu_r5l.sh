@@ -4,7 +4,7 @@ source "$(dirname "$0")/gpu_lib.sh"
 run pytest_gpu 900 python3 -u -m pytest tests -m gpu -x -q --timeout 300 --timeout-method thread
 tail -3 gpurun_out/pytest_gpu.log
 grep -q " passed" gpurun_out/pytest_gpu.log && ! grep -q "FAILED\|Error" gpurun_out/pytest_gpu.log || { echo "tests failed"; exit 1; }
-run bench 600 python3 bench.py --steps 20 --warmup 5
+run bench 600 python3 bench.py --full --steps 20 --warmup 5
 tail -1 gpurun_out/bench.log | cut -c1-300
 for ex in "alltoall rotated" "share interleaved" "alltoall interleaved"; do
   set -- $ex

@@ -6,6 +6,6 @@ run pytest_gpu 600 python3 -u -m pytest tests -m gpu -x -q --timeout 280 --timeo
 tail -2 gpurun_out/pytest_gpu.log
 grep -q " passed" gpurun_out/pytest_gpu.log && ! grep -q "FAILED\|Error" gpurun_out/pytest_gpu.log || { echo "tests failed"; exit 1; }
 run smoke 300 python3 -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')"
-run bench 600 python3 bench.py --steps 20 --warmup 5
+run bench 600 python3 bench.py --full --steps 20 --warmup 5
 tail -1 gpurun_out/bench.log | cut -c1-300
 echo done

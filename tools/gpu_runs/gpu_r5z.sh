@@ -6,5 +6,5 @@ tail -2 gpurun_out/pytest_gpu.log
 grep -q " passed" gpurun_out/pytest_gpu.log && ! grep -q "FAILED\|Error" gpurun_out/pytest_gpu.log || { echo "tests failed"; exit 1; }
 run smoke 300 python3 -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')"
 tail -1 gpurun_out/smoke.log
-run bench 600 python3 bench.py --steps 20 --warmup 5
+run bench 600 python3 bench.py --full --steps 20 --warmup 5
 tail -1 gpurun_out/bench.log | cut -c1-200

@@ -3,8 +3,8 @@
 # interleaved rounds: the headline (driver shape, 2 queues x 8-frame launches) and one frame in flight.
 # lib_exp/bt256 = the product's shape, rebuilt the same way as the others.
 source "$(dirname "$0")/gpu_lib.sh"
-B="python3 bench.py --steps 20 --warmup 5 --no-extras --no-cpu-baseline --no-e2e"
-S="python3 bench.py --steps 400 --warmup 20 --frames-per-step 1 --queues 1 --launch 1 --no-extras --no-cpu-baseline --no-e2e"
+B="python3 bench.py --full --steps 20 --warmup 5 --no-extras --no-cpu-baseline --no-e2e"
+S="python3 bench.py --full --steps 400 --warmup 20 --frames-per-step 1 --queues 1 --launch 1 --no-extras --no-cpu-baseline --no-e2e"
 for r in 1 2; do
   for v in bt256 bt128 bt128i2 bt512; do
     SRT_LIB=simpleraytracer_amd/lib_exp/$v/libModelRunner.so run ${v}_h_$r 150 $B
@@ -13,7 +13,7 @@ for r in 1 2; do
   done
 done
 # HBM traffic of the C5 leg's launch shape (1 queue x 16 frames per launch; the product library)
-B5="python3 bench.py --triangles 1000000 --width 3840 --height 2160 --frames-per-step 64 --steps 3 --warmup 1 --queues 1 --launch 16 --no-extras --no-cpu-baseline --no-e2e --brute-steps 0"
+B5="python3 bench.py --full --triangles 1000000 --width 3840 --height 2160 --frames-per-step 64 --steps 3 --warmup 1 --queues 1 --launch 16 --no-extras --no-cpu-baseline --no-e2e --brute-steps 0"
 K="--kernel-include-regex TraceCullKernel"
 run c5l16_fetch 300 timeout -s KILL 290 rocprofv3 --pmc FETCH_SIZE $K -d gpurun_out/c5l16_fetch -o run --output-format csv -- $B5
 run c5l16_write 300 timeout -s KILL 290 rocprofv3 --pmc WRITE_SIZE $K -d gpurun_out/c5l16_write -o run --output-format csv -- $B5

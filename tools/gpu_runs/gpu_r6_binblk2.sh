@@ -3,7 +3,7 @@
 # headline in both rounds): three more alternating rounds of the driver shape, 256 (product) against 128
 # (one tile-info tile per block), plus a P = 8 rank simulation of each (the band skip's block granularity).
 source "$(dirname "$0")/gpu_lib.sh"
-B="python3 bench.py --steps 20 --warmup 5 --no-extras --no-cpu-baseline --no-e2e"
+B="python3 bench.py --full --steps 20 --warmup 5 --no-extras --no-cpu-baseline --no-e2e"
 for r in 3 4 5; do
   for v in bt256 bt128; do
     SRT_LIB=simpleraytracer_amd/lib_exp/$v/libModelRunner.so run ${v}_h_$r 150 $B

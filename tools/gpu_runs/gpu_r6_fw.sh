@@ -8,8 +8,8 @@ L=simpleraytracer_amd/lib_exp
 SRT_LIB=$L/fw/libModelRunner.so SRT_FUSED_INFO=0 run fw_pytest 600 python3 -u -m pytest tests -m gpu -q --timeout 200 --timeout-method thread --deselect "tests/test_gpu_parity.py::test_stage_timing_does_not_change_the_frame[cull]"
 tail -1 gpurun_out/fw_pytest.log
 grep -q " passed" gpurun_out/fw_pytest.log && ! grep -q "FAILED\|Error" gpurun_out/fw_pytest.log || { echo "tests failed"; exit 1; }
-B="python3 bench.py --steps 20 --warmup 5 --no-extras --no-cpu-baseline --no-e2e"
-S="python3 bench.py --steps 400 --warmup 20 --frames-per-step 1 --queues 1 --launch 1 --no-extras --no-cpu-baseline --no-e2e"
+B="python3 bench.py --full --steps 20 --warmup 5 --no-extras --no-cpu-baseline --no-e2e"
+S="python3 bench.py --full --steps 400 --warmup 20 --frames-per-step 1 --queues 1 --launch 1 --no-extras --no-cpu-baseline --no-e2e"
 for r in 1 2 3; do
   SRT_LIB=$L/base/libModelRunner.so run fw_base_$r 150 $B
   SRT_LIB=$L/base/libModelRunner.so SRT_FUSED_INFO=0 run fw_unf_$r 150 $B

@@ -3,7 +3,7 @@
 # driver shape, four more alternating rounds.
 source "$(dirname "$0")/gpu_lib.sh"
 L=simpleraytracer_amd/lib_exp
-B="python3 bench.py --steps 20 --warmup 5 --no-extras --no-cpu-baseline --no-e2e"
+B="python3 bench.py --full --steps 20 --warmup 5 --no-extras --no-cpu-baseline --no-e2e"
 for r in 3 4 5 6; do
   for v in ba4 it4; do
     SRT_LIB=$L/$v/libModelRunner.so run k${v}_h_$r 150 $B

@@ -4,8 +4,8 @@
 # shape and one frame in flight, two alternating rounds.
 source "$(dirname "$0")/gpu_lib.sh"
 L=simpleraytracer_amd/lib_exp
-B="python3 bench.py --steps 20 --warmup 5 --no-extras --no-cpu-baseline --no-e2e"
-S="python3 bench.py --steps 400 --warmup 20 --frames-per-step 1 --queues 1 --launch 1 --no-extras --no-cpu-baseline --no-e2e"
+B="python3 bench.py --full --steps 20 --warmup 5 --no-extras --no-cpu-baseline --no-e2e"
+S="python3 bench.py --full --steps 400 --warmup 20 --frames-per-step 1 --queues 1 --launch 1 --no-extras --no-cpu-baseline --no-e2e"
 for r in 1 2; do
   line="round $r:"
   for v in ba4 ba2 ba8 it4; do

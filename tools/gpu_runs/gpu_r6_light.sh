@@ -4,7 +4,7 @@
 # (driver shape, 2 queues) with records recomputed for every launch, against stored records, two rounds.
 source "$(dirname "$0")/gpu_lib.sh"
 L=simpleraytracer_amd/lib_exp
-B="python3 bench.py --steps 20 --warmup 5 --no-extras --no-cpu-baseline --no-e2e"
+B="python3 bench.py --full --steps 20 --warmup 5 --no-extras --no-cpu-baseline --no-e2e"
 for r in 1 2; do
   SRT_LIB=$L/light0/libModelRunner.so SRT_TRACE_RECORDS=stored run st_$r 150 $B
   line="round $r: stored $(grep -o '"value": [0-9.]*' gpurun_out/st_$r.log | head -1)"

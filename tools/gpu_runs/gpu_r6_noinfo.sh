@@ -4,8 +4,8 @@
 # the product's build (base), three alternating rounds; and one frame in flight.
 source "$(dirname "$0")/gpu_lib.sh"
 L=simpleraytracer_amd/lib_exp
-B="python3 bench.py --steps 20 --warmup 5 --no-extras --no-cpu-baseline --no-e2e"
-S="python3 bench.py --steps 400 --warmup 20 --frames-per-step 1 --queues 1 --launch 1 --no-extras --no-cpu-baseline --no-e2e"
+B="python3 bench.py --full --steps 20 --warmup 5 --no-extras --no-cpu-baseline --no-e2e"
+S="python3 bench.py --full --steps 400 --warmup 20 --frames-per-step 1 --queues 1 --launch 1 --no-extras --no-cpu-baseline --no-e2e"
 for r in 1 2 3; do
   for v in base noinfo; do
     SRT_LIB=$L/$v/libModelRunner.so run ni_${v}_$r 150 $B

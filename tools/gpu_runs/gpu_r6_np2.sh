@@ -7,8 +7,8 @@ L=simpleraytracer_amd/lib_exp
 SRT_LIB=$L/np2/libModelRunner.so run np2_pytest 600 python3 -u -m pytest tests -m gpu -x -q --timeout 200 --timeout-method thread
 tail -1 gpurun_out/np2_pytest.log
 grep -q " passed" gpurun_out/np2_pytest.log && ! grep -q "FAILED\|Error" gpurun_out/np2_pytest.log || { echo "tests failed"; exit 1; }
-B="python3 bench.py --steps 20 --warmup 5 --no-extras --no-cpu-baseline --no-e2e"
-S="python3 bench.py --steps 400 --warmup 20 --frames-per-step 1 --queues 1 --launch 1 --no-extras --no-cpu-baseline --no-e2e"
+B="python3 bench.py --full --steps 20 --warmup 5 --no-extras --no-cpu-baseline --no-e2e"
+S="python3 bench.py --full --steps 400 --warmup 20 --frames-per-step 1 --queues 1 --launch 1 --no-extras --no-cpu-baseline --no-e2e"
 for r in 1 2; do
   line="round $r single:"
   SRT_LIB=$L/p2/libModelRunner.so run np_p2_s_$r 150 $S

@@ -3,8 +3,8 @@
 # four more alternating rounds, and the C5 leg's shape once each.
 source "$(dirname "$0")/gpu_lib.sh"
 L=simpleraytracer_amd/lib_exp
-B="python3 bench.py --steps 20 --warmup 5 --no-extras --no-cpu-baseline --no-e2e"
-C5="python3 bench.py --triangles 1000000 --width 3840 --height 2160 --frames-per-step 64 --steps 10 --warmup 2 --queues 1 --launch 64 --no-extras --no-cpu-baseline --no-e2e"
+B="python3 bench.py --full --steps 20 --warmup 5 --no-extras --no-cpu-baseline --no-e2e"
+C5="python3 bench.py --full --triangles 1000000 --width 3840 --height 2160 --frames-per-step 64 --steps 10 --warmup 2 --queues 1 --launch 64 --no-extras --no-cpu-baseline --no-e2e"
 for r in 3 4 5 6; do
   for v in p2 np2; do
     SRT_LIB=$L/$v/libModelRunner.so run nb_${v}_$r 150 $B

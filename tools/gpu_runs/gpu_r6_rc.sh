@@ -7,9 +7,9 @@ source "$(dirname "$0")/gpu_lib.sh"
 L=simpleraytracer_amd/lib_exp
 SRT_LIB=$L/rc/libModelRunner.so run rc_pytest 600 python -u -m pytest tests -m gpu -x -q --timeout 120 --timeout-method thread
 grep -E "passed|failed" gpurun_out/rc_pytest.log | tail -1
-B="python3 bench.py --steps 20 --warmup 5 --no-extras --no-cpu-baseline --no-e2e"
-S="python3 bench.py --steps 400 --warmup 20 --frames-per-step 1 --queues 1 --launch 1 --no-extras --no-cpu-baseline --no-e2e"
-C5="python3 bench.py --triangles 1000000 --width 3840 --height 2160 --frames-per-step 64 --steps 10 --warmup 2 --queues 1 --launch 16 --no-extras --no-cpu-baseline --no-e2e"
+B="python3 bench.py --full --steps 20 --warmup 5 --no-extras --no-cpu-baseline --no-e2e"
+S="python3 bench.py --full --steps 400 --warmup 20 --frames-per-step 1 --queues 1 --launch 1 --no-extras --no-cpu-baseline --no-e2e"
+C5="python3 bench.py --full --triangles 1000000 --width 3840 --height 2160 --frames-per-step 64 --steps 10 --warmup 2 --queues 1 --launch 16 --no-extras --no-cpu-baseline --no-e2e"
 for r in 1 2 3; do
   for v in rc0 rc; do
     SRT_LIB=$L/$v/libModelRunner.so run ${v}_h_$r 150 $B

@@ -6,9 +6,9 @@ source "$(dirname "$0")/gpu_lib.sh"
 run rm_pytest 600 python -u -m pytest tests -m gpu -x -q --timeout 120 --timeout-method thread
 grep -E "passed|failed" gpurun_out/rm_pytest.log | tail -1
 run rm_smoke 300 python -c "import __graft_entry__ as g; g.smoke()"
-B="python3 bench.py --steps 20 --warmup 5 --no-extras --no-cpu-baseline --no-e2e"
-S="python3 bench.py --steps 400 --warmup 20 --frames-per-step 1 --queues 1 --launch 1 --no-extras --no-cpu-baseline --no-e2e"
-C5="python3 bench.py --triangles 1000000 --width 3840 --height 2160 --frames-per-step 64 --steps 10 --warmup 2 --queues 1 --launch 16 --no-extras --no-cpu-baseline --no-e2e"
+B="python3 bench.py --full --steps 20 --warmup 5 --no-extras --no-cpu-baseline --no-e2e"
+S="python3 bench.py --full --steps 400 --warmup 20 --frames-per-step 1 --queues 1 --launch 1 --no-extras --no-cpu-baseline --no-e2e"
+C5="python3 bench.py --full --triangles 1000000 --width 3840 --height 2160 --frames-per-step 64 --steps 10 --warmup 2 --queues 1 --launch 16 --no-extras --no-cpu-baseline --no-e2e"
 for r in 1 2; do
   run rm_h_$r 150 $B
   for m in policy stored; do

@@ -2,7 +2,7 @@
 # Round 6: the headline's frame loop at the final code -- frame queues 2 / 3 x frames per launch 8 / 16 / 32
 # (driver shape, 256-frame steps), two alternating rounds.
 source "$(dirname "$0")/gpu_lib.sh"
-B="python3 bench.py --steps 20 --warmup 5 --no-extras --no-cpu-baseline --no-e2e"
+B="python3 bench.py --full --steps 20 --warmup 5 --no-extras --no-cpu-baseline --no-e2e"
 for r in 1 2; do
   line="round $r:"
   for q in 2 3; do

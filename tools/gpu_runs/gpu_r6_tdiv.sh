@@ -7,8 +7,8 @@ L=simpleraytracer_amd/lib_exp
 run td_pytest 600 python3 -u -m pytest tests -m gpu -x -q --timeout 200 --timeout-method thread
 tail -1 gpurun_out/td_pytest.log
 grep -q " passed" gpurun_out/td_pytest.log && ! grep -q "FAILED\|Error" gpurun_out/td_pytest.log || { echo "tests failed"; exit 1; }
-B="python3 bench.py --steps 20 --warmup 5 --no-extras --no-cpu-baseline --no-e2e"
-S="python3 bench.py --steps 400 --warmup 20 --frames-per-step 1 --queues 1 --launch 1 --no-extras --no-cpu-baseline --no-e2e"
+B="python3 bench.py --full --steps 20 --warmup 5 --no-extras --no-cpu-baseline --no-e2e"
+S="python3 bench.py --full --steps 400 --warmup 20 --frames-per-step 1 --queues 1 --launch 1 --no-extras --no-cpu-baseline --no-e2e"
 for r in 1 2 3 4; do
   for v in base tdiv; do
     SRT_LIB=$L/$v/libModelRunner.so run td_${v}_$r 150 $B

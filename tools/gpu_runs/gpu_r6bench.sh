@@ -3,5 +3,5 @@
 source "$(dirname "$0")/gpu_lib.sh"
 run smoke_head 300 python3 -c "import __graft_entry__ as g; g.smoke()"
 tail -1 gpurun_out/smoke_head.log
-run bench 900 python3 bench.py --steps 20 --warmup 5
+run bench 900 python3 bench.py --full --steps 20 --warmup 5
 tail -1 gpurun_out/bench.log | cut -c1-200

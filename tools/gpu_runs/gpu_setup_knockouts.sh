@@ -3,7 +3,7 @@
 # PrepareBinKernel with SRT_EXP knockouts (1: no tile ranges / bins, 4: no global list reservations,
 # 512: no screen-box solve), and the kernel mix of one P = 8 band rank's stream (rank simulation).
 source "$(dirname "$0")/gpu_lib.sh"
-Q="--steps 300 --warmup 20 --queues 1 --frames-per-step 1 --no-extras --no-cpu-baseline"
+Q="--steps 300 --warmup 20 --queues 1 --frames-per-step 1 --no-extras --no-cpu-baseline --full"
 for e in ${EXPS:-0 1 4 512}; do
     SRT_LIB=simpleraytracer_amd/lib_diag/libModelRunner.so SRT_EXP=$e run exp_$e 200 rocprofv3 --kernel-trace --stats \
         -d gpurun_out/exp_$e -o run --output-format csv -- python3 bench.py $Q

@@ -6,10 +6,10 @@
 #  * exp_N: the diag build's PrepareBinKernel with SRT_EXP bit N (2: no tile tests / lists,
 #    4: no global list reservations, 512: no screen-box solve), one frame per dispatch.
 source "$(dirname "$0")/gpu_lib.sh"
-Q="--steps 50 --warmup 5 --queues 1 --batch 1 --no-extras --no-cpu-baseline"
+Q="--steps 50 --warmup 5 --queues 1 --batch 1 --no-extras --no-cpu-baseline --full"
 run q1b8 300 rocprofv3 --kernel-trace --stats -d gpurun_out/q1b8 -o run --output-format csv -- \
-    python3 bench.py --steps 400 --warmup 8 --queues 1 --batch 8 --no-extras --no-cpu-baseline
-SRT_LIB=simpleraytracer_amd/lib_ab/setup/libModelRunner.so run setup_only 300 python bench.py --no-extras --no-cpu-baseline
+    python3 bench.py --full --steps 400 --warmup 8 --queues 1 --batch 8 --no-extras --no-cpu-baseline
+SRT_LIB=simpleraytracer_amd/lib_ab/setup/libModelRunner.so run setup_only 300 python bench.py --full --no-extras --no-cpu-baseline
 for e in ${EXPS:-0 2 4 512}; do
     SRT_LIB=simpleraytracer_amd/lib_diag/libModelRunner.so SRT_EXP=$e run exp_$e 200 rocprofv3 --kernel-trace --stats \
         -d gpurun_out/exp_$e -o run --output-format csv -- python3 bench.py $Q

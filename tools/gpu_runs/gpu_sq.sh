@@ -7,7 +7,7 @@ cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 mkdir -p gpurun_out
 export TMPDIR=/tmp
 CNT="SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_WAVES SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_WAIT_INST_ANY SQ_ACTIVE_INST_VALU"
-BENCH=(python3 bench.py --steps 20 --warmup 3 --no-cpu-baseline --no-e2e --brute-steps 0 --queues 1)
+BENCH=(python3 bench.py --full --steps 20 --warmup 3 --no-cpu-baseline --no-e2e --brute-steps 0 --queues 1)
 for cfg in ${CFGS:-product}; do
     case $cfg in
         product) lib=""; exp="" ;;

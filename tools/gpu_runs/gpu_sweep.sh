@@ -9,9 +9,9 @@ for cfg in $CFGS; do
     (
         IFS=','
         for kv in $envs; do [ -n "$kv" ] && export "$kv"; done
-        run bench_$name 300 python bench.py --no-extras --no-cpu-baseline --steps ${STEPS:-3000}
+        run bench_$name 300 python bench.py --full --no-extras --no-cpu-baseline --steps ${STEPS:-3000}
         run prof_$name 300 rocprofv3 --kernel-trace --stats -d gpurun_out/prof_$name -o run --output-format csv -- \
-            python3 bench.py --steps 50 --warmup 5 --queues 1 --no-extras --no-cpu-baseline
+            python3 bench.py --full --steps 50 --warmup 5 --queues 1 --no-extras --no-cpu-baseline
         if [ "${BANDSIM:-0}" = 1 ]; then
             run band_sim_$name 300 python tools/band_sim.py --steps 1000
         fi
