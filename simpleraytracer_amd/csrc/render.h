@@ -296,6 +296,46 @@ hipError_t LaunchCullFrames(const CullFrame* frames, std::size_t count, std::uin
                             const float* d_shade, const Frame& frame, const float background[3], const unsigned* d_rank,
                             hipStream_t stream, const StageEvents* events, const CullTable* table = nullptr);
 
+// The shared cull setup of a prepared frame (DeviceScene: one copy, built once per Prepare). For a
+// whole-frame binned trace (CullFusedInfo) the record pass, the bins and the work plan are a function
+// of the scene, the camera and W x H only: the bin kernel tests every record against the analytic
+// tile boxes, which do not depend on the sample offsets. So they are built once (LaunchCullSetup:
+// the per-frame path's own PrepareBinKernel and WorkOrderKernel, run on this copy) and every later
+// frame runs two launches (LaunchSharedCullFrames): the tile facts of its offsets, and the trace,
+// which reads the setup and never writes it. One allocation of CullSetupBytes, carved by
+// CullSetupLayout; a build zero-fills its first zero_bytes itself.
+struct CullSetup {
+    void* screen_boxes;    // per position: screen box (read by traces that recompute their records)
+    void* qboxes;          // per position: quantized screen box (the FULL stream)
+    void* cull;            // per position: 64-B cull record
+    void* tile_info;       // tiles x 32 B: the analytic tile boxes (the work order's input)
+    unsigned* counts;      // tiles + 1: list lengths, then the large-list length
+    unsigned* range_tag;   // stays zero (no frame of the build is tagged)
+    unsigned* lists;       // tiles x capacity candidate positions
+    unsigned* large_list;  // positions binned to every tile
+    void* work;            // the plan: descs descriptors, heaviest first, facts baked in
+    unsigned* work_count;
+    std::size_t zero_bytes;
+    std::size_t tiles;
+    unsigned capacity;
+    unsigned descs;        // the trace grid the plan was made for
+    unsigned min_chunk;    // smallest candidate chunk of a split part (env SRT_CULL_CHUNK at the carve-up)
+    bool recompute;        // CullBins::recompute of the traces it serves
+};
+std::size_t CullSetupBytes(std::uint64_t n, std::size_t width, std::size_t height, unsigned descs);
+CullSetup CullSetupLayout(void* base, std::uint64_t n, std::size_t width, std::size_t height, unsigned descs,
+                          bool recompute);
+// Builds the setup on `stream`: zero fill, analytic tile info, records + bins, work plan.
+hipError_t LaunchCullSetup(const CullSetup& setup, std::uint64_t n, const Frame& frame, std::size_t width,
+                           std::size_t height, const unsigned* d_order, const float* d_svertices, hipStream_t stream);
+// `count` whole frames on the setup. frames[f].bins: the frame slot's own state -- tile_info (the
+// frame's 16-B tile facts are written there), arrive, split_keys, and descs == setup.descs; edges
+// unused. Events: bin = the tile-facts launch, begin / end = the trace.
+hipError_t LaunchSharedCullFrames(const CullFrame* frames, std::size_t count, const CullSetup& setup, std::uint64_t n,
+                                  const float* d_vertices, const float* d_shade, const Frame& frame,
+                                  const float background[3], hipStream_t stream, const StageEvents* events,
+                                  const CullTable* table = nullptr);
+
 // Deferred shading of a band from hit ids (band.ids) and sample offsets into band.rgba (normals
 // from the vertices, d_edges unused): bit-identical to the fused trace.
 // frames > 1 shades a batch whose ids are band-major, ids[band][frame][band_rows][width] (a

@@ -70,6 +70,19 @@ struct TileInfo {
     unsigned usable;    // box within the screen-box range (else the tile streams every record)
 };
 
+// Per-tile facts of one frame on the shared setup (render.h CullSetup; TileInfoKernel<.., true>),
+// 16 B: what a trace block still needs from its own frame's offsets. The tile box is not among
+// them: the shared lists were binned against the analytic box, which contains the tile's rays
+// exactly when every offset of the tile lies in [0, 1] (kFactInRange).
+constexpr unsigned kFactRegular = 1u;  // every ray of the tile has offset (ox, oy), bit for bit
+constexpr unsigned kFactUsable = 2u;   // the tile's ray box lies within the screen-box range
+constexpr unsigned kFactInRange = 4u;  // every offset of the tile lies in [0, 1] (NaN: outside)
+struct TileFacts {
+    float ox, oy;  // sample offset of the tile's first ray
+    unsigned flags;
+    unsigned pad;
+};
+
 struct TraceParams {
     const float4* __restrict__ edges;
     const float4* __restrict__ screen_boxes;
@@ -98,7 +111,8 @@ struct TraceParams {
     // Cull variant with bins (render.h CullBins); tile_info == null: no bins, every tile
     // computes its own ray box and streams every record.
     const TileInfo* __restrict__ tile_info;   // per tile: ray box, uniform offset (TileInfoKernel)
-    const CullRecord* __restrict__ cull;      // cull records in spatial order (the lists hold positions)
+    const TileFacts* __restrict__ tile_facts; // shared setup: this frame's per-tile facts (work, lists: the setup's)
+    const CullRecord* __restrict__ cull;     // cull records in spatial order (the lists hold positions)
     const unsigned* __restrict__ order;       // spatial-order position -> record id
     const float* __restrict__ svertices;      // vertices by spatial-order position (binned trace: records recomputed)
     const uint4* __restrict__ work;           // tile parts (2 x uint4 each), most work first (BuildWorkOrder)
@@ -1632,6 +1646,7 @@ struct BinParams {
     const float2* __restrict__ offsets;
     const CullRecord* __restrict__ cull;  // cull records in spatial order
     TileInfo* __restrict__ tile_info;
+    TileFacts* __restrict__ tile_facts; // TileInfoKernel<.., true>: the frame's facts instead of tile_info
     unsigned* __restrict__ counts;      // tiles + 1 (the last one: large list)
     unsigned* __restrict__ lists;       // tiles x capacity
     unsigned* __restrict__ large_list;  // n_pad
@@ -1695,6 +1710,9 @@ __device__ void WaveScanOrdered(unsigned* a, int n, bool reverse, int lane) {
 #define SRT_INFO_TILES 2  // 4: one wave per tile, 510 blocks: tile info 5.2 -> 5.6 us, throughput +1 % (noise)
 #endif
 constexpr int kInfoTiles = SRT_INFO_TILES;
+// FACTS: a frame on the shared setup -- the tile's TileFacts (with its own in-range flag) into
+// p.tile_facts instead of the TileInfo, and no frame-wide range tag.
+template <bool FACTS>
 __device__ __forceinline__ void TileInfoBlock(const BinParams& p, int bx, int by) {
     constexpr int kWaves = kBinThreads / kWave;
     constexpr int kInfoWaves = kWaves / kInfoTiles;             // waves per tile
@@ -1703,6 +1721,7 @@ __device__ __forceinline__ void TileInfoBlock(const BinParams& p, int bx, int by
     __shared__ Box boxes[kWaves];
     __shared__ unsigned irregular[kInfoTiles];
     __shared__ unsigned out_of_range;
+    __shared__ unsigned outside[kInfoTiles];  // FACTS: some offset of the tile lies outside [0, 1]
     const int tid = threadIdx.x;
     const int lane = tid & (kWave - 1);
     const int wave = tid / kWave;
@@ -1712,6 +1731,9 @@ __device__ __forceinline__ void TileInfoBlock(const BinParams& p, int bx, int by
     const int y0 = min(ty * kTileRows, p.row_count - 1);
     if (tid < kInfoTiles) {
         irregular[tid] = 0u;
+        if constexpr (FACTS) {
+            outside[tid] = 0u;
+        }
     }
     if (tid == 0) {
         out_of_range = 0u;
@@ -1771,6 +1793,9 @@ __device__ __forceinline__ void TileInfoBlock(const BinParams& p, int bx, int by
         }
         if (!wave_in_range) {
             out_of_range = 1u;
+            if constexpr (FACTS) {
+                outside[sub] = 1u;
+            }
         }
     }
     __syncthreads();
@@ -1782,26 +1807,38 @@ __device__ __forceinline__ void TileInfoBlock(const BinParams& p, int bx, int by
             box = Box{fminf(box.xlo, b.xlo), fmaxf(box.xhi, b.xhi), fminf(box.ylo, b.ylo), fmaxf(box.yhi, b.yhi)};
         }
         box = Box{box.xlo / p.wf, box.xhi / p.wf, box.ylo / p.hf, box.yhi / p.hf};  // the rays' (fx, fy) box
-        TileInfo ti;
-        ti.box = make_float4(box.xlo, box.xhi, box.ylo, box.yhi);
-        ti.ox = o0.x;
-        ti.oy = o0.y;
-        ti.regular = irregular[sub] == 0u ? 1u : 0u;
-        ti.usable = ScreenBoxUsable(box) ? 1u : 0u;
         const unsigned tile = ty * p.tiles_x + bx;
-        p.tile_info[tile] = ti;  // (the bin counts are reset by the work order that reads them)
+        if constexpr (FACTS) {
+            TileFacts tf;
+            tf.ox = o0.x;
+            tf.oy = o0.y;
+            tf.flags = (irregular[sub] == 0u ? kFactRegular : 0u) | (ScreenBoxUsable(box) ? kFactUsable : 0u) |
+                       (outside[sub] == 0u ? kFactInRange : 0u);
+            tf.pad = 0u;
+            p.tile_facts[tile] = tf;
+        } else {
+            TileInfo ti;
+            ti.box = make_float4(box.xlo, box.xhi, box.ylo, box.yhi);
+            ti.ox = o0.x;
+            ti.oy = o0.y;
+            ti.regular = irregular[sub] == 0u ? 1u : 0u;
+            ti.usable = ScreenBoxUsable(box) ? 1u : 0u;
+            p.tile_info[tile] = ti;  // (the bin counts are reset by the work order that reads them)
+        }
     }
-    if (tid == 0 && out_of_range != 0u) {
-        *p.range_tag = p.gen;  // this frame's bin blocks reduce the tile boxes (BinTileBounds)
+    if constexpr (!FACTS) {
+        if (tid == 0 && out_of_range != 0u) {
+            *p.range_tag = p.gen;  // this frame's bin blocks reduce the tile boxes (BinTileBounds)
+        }
     }
 }
 
 using BinBatch = FrameArgs<BinParams>;
 using BinTable = FrameTable<BinParams>;
 
-template <class Frames>
+template <class Frames, bool FACTS = false>
 __global__ __launch_bounds__(kBinThreads) void TileInfoKernel(const Frames batch) {
-    TileInfoBlock(batch[blockIdx.z], blockIdx.x, blockIdx.y);
+    TileInfoBlock<FACTS>(batch[blockIdx.z], blockIdx.x, blockIdx.y);
 }
 
 // Searches in a bin block's monotone tile bounds b[0..n) (lo' = .x, hi' = .y, both
@@ -1903,6 +1940,17 @@ __device__ __forceinline__ void ItemChunks(unsigned cand, unsigned flags, unsign
 //    hi' = prefix maximum) by wave scans.
 // Either way a tile outside a record's searched range cannot overlap its screen box; the tiles
 // inside are tested against their own boxes, so the bins do not depend on which path ran.
+// Analytic bound i of a band's nx + ny tile columns and rows (BinTileBounds' first case).
+__device__ __forceinline__ float2 AnalyticTileBound(const BinParams& p, int i) {
+    const int nx = p.tiles_x;
+    const bool col = i < nx;
+    const int r0 = FrameRow(p.row_begin, p.row_interleave, (i - nx) * kTileRows);  // the tile row's first
+    const float v0 = col ? static_cast<float>(i * kWave) : static_cast<float>(r0);
+    const float v1 = col ? static_cast<float>((i + 1) * kWave) : static_cast<float>(r0 + kTileRows);
+    const float d = col ? p.wf : p.hf;
+    return make_float2(v0 / d, v1 / d);
+}
+
 __device__ void BinTileBounds(const BinParams& p, unsigned* scratch, float2* out) {
     const int tid = threadIdx.x;
     const int nthreads = blockDim.x;
@@ -1911,12 +1959,7 @@ __device__ void BinTileBounds(const BinParams& p, unsigned* scratch, float2* out
     const int nx = p.tiles_x, ny = p.tiles_y;
     if (p.fused != 0u || *p.range_tag != p.gen) {  // tag: written by the previous launch's tile blocks
         for (int i = tid; i < nx + ny; i += nthreads) {
-            const bool col = i < nx;
-            const int r0 = FrameRow(p.row_begin, p.row_interleave, (i - nx) * kTileRows);  // the tile row's first
-            const float v0 = col ? static_cast<float>(i * kWave) : static_cast<float>(r0);
-            const float v1 = col ? static_cast<float>((i + 1) * kWave) : static_cast<float>(r0 + kTileRows);
-            const float d = col ? p.wf : p.hf;
-            out[i] = make_float2(v0 / d, v1 / d);
+            out[i] = AnalyticTileBound(p, i);
         }
         __syncthreads();
         return;
@@ -1960,6 +2003,27 @@ __device__ void BinTileBounds(const BinParams& p, unsigned* scratch, float2* out
         out[i] = make_float2(FromOrderedBits(col ? col_lo[j] : row_lo[j]), FromOrderedBits(col ? col_hi[j] : row_hi[j]));
     }
     __syncthreads();
+}
+
+// The shared setup's tile info (render.h CullSetup): every tile's analytic box, the box the fused
+// bin kernel tests its records against (PrepareBinKernel, p.fused != 0), as the tile info the work
+// order reads -- its empty test then runs against a box that contains the rays of every frame whose
+// offsets of that tile lie in [0, 1]. `regular` and the offset are placeholders: a trace on the
+// shared setup takes them from its own frame's TileFacts.
+__global__ __launch_bounds__(256) void SetupTileInfoKernel(BinParams p) {
+    const int t = static_cast<int>(blockIdx.x * 256u + threadIdx.x);
+    if (t >= p.tiles_x * p.tiles_y) {
+        return;
+    }
+    const float2 bx = AnalyticTileBound(p, t % p.tiles_x), by = AnalyticTileBound(p, p.tiles_x + t / p.tiles_x);
+    const Box box{bx.x, bx.y, by.x, by.y};
+    TileInfo ti;
+    ti.box = make_float4(box.xlo, box.xhi, box.ylo, box.yhi);
+    ti.ox = 0.f;
+    ti.oy = 0.f;
+    ti.regular = 1u;
+    ti.usable = ScreenBoxUsable(box) ? 1u : 0u;
+    p.tile_info[t] = ti;
 }
 
 // LDS of a bin block (dynamic, sized to the band so the bin blocks of one frame leave room for
@@ -2097,7 +2161,7 @@ __global__ __launch_bounds__(kBinThreads) void PrepareBinKernel(const Frames bat
         const unsigned rec_blocks = (pp.n_pad + kBinThreads - 1) / kBinThreads;
         if (blockIdx.x >= rec_blocks) {
             const unsigned k = blockIdx.x - rec_blocks;
-            TileInfoBlock(p, static_cast<int>(k % static_cast<unsigned>(p.tiles_x)),
+            TileInfoBlock<false>(p, static_cast<int>(k % static_cast<unsigned>(p.tiles_x)),
                           static_cast<int>(k / static_cast<unsigned>(p.tiles_x)));
             SRT_SETUP_MARK(kDiagBinRow + blockIdx.x, 1);
             return;
@@ -2606,7 +2670,11 @@ struct TraceRecords<true> {
     }
 };
 
-template <class Frames, bool RC = false>
+// SHARED: the frame runs on the scene's shared setup (render.h CullSetup): p.work is the setup's
+// plan, whose descriptors hold the tile's candidate count, list length, chunking, and the FULL
+// (unusable analytic box, overflowed list) and empty flags; p.bin_lists, p.large_list and the
+// records are the setup's and read-only (no count is reset); p.tile_facts holds this frame's facts.
+template <class Frames, bool RC = false, bool SHARED = false>
 __global__ __launch_bounds__(kCullThreads, SRT_TRACE_OCC) void TraceCullKernel(const Frames batch) {
     const TraceParams& p = batch[blockIdx.z];
     using Recs = TraceRecords<RC>;
@@ -2657,15 +2725,30 @@ __global__ __launch_bounds__(kCullThreads, SRT_TRACE_OCC) void TraceCullKernel(c
         const unsigned t = item / kParts;
         // The slot's next frame bins into the other count buffer: each tile's count reset by its
         // first part's first chunk, the large list's by the first descriptor.
-        if (threadIdx.x == 0 && chunk == 0u && item % kParts == 0u) {
-            p.bin_counts_next[t] = 0u;
-        }
-        if (threadIdx.x == 0 && d == 0u) {
-            p.bin_counts_next[p.tiles] = 0u;
+        if constexpr (!SHARED) {
+            if (threadIdx.x == 0 && chunk == 0u && item % kParts == 0u) {
+                p.bin_counts_next[t] = 0u;
+            }
+            if (threadIdx.x == 0 && d == 0u) {
+                p.bin_counts_next[p.tiles] = 0u;
+            }
         }
         bool full;
         unsigned c_t, list_len;
-        if (p.plan_only != 0u) {
+        if constexpr (SHARED) {
+            // The tile's list is valid exactly when this frame's offsets of the tile lie in [0, 1]
+            // (the analytic box it was binned against then contains the tile's rays); otherwise, and
+            // for an unusable box, the tile streams every record, as a plan-only frame's would, and
+            // the setup's empty flag (made for rays inside the analytic box) does not hold.
+            const TileFacts tf = p.tile_facts[t];
+            constexpr unsigned kValid = kFactUsable | kFactInRange;
+            full = (w0.w & kItemFull) != 0u || (tf.flags & kValid) != kValid;
+            flags = (full ? kItemFull : (w0.w & kItemEmpty)) | ((tf.flags & kFactRegular) != 0u ? kItemRegular : 0u);
+            ox = tf.ox;
+            oy = tf.oy;
+            c_t = full ? 0u : w0.y;
+            list_len = full ? 0u : w0.z;
+        } else if (p.plan_only != 0u) {
             // This frame's facts, which the order kernel would have put in the descriptor.
             const unsigned cnt = p.bin_counts[t], large = p.bin_counts[p.tiles];
             const TileInfo ti = p.tile_info[t];
@@ -3603,10 +3686,9 @@ CullBins CullBinLayout(void* base, std::uint64_t n, std::size_t width, std::size
 }
 
 namespace {
-TraceParams MakeTraceParams(const float* d_edges, std::uint64_t n, const float* d_vertices, const float* d_shade,
+TraceParams MakeTraceParams(const EdgeLayout& e, std::uint64_t n, const float* d_vertices, const float* d_shade,
                             const Frame& frame, const float background[3], const BandArgs& band) {
     TraceParams p{};
-    const EdgeLayout e = EdgeBuffers(d_edges, n);
     p.edges = e.tiles;
     p.screen_boxes = e.screen_boxes;
     p.qboxes = e.qboxes;
@@ -3803,7 +3885,7 @@ hipError_t LaunchCullFrames(const CullFrame* frames, std::size_t count, std::uin
             f.bins->recompute != frames[0].bins->recompute) {
             return hipErrorInvalidValue;  // one band shape per batch (its first row may differ per frame)
         }
-        tp[i] = MakeTraceParams(f.edges, n, d_vertices, d_shade, frame, background, f.band);
+        tp[i] = MakeTraceParams(EdgeBuffers(f.edges, n), n, d_vertices, d_shade, frame, background, f.band);
         if (f.bins->tiles != tp[i].tiles) {
             return hipErrorInvalidValue;  // bins sized for another band shape
         }
@@ -3861,6 +3943,240 @@ hipError_t LaunchCullFrames(const CullFrame* frames, std::size_t count, std::uin
     return hipGetLastError();
 }
 
+namespace {
+struct SetupSizes {
+    std::size_t counts, range_tag, work_count, info, screen_boxes, qboxes, cull, lists, large, work;
+};
+SetupSizes CullSetupSizes(std::uint64_t n, std::size_t width, std::size_t height, unsigned descs) {
+    const std::size_t tiles = CullTiles(width, height), n_pad = PaddedTriangleCount(n);
+    const auto al = [](std::size_t b) { return (b + 255) / 256 * 256; };
+    SetupSizes z;
+    z.counts = al((tiles + 1) * 4);
+    z.range_tag = al(4);
+    z.work_count = al(kOrderWords * 4);
+    z.info = al(tiles * sizeof(TileInfo));
+    z.screen_boxes = al(n_pad * sizeof(float4));
+    z.qboxes = al(n_pad * sizeof(uint2));
+    z.cull = al(n_pad * sizeof(CullRecord));
+    z.lists = al(tiles * static_cast<std::size_t>(CullBinCapacity(n, tiles)) * 4);
+    z.large = al(n_pad * 4);
+    z.work = al(static_cast<std::size_t>(descs) * 2 * sizeof(uint4));
+    return z;
+}
+}  // namespace
+
+std::size_t CullSetupBytes(std::uint64_t n, std::size_t width, std::size_t height, unsigned descs) {
+    const SetupSizes z = CullSetupSizes(n, width, height, descs);
+    return z.counts + z.range_tag + z.work_count + z.info + z.screen_boxes + z.qboxes + z.cull + z.lists + z.large +
+           z.work;
+}
+
+CullSetup CullSetupLayout(void* base, std::uint64_t n, std::size_t width, std::size_t height, unsigned descs,
+                          bool recompute) {
+    const SetupSizes z = CullSetupSizes(n, width, height, descs);
+    unsigned char* w = static_cast<unsigned char*>(base);
+    auto take = [&w](std::size_t bytes) {
+        unsigned char* at = w;
+        w += bytes;
+        return at;
+    };
+    CullSetup s{};
+    // The counts and the range tag first: the bytes a build zero-fills (zero_bytes).
+    s.counts = reinterpret_cast<unsigned*>(take(z.counts));
+    s.range_tag = reinterpret_cast<unsigned*>(take(z.range_tag));
+    s.zero_bytes = z.counts + z.range_tag;
+    s.work_count = reinterpret_cast<unsigned*>(take(z.work_count));
+    s.tile_info = take(z.info);
+    s.screen_boxes = take(z.screen_boxes);
+    s.qboxes = take(z.qboxes);
+    s.cull = take(z.cull);
+    s.lists = reinterpret_cast<unsigned*>(take(z.lists));
+    s.large_list = reinterpret_cast<unsigned*>(take(z.large));
+    s.work = take(z.work);
+    s.tiles = CullTiles(width, height);
+    s.capacity = CullBinCapacity(n, s.tiles);
+    s.descs = descs;
+    s.min_chunk = CullChunkFromEnv();
+    s.recompute = recompute;
+    return s;
+}
+
+namespace {
+EdgeLayout SetupRecords(const CullSetup& s) {
+    EdgeLayout e{};
+    e.tiles = nullptr;  // the tile-planar records belong to the lds / scalar variants (edge slot 0)
+    e.screen_boxes = static_cast<float4*>(s.screen_boxes);
+    e.qboxes = static_cast<uint2*>(s.qboxes);
+    e.cull = static_cast<CullRecord*>(s.cull);
+    return e;
+}
+}  // namespace
+
+hipError_t LaunchCullSetup(const CullSetup& s, std::uint64_t n, const Frame& frame, std::size_t width,
+                           std::size_t height, const unsigned* d_order, const float* d_svertices, hipStream_t stream) {
+    if (width == 0 || height == 0 || !CullBinnable(width, height) || d_order == nullptr || d_svertices == nullptr ||
+        s.tiles != CullTiles(width, height)) {
+        return hipErrorInvalidValue;
+    }
+    const hipError_t zeroed = hipMemsetAsync(s.counts, 0, s.zero_bytes, stream);
+    if (zeroed != hipSuccess) {
+        return zeroed;
+    }
+    const EdgeLayout e = SetupRecords(s);
+    BinParams b{};
+    b.cull = e.cull;
+    b.tile_info = static_cast<TileInfo*>(s.tile_info);
+    b.counts = s.counts;
+    b.lists = s.lists;
+    b.large_list = s.large_list;
+    b.work = static_cast<uint4*>(s.work);
+    b.work_count = s.work_count;
+    b.range_tag = s.range_tag;  // zero, never written: no frame is tagged
+    b.gen = 1u;
+    b.capacity = s.capacity;
+    b.descs = s.descs;
+    b.min_chunk = s.min_chunk;
+    b.n = static_cast<unsigned>(n);
+    b.fused = 1u;  // analytic tile bounds, every record needed
+    b.recompute = s.recompute ? 1u : 0u;
+    b.tiles_x = static_cast<int>((width + kWave - 1) / kWave);
+    b.tiles_y = static_cast<int>((height + kTileRows - 1) / kTileRows);
+    b.width = static_cast<int>(width);
+    b.row_count = static_cast<int>(height);
+    b.row_begin = 0;
+    b.row_interleave = 1;
+    b.wf = static_cast<float>(width);
+    b.hf = static_cast<float>(height);
+    PrepareBinBatch pb{};
+    pb.f[0].prep = MakePrepareParams(nullptr, nullptr, n, frame, nullptr);
+    pb.f[0].prep.edges = e.tiles;
+    pb.f[0].prep.screen_boxes = e.screen_boxes;
+    pb.f[0].prep.qboxes = e.qboxes;
+    pb.f[0].prep.cull = e.cull;
+    pb.f[0].prep.order = d_order;
+    pb.f[0].prep.svertices = d_svertices;
+    b.exp = pb.f[0].prep.exp;
+    pb.f[0].bin = b;
+    BinBatch bb{};
+    bb.f[0] = b;
+    const unsigned gx = static_cast<unsigned>(b.tiles_x), gy = static_cast<unsigned>(b.tiles_y);
+    const unsigned tiles = gx * gy;
+    hipLaunchKernelGGL(SetupTileInfoKernel, dim3((tiles + 255) / 256), dim3(256), 0, stream, b);
+    // The record blocks alone (no tile-info blocks: the grid ends with the records).
+    LaunchLds(PrepareBinKernel<PrepareBinBatch, false>, dim3((pb.f[0].prep.n_pad + kBinThreads - 1) / kBinThreads, 1, 1),
+              dim3(kBinThreads), BinLdsBytes(b.tiles_x, b.tiles_y), stream, nullptr, nullptr, pb);
+    LaunchLds(WorkOrderKernel<BinBatch>, dim3((tiles + kOrderBlock - 1) / kOrderBlock, 1, 1), dim3(kOrderBlock),
+              OrderLdsBytes(static_cast<int>(tiles)), stream, nullptr, nullptr, bb);
+    return hipGetLastError();
+}
+
+namespace {
+// The two launches of a frame set on the shared setup: tile facts, trace.
+template <class TB, class BB>
+void LaunchSharedStages(const TB& tb, const BB& bb, unsigned z, unsigned gx, unsigned gy, bool recompute,
+                        unsigned descs, hipStream_t stream, const StageEvents& ev) {
+    Launch(TileInfoKernel<BB, true>, dim3(gx, (gy + kInfoTiles - 1) / kInfoTiles, z), dim3(kBinThreads), stream,
+           ev.bin_begin, ev.bin_end, bb);
+    if (recompute) {
+        Launch(TraceCullKernel<TB, true, true>, dim3(descs, 1, z), dim3(kWave * kCullWaves), stream, ev.begin, ev.end, tb);
+    } else {
+        Launch(TraceCullKernel<TB, false, true>, dim3(descs, 1, z), dim3(kWave * kCullWaves), stream, ev.begin, ev.end, tb);
+    }
+}
+}  // namespace
+
+hipError_t LaunchSharedCullFrames(const CullFrame* frames, std::size_t count, const CullSetup& setup, std::uint64_t n,
+                                  const float* d_vertices, const float* d_shade, const Frame& frame,
+                                  const float background[3], hipStream_t stream, const StageEvents* events,
+                                  const CullTable* table) {
+    const bool use_table = count > static_cast<std::size_t>(kMaxBatch);
+    if (frames == nullptr || count == 0 || count > static_cast<std::size_t>(kMaxTableFrames) ||
+        (use_table && (table == nullptr || table->device == nullptr || table->host == nullptr ||
+                       count > table->frames))) {
+        return hipErrorInvalidValue;
+    }
+    const BandArgs& band0 = frames[0].band;
+    if (band0.row_begin != 0 || band0.row_count != band0.height || band0.row_interleave != 1 || band0.width == 0 ||
+        band0.height == 0 || !CullBinnable(band0.width, band0.row_count) ||
+        setup.tiles != CullTiles(band0.width, band0.row_count)) {
+        return hipErrorInvalidValue;  // whole frames of the setup's shape only
+    }
+    const StageEvents ev = events != nullptr ? *events : StageEvents{};
+    TraceBatch tb{};
+    BinBatch bb{};
+    const TableLayout lay = MakeTableLayout(count);
+    unsigned char* host = use_table ? static_cast<unsigned char*>(table->host) : nullptr;
+    BinParams* bp = use_table ? reinterpret_cast<BinParams*>(host + lay.bin) : bb.f;
+    TraceParams* tp = use_table ? reinterpret_cast<TraceParams*>(host + lay.trace) : tb.f;
+    if (use_table) {
+        std::memset(host + lay.prep, 0, lay.bin - lay.prep);  // (no record pass: uploaded, never read)
+    }
+    const EdgeLayout e = SetupRecords(setup);
+    for (std::size_t i = 0; i < count; ++i) {
+        const CullFrame& f = frames[i];
+        if (f.bins == nullptr || f.bins->order == nullptr || f.bins->svertices == nullptr ||
+            f.bins->tile_info == nullptr || f.band.width != band0.width || f.band.height != band0.height ||
+            f.band.row_begin != 0 || f.band.row_count != band0.row_count || f.band.row_interleave != 1 ||
+            f.bins->tiles != setup.tiles || f.bins->descs != setup.descs) {
+            return hipErrorInvalidValue;
+        }
+        TraceParams& p = tp[i];
+        p = MakeTraceParams(e, n, d_vertices, d_shade, frame, background, f.band);
+        // The frame slot's own (mutable) state: tile facts, split key slices, arrival counters.
+        p.tile_facts = static_cast<const TileFacts*>(f.bins->tile_info);
+        p.split_keys = static_cast<unsigned long long*>(f.bins->split_keys);
+        p.arrive = f.bins->arrive;
+        // The setup's (read-only): plan, lists, records.
+        p.order = f.bins->order;
+        p.svertices = f.bins->svertices;
+        p.work = static_cast<const uint4*>(setup.work);
+        p.work_count = setup.work_count;
+        p.bin_lists = setup.lists;
+        p.large_list = setup.large_list;
+        p.bin_capacity = setup.capacity;
+        BinParams& b = bp[i];
+        b = BinParams{};
+        b.offsets = p.offsets;
+        b.tile_facts = static_cast<TileFacts*>(f.bins->tile_info);
+        b.tiles_x = p.tiles_x;
+        b.tiles_y = static_cast<int>(p.tiles / static_cast<unsigned>(p.tiles_x));
+        b.width = p.width;
+        b.row_count = p.row_count;
+        b.row_begin = p.row_begin;
+        b.row_interleave = p.row_interleave;
+        b.wf = p.wf;
+        b.hf = p.hf;
+        b.exp = p.exp;
+    }
+    const unsigned z = static_cast<unsigned>(count);
+    const unsigned gx = static_cast<unsigned>(tp[0].tiles_x), gy = tp[0].tiles / gx;
+    if (!use_table) {
+        LaunchSharedStages(tb, bb, z, gx, gy, setup.recompute, setup.descs, stream, ev);
+        return hipGetLastError();
+    }
+    if (table->host_device != nullptr) {
+        const std::size_t n16 = (lay.bytes + 15) / 16;
+        hipLaunchKernelGGL(UploadTableKernel, dim3(static_cast<unsigned>((n16 + 255) / 256)), dim3(256), 0, stream,
+                           static_cast<const uint4*>(table->host_device), static_cast<uint4*>(table->device), n16);
+    } else {
+        const hipError_t up = hipMemcpyAsync(table->device, table->host, lay.bytes, hipMemcpyHostToDevice, stream);
+        if (up != hipSuccess) {
+            return up;
+        }
+    }
+    if (table->uploaded != nullptr) {
+        const hipError_t rec = hipEventRecord(table->uploaded, stream);
+        if (rec != hipSuccess) {
+            return rec;
+        }
+    }
+    unsigned char* dev = static_cast<unsigned char*>(table->device);
+    const BinTable bt{(ConstantPtr<BinParams>)(dev + lay.bin)};
+    const TraceTable tt{(ConstantPtr<TraceParams>)(dev + lay.trace)};
+    LaunchSharedStages(tt, bt, z, gx, gy, setup.recompute, setup.descs, stream, ev);
+    return hipGetLastError();
+}
+
 hipError_t LaunchTrace(const float* d_edges, std::uint64_t n, const float* d_vertices, const float* d_shade,
                        const Frame& frame, const float background[3], const BandArgs& band, int variant,
                        const CullBins* bins, hipStream_t stream, const StageEvents* events,
@@ -3880,7 +4196,7 @@ hipError_t LaunchTrace(const float* d_edges, std::uint64_t n, const float* d_ver
             return e;
         }
     }
-    const TraceParams p = MakeTraceParams(d_edges, n, d_vertices, d_shade, frame, background, band);
+    const TraceParams p = MakeTraceParams(EdgeBuffers(d_edges, n), n, d_vertices, d_shade, frame, background, band);
     const unsigned gx = static_cast<unsigned>(p.tiles_x);
     if (variant == kTraceBvh) {
         if (bvh == nullptr) {

@@ -3,6 +3,7 @@
 #include <rccl/rccl.h>
 
 #include <algorithm>
+#include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <sstream>
@@ -168,6 +169,7 @@ DeviceScene::~DeviceScene() {
     (void)hipFree(m_rank);
     (void)hipFree(m_svertices);
     (void)hipFree(m_block_ext);
+    (void)hipFree(m_setup);
     for (CullArena& a : m_arenas) {
         (void)hipFree(a.work);
     }
@@ -203,7 +205,11 @@ void DeviceScene::Prepare(std::size_t width, std::size_t height, hipStream_t str
     if (width != m_width || height != m_height) {
         DropPlans(~std::size_t{0});  // (a plan is scheduling only; a new shape deserves a new one)
     }
-    m_frame = MakeFrame(m_camera, width, height);
+    const Frame frame = MakeFrame(m_camera, width, height);
+    if (width != m_width || height != m_height || std::memcmp(&frame, &m_frame, sizeof(Frame)) != 0) {
+        m_setup_pending = true;  // the shared cull setup is a function of this frame (EnsureSetup's key: the rest)
+    }
+    m_frame = frame;
     m_width = width;
     m_height = height;
     // Deferred: the next Trace enqueues the record setup on its stream (the binned cull path
@@ -478,6 +484,12 @@ void DeviceScene::TraceBatch(const float* const* d_offsets, float* const* d_rgba
         }
         return;
     }
+    if (row_begins == nullptr && OnSharedSetup(row_begin, row_count, row_interleave)) {
+        TraceShared(d_offsets, d_rgba, d_ids, frames, stream, id_planes, rgba_frame_rows);
+        return;
+    }
+    m_setup_stats.per_frame_frames += frames;
+    LogSetupStats();
     OrderAfterPrevious(stream);
     EnsureEdgeSlots(frames, stream);
     EnsureCullWork(frames, row_count, stream);
@@ -531,12 +543,21 @@ void DeviceScene::Trace(const float* d_offsets, float* d_rgba, std::size_t row_b
     if (!BandFits(row_begin, row_count, row_interleave, m_height)) {
         throw std::runtime_error("Trace: row band outside the frame");
     }
+    const bool binned = variant == kTraceCull && row_count != 0 && CullBinningEnabled() && CullBinnable(m_width, row_count);
+    if (binned && OnSharedSetup(row_begin, row_count, row_interleave)) {
+        float* const rgba1[1] = {d_rgba};
+        int* const ids1[1] = {d_ids};
+        TraceShared(&d_offsets, rgba1, d_ids != nullptr ? ids1 : nullptr, 1, stream, id_planes, rgba_frame_rows);
+        return;
+    }
     OrderAfterPrevious(stream);
     BandArgs band{d_offsets, d_rgba, m_width, m_height, row_begin, row_count, d_ids, row_interleave, id_planes,
                   rgba_frame_rows};
     CullBins bins{};
     const CullBins* use_bins = nullptr;
-    if (variant == kTraceCull && row_count != 0 && CullBinningEnabled() && CullBinnable(m_width, row_count)) {
+    if (binned) {
+        ++m_setup_stats.per_frame_frames;
+        LogSetupStats();
         EnsureCullWork(1, row_count, stream);
         EnsureBlockExtents(stream);
         bins = CullSlot(0, row_count);
@@ -639,6 +660,98 @@ bool DeviceScene::RecomputeRecords(std::size_t frames) const {
     const int env = RecordModeFromEnv();
     const int mode = env >= 0 ? env : m_records;
     return mode == kRecordsRecompute || (mode == kRecordsAuto && frames == 1);
+}
+
+// SRT_SETUP = prepare (default) | frame, read per call (like SRT_TRACE_RECORDS): `prepare` runs the
+// whole-frame binned traces on the shared setup; `frame` keeps the per-frame setup for every band.
+// The shared setup serves the bands whose bin launch ignores the offsets already: whole frames with
+// the tile info fused into it (CullFusedInfo).
+bool DeviceScene::OnSharedSetup(std::size_t row_begin, std::size_t row_count, std::size_t row_interleave) const {
+    const char* e = std::getenv("SRT_SETUP");
+    const std::string v = e == nullptr || *e == '\0' ? "prepare" : e;
+    if (v != "prepare" && v != "frame") {
+        throw std::runtime_error("SRT_SETUP must be prepare or frame, got '" + v + "'");
+    }
+    return v == "prepare" && row_begin == 0 && row_count == m_height && row_interleave == 1 &&
+           CullFusedInfo(row_begin, row_count, m_height, row_interleave);
+}
+
+// Env SRT_SETUP_LOG (read per call; unset, empty or "0": off): after every binned cull call one line on
+// stderr with the scene's counters so far -- what tells a run on the shared setup from a silent
+// per-frame one (tests/test_gpu_shared_setup.py; the C ABI has no entry for them).
+void DeviceScene::LogSetupStats() const {
+    const char* e = std::getenv("SRT_SETUP_LOG");
+    if (e == nullptr || *e == '\0' || std::strcmp(e, "0") == 0) {
+        return;
+    }
+    std::fprintf(stderr, "srt setup: scene %p builds %llu shared_frames %llu per_frame_frames %llu\n",
+                 static_cast<const void*>(this), m_setup_stats.builds, m_setup_stats.shared_frames,
+                 m_setup_stats.per_frame_frames);
+    std::fflush(stderr);
+}
+
+void DeviceScene::TraceShared(const float* const* d_offsets, float* const* d_rgba, int* const* d_ids,
+                              std::size_t frames, hipStream_t stream, int id_planes, bool rgba_frame_rows) const {
+    OrderAfterPrevious(stream);
+    // The frame slots' own state (tile facts, split key slices, arrival counters) lives in the cull
+    // work of the whole-frame shape; no edge slots: the records are the setup's.
+    EnsureCullWork(frames, m_height, stream);
+    const CullArena& a = m_arenas.at(m_arena);
+    const std::size_t tiles = CullTiles(m_width, m_height);
+    std::vector<CullBins> bins(frames);
+    std::vector<CullFrame> cf(frames);
+    for (std::size_t f = 0; f < frames; ++f) {
+        // (not CullSlot: the slot's count parity and its per-frame plan stay as the per-frame path left them)
+        bins[f] = CullBinLayout(a.work + f * a.layout, m_n, m_width, m_height);
+        bins[f].descs = std::min(bins[f].descs, CullDescriptors(tiles, frames));
+        bins[f].order = m_order;
+        bins[f].svertices = m_svertices;
+        cf[f].edges = nullptr;
+        cf[f].bins = &bins[f];
+        cf[f].band = BandArgs{d_offsets[f], d_rgba != nullptr ? d_rgba[f] : nullptr, m_width, m_height, 0, m_height,
+                              d_ids != nullptr ? d_ids[f] : nullptr, 1, id_planes, rgba_frame_rows};
+    }
+    // Stored records unless the env asks for recomputed ones: the engine's one-queue hint
+    // (SetRecordMode) shortened a bin launch that this path does not run.
+    const bool recompute = RecordModeFromEnv() == static_cast<int>(kRecordsRecompute);
+    const unsigned descs = bins[0].descs;
+    const std::size_t bytes = CullSetupBytes(m_n, m_width, m_height, descs);
+    if (bytes > m_setup_bytes) {
+        // (earlier readers of the old copy ran before this stream's end: OrderAfterPrevious)
+        HipCheck(hipStreamSynchronize(stream), "hipStreamSynchronize(cull setup)");
+        (void)hipFree(m_setup);
+        m_setup = nullptr;
+        m_setup_bytes = 0;
+        m_setup = DeviceAlloc<unsigned char>(bytes, "hipMalloc(cull setup)");
+        m_setup_bytes = bytes;
+        m_setup_pending = true;
+    }
+    const CullSetup setup = CullSetupLayout(m_setup, m_n, m_width, m_height, descs, recompute);
+    const SetupKey key{m_width, m_height, setup.capacity, setup.descs, setup.min_chunk, setup.recompute};
+    const SetupKey& k = m_setup_key;
+    if (m_setup_pending || key.width != k.width || key.height != k.height || key.capacity != k.capacity ||
+        key.descs != k.descs || key.min_chunk != k.min_chunk || key.recompute != k.recompute) {
+        m_setup_pending = true;  // (a failed build leaves none)
+        HipCheck(LaunchCullSetup(setup, m_n, m_frame, m_width, m_height, m_order, m_svertices, stream),
+                 "cull setup launch");
+        m_setup_key = key;
+        m_setup_pending = false;
+        ++m_setup_stats.builds;
+    }
+    const StageEvents ev = BindStageEvents(false, true);
+    ParamTable* table = frames > static_cast<std::size_t>(kMaxBatch) ? &AcquireTable(frames, stream) : nullptr;
+    const CullTable ct{table != nullptr ? table->device : nullptr, table != nullptr ? table->host : nullptr,
+                       table != nullptr ? table->frames : 0, table != nullptr ? table->host_device : nullptr,
+                       table != nullptr ? table->uploaded : nullptr};
+    HipCheck(LaunchSharedCullFrames(cf.data(), frames, setup, m_n, m_vertices, m_shade, m_frame, m_background, stream,
+                                    m_timing ? &ev : nullptr, table != nullptr ? &ct : nullptr),
+             "shared-setup trace launch");
+    if (table != nullptr) {
+        table->pending = true;  // (LaunchSharedCullFrames recorded `uploaded` after the upload)
+    }
+    m_setup_stats.shared_frames += frames;
+    LogSetupStats();
+    RecordOrder(stream);
 }
 
 DeviceScene::StageTimes DeviceScene::TakeTimes() {

@@ -92,6 +92,8 @@ public:
     // bins, work list, trace), as `frames` Prepare + Trace calls would; the cull variant runs all
     // frames in one launch per stage (render.h LaunchCullFrames; more than kMaxBatch frames read
     // their parameters from a device table uploaded once per call), the others frame by frame.
+    // Whole frames of the binned cull variant run on the shared setup instead (below; env SRT_SETUP):
+    // the record setup, bins and work plan once per prepared frame, tile facts + trace per frame.
     void TraceBatch(const float* const* d_offsets, float* const* d_rgba, int* const* d_ids, std::size_t frames,
                     std::size_t row_begin, std::size_t row_count, int variant, hipStream_t stream,
                     std::size_t row_interleave = 1, int id_planes = -1, bool rgba_frame_rows = false,
@@ -113,7 +115,8 @@ public:
     struct StageTimes {
         unsigned launches = 0;     // timed Trace calls
         double prepare_ms = 0.0;   // PrepareKernel (mean over timed Prepare calls)
-        double bin_ms = 0.0;       // bin stage (cull: BinTriangles start .. WorkOrder end); 0 otherwise
+        double bin_ms = 0.0;       // bin stage (cull: BinTriangles start .. WorkOrder end; on the shared setup
+                                   // the per-frame tile-facts launch, the one-off build uncounted); 0 otherwise
         double kernel_ms = 0.0;    // the trace kernel alone
     };
     void SetTiming(bool on);
@@ -121,6 +124,16 @@ public:
     // Records of the binned traces (render.h RecordMode; the env SRT_TRACE_RECORDS overrides it):
     // the frame engine sets kRecordsRecompute when it keeps one frame queue per device.
     void SetRecordMode(int mode);
+    // Which setup the binned cull traces ran on (env SRT_SETUP, read per call): builds of the shared
+    // setup, frames traced on it, frames traced with a per-frame setup (the bin launch of
+    // bands, per-frame row_begins and SRT_SETUP=frame). The other variants and the unbinned cull
+    // trace count in none of them. Env SRT_SETUP_LOG=1 prints them to stderr after every such call.
+    struct SetupStats {
+        unsigned long long builds = 0;
+        unsigned long long shared_frames = 0;
+        unsigned long long per_frame_frames = 0;
+    };
+    SetupStats setup_stats() const { return m_setup_stats; }
 
 private:
     int m_device;
@@ -141,6 +154,28 @@ private:
     mutable float2* m_block_ext = nullptr;
     mutable bool m_ext_pending = true;
     void EnsureBlockExtents(hipStream_t stream) const;
+    // The shared cull setup of the prepared frame (render.h CullSetup): records, bins and work plan
+    // of a whole-frame binned trace, which depend on the scene, the camera and W x H only. Its own
+    // buffers (edge slot 0 belongs to the record passes of the other variants). Built on the stream
+    // of the first such trace after a Prepare that changed the frame (m_setup_pending), and again
+    // whenever what shapes it changed (m_setup_key); calls on one scene are stream-ordered
+    // (OrderAfterPrevious), so later traces on any stream see it complete.
+    struct SetupKey {
+        std::size_t width = 0, height = 0;
+        unsigned capacity = 0, descs = 0, min_chunk = 0;
+        bool recompute = false;
+    };
+    mutable unsigned char* m_setup = nullptr;
+    mutable std::size_t m_setup_bytes = 0;
+    mutable bool m_setup_pending = true;
+    mutable SetupKey m_setup_key{};
+    mutable SetupStats m_setup_stats{};
+    void LogSetupStats() const;
+    // Whether a binned cull trace of this band runs on the shared setup (env SRT_SETUP).
+    bool OnSharedSetup(std::size_t row_begin, std::size_t row_count, std::size_t row_interleave) const;
+    // Whole frames on the shared setup: the setup (re)built if need be, then tile facts + trace.
+    void TraceShared(const float* const* d_offsets, float* const* d_rgba, int* const* d_ids, std::size_t frames,
+                     hipStream_t stream, int id_planes, bool rgba_frame_rows) const;
     Frame m_frame{};
     std::size_t m_width = 0;
     std::size_t m_height = 0;
