@@ -1,4 +1,4 @@
-"""ctypes binding of libModelRunner.so (include/model_runner.h + include/srt_render.h).
+"""ctypes binding of libModelRunner.so (include/model_runner.h + include/srt_render.h + include/srt_query.h).
 
 The shared library is built in-tree by ``make`` (or ``__graft_entry__.build()``) into
 ``simpleraytracer_amd/lib/libModelRunner.so``. There is no fallback: importing the renderer
@@ -161,6 +161,12 @@ _SIGNATURES = {
     "srtExchangeHostShare": (ctypes.c_int, [ctypes.POINTER(ctypes.c_void_p), _SZ, _SZ, _SZ, _SZ, _SZ, _SZ,
                                             ctypes.POINTER(ctypes.c_void_p), _PSZ, _PSZ]),
     "srtScreenBoxHost": (ctypes.c_int, [ctypes.POINTER(ctypes.c_float), ctypes.c_int, ctypes.POINTER(ctypes.c_float)]),
+    # include/srt_query.h: point queries
+    "rtqQueryAsync": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, _SZ, ctypes.c_void_p, ctypes.c_void_p,
+                                     ctypes.c_void_p, ctypes.c_void_p]),
+    "rtqQueryHost": (ctypes.c_int, [ctypes.c_char_p, _SZ, _SZ, ctypes.c_void_p, _SZ, ctypes.c_void_p, ctypes.c_void_p]),
+    "rtqTileHost": (ctypes.c_int, [_SZ, _SZ, ctypes.c_float, ctypes.c_float, ctypes.POINTER(ctypes.c_int),
+                                   ctypes.POINTER(ctypes.c_int)]),
 }
 
 _lib = None

@@ -189,6 +189,40 @@ bool HostScreenBox(const float c[9], int mode, float box[4]) {
     return true;
 }
 
+void HostClosestHits(const Scene& scene, std::size_t width, std::size_t height, const float* positions,
+                     std::size_t count, int* ids, float* t) {
+    if (width == 0 || height == 0) {
+        throw std::runtime_error("Host query: frame dimensions must be non-zero");
+    }
+    const Frame f = MakeFrame(scene.camera, width, height);
+    const std::size_t n = scene.triangle_count();
+    std::vector<Rec> recs(n);
+    ParallelFor(n, 1024, [&](std::size_t i) { recs[i] = MakeRecord(scene.vertices.data() + 9 * i, f); });
+    ParallelFor(count, 64, [&](std::size_t q) {
+        const float px = positions[2 * q], py = positions[2 * q + 1];
+        float best = std::numeric_limits<float>::infinity();
+        int id = -1;
+        for (std::size_t k = 0; k < n; ++k) {  // ascending ids: strict < keeps the lowest on ties
+            const float* c = recs[k].c;
+            const float eA = std::fma(py, c[2], std::fma(px, c[1], c[0]));
+            const float eB = std::fma(py, c[5], std::fma(px, c[4], c[3]));
+            const float eC = std::fma(py, c[8], std::fma(px, c[7], c[6]));
+            if (eA >= 0.f && eB >= 0.f && eC >= 0.f) {
+                const float det = (eA + eB) + eC;
+                if (det > 0.f) {
+                    const float tt = recs[k].vol / det;
+                    if (tt < best) {
+                        best = tt;
+                        id = static_cast<int>(k);
+                    }
+                }
+            }
+        }
+        ids[q] = id;
+        t[q] = best;
+    });
+}
+
 bool CpuBackendSelected() {
     const char* v = std::getenv("ML_VISIBLE_DEVICES");
     return v != nullptr && (*v == '\0' || std::strcmp(v, "cpu") == 0);

@@ -25,6 +25,12 @@ namespace srt {
 // path only (false where it does not apply). box = (xlo, xhi, ylo, yhi).
 bool HostScreenBox(const float c[9], int mode, float box[4]);
 
+// The closest hit at `count` image positions (fx, fy) of the scene's width x height frame, brute
+// force over every record with the canonical math (the host answer of a point query: render.h
+// LaunchQuery): ids[i] = the hit triangle or -1, t[i] = its t or +inf.
+void HostClosestHits(const Scene& scene, std::size_t width, std::size_t height, const float* positions,
+                     std::size_t count, int* ids, float* t);
+
 // Whether env ML_VISIBLE_DEVICES selects the CPU backend ("cpu", or set to the empty string).
 bool CpuBackendSelected();
 

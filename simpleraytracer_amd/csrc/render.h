@@ -336,6 +336,26 @@ hipError_t LaunchSharedCullFrames(const CullFrame* frames, std::size_t count, co
                                   const float background[3], hipStream_t stream, const StageEvents* events,
                                   const CullTable* table = nullptr);
 
+// Point queries (render.hip QueryKernel): the closest hit at `count` arbitrary image positions
+// (fx, fy) of the frame -- the quantity ray generation produces, nothing about pixels: ids[i] = the
+// hit record's id or -1, t[i] = its t = vol / det or +inf, the lexicographic (t, id) minimum, bit
+// for bit what the traces compute for a ray at that position. how[i] (null: not stored): 0 = answered
+// from the list of the tile whose analytic box contains the position plus the large list, 1 = every
+// record streamed (position outside [0, 1]^2 or NaN, overflowed list, unusable tile box, no setup).
+struct QueryArgs {
+    const float* positions;  // device, count x 2
+    std::size_t count;
+    int* ids;                // device, count
+    float* t;                // device, count
+    unsigned char* how;      // device, count, or null
+};
+// `setup`: the built shared setup of the width x height frame (read-only here), or null: none, every
+// query streams the records recomputed from d_svertices. d_edges: the scene's edge allocation
+// (kEdgeFloatsPerTriangle per padded record; not written). One launch; count == 0: none.
+hipError_t LaunchQuery(const CullSetup* setup, std::uint64_t n, const Frame& frame, std::size_t width,
+                       std::size_t height, const float* d_svertices, const float* d_edges, const QueryArgs& args,
+                       hipStream_t stream);
+
 // Deferred shading of a band from hit ids (band.ids) and sample offsets into band.rgba (normals
 // from the vertices, d_edges unused): bit-identical to the fused trace.
 // frames > 1 shades a batch whose ids are band-major, ids[band][frame][band_rows][width] (a

@@ -5,6 +5,7 @@
 // fmaf, so CPU (oracle/srt_oracle.c) and GPU evaluate bit-identical float expressions.
 #include "render.h"
 #include "screen_box.h"
+#include "tile_lookup.h"
 
 #include <hip/hip_ext.h>
 
@@ -3133,6 +3134,126 @@ __global__ __launch_bounds__(kCullThreads, SRT_TRACE_OCC) void TraceCullKernel(c
 }
 
 // ---------------------------------------------------------------------------------------
+// Point queries (render.h LaunchQuery; DESIGN.md section 5 "Point queries"): the closest hit at
+// arbitrary image positions of the prepared frame, answered from the shared setup's lists.
+// The lists were binned against the analytic tile boxes, and that binning is about boxes, not pixel
+// grids: BoxMayHit bounds the edge functions at every (fx, fy) of the box, and a record's screen box
+// contains every position with |fx|, |fy| <= kScreenBoxRange at which its float test can pass. So a
+// position inside a usable tile box passes the exact test of no record outside that tile's list and
+// the large list. A position outside [0, 1]^2 (NaN included), a tile whose list overflowed or whose
+// box is not ScreenBoxUsable, and a scene without a setup stream every record instead.
+// A group of kQueryLanes lanes per query: the lanes stride the candidates (a coalesced 4-B entry
+// load, then each lane gathers its record), run the trace kernels' exact test on them
+// (ExactTestAnyOrder, one ray) and the group reduces the (t, id) key with shuffles -- no LDS, no
+// atomics, no cross-block traffic. kQueryAhead candidates per lane and round, so a round has that
+// many dependent load pairs in flight; a lane past the end repeats the last candidate, which
+// changes no minimum (no divergent tail). The kernel is bound by the latency of its chain of
+// dependent loads (position -> tile counts -> list entries -> records), not by bandwidth or VALU, so
+// fewer, fuller waves win: 16 lanes x 2 candidates measured best of 64 / 32 / 16 / 8 lanes and
+// 1 / 2 / 4 candidates at C3 (profiles/query/). SRT_QUERY_LANES, SRT_QUERY_AHEAD:
+// measurement builds.
+// ---------------------------------------------------------------------------------------
+#ifndef SRT_QUERY_LANES
+#define SRT_QUERY_LANES 16
+#endif
+constexpr int kQueryLanes = SRT_QUERY_LANES;  // lanes per query (a divisor of the wave)
+#ifndef SRT_QUERY_AHEAD
+#define SRT_QUERY_AHEAD 2
+#endif
+constexpr int kQueryAhead = SRT_QUERY_AHEAD;  // candidates per lane and round
+constexpr int kQueryThreads = 256;
+constexpr int kQueryBlock = kQueryThreads / kQueryLanes;  // queries per block
+static_assert(kQueryLanes >= 2 && kWave % kQueryLanes == 0, "a query's lanes share a wave");
+struct QueryParams {
+    TraceParams rec;  // the records (TraceRecords), the frame vectors, the setup's tiles, lists and counts
+    const float2* __restrict__ positions;
+    int* __restrict__ ids;
+    float* __restrict__ t;
+    unsigned char* __restrict__ how;  // null: not stored
+    unsigned count;
+    unsigned stream_end;  // records of a streamed query: positions [0, stream_end)
+    int tiles_y;
+};
+
+template <bool RC>
+__global__ __launch_bounds__(kQueryThreads) void QueryKernel(const QueryParams q) {
+    const TraceParams& p = q.rec;
+    using Recs = TraceRecords<RC>;
+    const unsigned lane = threadIdx.x & (kQueryLanes - 1);
+    unsigned group = threadIdx.x / kQueryLanes;
+    if constexpr (kQueryLanes == kWave) {  // wave-uniform: the query's facts load through the scalar cache
+        group = static_cast<unsigned>(__builtin_amdgcn_readfirstlane(static_cast<int>(group)));
+    }
+    const unsigned query = blockIdx.x * kQueryBlock + group;
+    if (query >= q.count) {
+        return;
+    }
+    const float2 f = q.positions[query];
+    Rays<1> s;
+    s.fx[0] = f.x;
+    s.fy[0] = f.y;
+    s.bt[0] = __builtin_inff();
+    s.bi[0] = -1;
+    int col = 0, row = 0;
+    bool listed = p.tile_info != nullptr &&
+                  TileOfPosition(f.x, f.y, p.wf, p.hf, kCullTileCols, kTileRows, p.tiles_x, q.tiles_y, col, row);
+    unsigned cnt = 0u, large = 0u;
+    const unsigned* list = nullptr;
+    if (listed) {
+        const unsigned tile = static_cast<unsigned>(row) * static_cast<unsigned>(p.tiles_x) + static_cast<unsigned>(col);
+        cnt = p.bin_counts[tile];
+        large = p.bin_counts[p.tiles];
+        list = p.bin_lists + static_cast<size_t>(tile) * p.bin_capacity;
+        listed = cnt <= p.bin_capacity && p.tile_info[tile].usable != 0u;
+    }
+    const unsigned total = listed ? cnt + large : q.stream_end;
+    auto entry = [&](unsigned k) {
+        if (!listed) {
+            return k;
+        }
+        const unsigned* at = k < cnt ? list + k : p.large_list + (k - cnt);
+        return *at;
+    };
+    auto test = [&](const typename Recs::Raw& raw) {
+        const CullRecord r = Recs::Make(p, raw);
+        const Record rec{r.a.x, r.a.y, r.a.z, r.a.w, r.b.x, r.b.y, r.b.z, r.b.w, r.x.x};
+        ExactTestAnyOrder<1, false>(s, rec, r.x.y, static_cast<int>(__float_as_uint(r.x.z)));
+    };
+    for (unsigned base = 0u; base < total; base += kQueryAhead * kQueryLanes) {
+        unsigned pos[kQueryAhead];
+        typename Recs::Raw raw[kQueryAhead];
+#pragma unroll
+        for (int a = 0; a < kQueryAhead; ++a) {
+            pos[a] = entry(min(base + a * kQueryLanes + lane, total - 1u));
+        }
+#pragma unroll
+        for (int a = 0; a < kQueryAhead; ++a) {
+            raw[a] = Recs::Load(p, pos[a]);
+        }
+#pragma unroll
+        for (int a = 0; a < kQueryAhead; ++a) {
+            test(raw[a]);
+        }
+    }
+    // The lanes' (t, id) minimum; a miss is (+inf, -1), above every hit's key (a hit's t < +inf).
+    unsigned long long key = HitKey(s.bt[0], s.bi[0]);
+#pragma unroll
+    for (int o = 1; o < kQueryLanes; o <<= 1) {
+        const unsigned lo = static_cast<unsigned>(__shfl_xor(static_cast<int>(key), o));
+        const unsigned hi = static_cast<unsigned>(__shfl_xor(static_cast<int>(key >> 32), o));
+        const unsigned long long other = static_cast<unsigned long long>(hi) << 32 | lo;
+        key = other < key ? other : key;
+    }
+    if (lane == 0u) {
+        q.ids[query] = static_cast<int>(static_cast<unsigned>(key));
+        q.t[query] = __uint_as_float(static_cast<unsigned>(key >> 32));
+        if (q.how != nullptr) {
+            q.how[query] = listed ? 0 : 1;
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------------------
 // BVH variant: primary rays share the eye, so the closest-hit search
 // is a 2-D query over the records' screen boxes. The tree is implicit and 8 wide over the
 // cull records in the scene's spatial (Morton) order -- no sort, no topology arrays; only the
@@ -4174,6 +4295,64 @@ hipError_t LaunchSharedCullFrames(const CullFrame* frames, std::size_t count, co
     const BinTable bt{(ConstantPtr<BinParams>)(dev + lay.bin)};
     const TraceTable tt{(ConstantPtr<TraceParams>)(dev + lay.trace)};
     LaunchSharedStages(tt, bt, z, gx, gy, setup.recompute, setup.descs, stream, ev);
+    return hipGetLastError();
+}
+
+hipError_t LaunchQuery(const CullSetup* setup, std::uint64_t n, const Frame& frame, std::size_t width,
+                       std::size_t height, const float* d_svertices, const float* d_edges, const QueryArgs& args,
+                       hipStream_t stream) {
+    if (args.count == 0) {
+        return hipSuccess;
+    }
+    if (args.positions == nullptr || args.ids == nullptr || args.t == nullptr || d_svertices == nullptr ||
+        d_edges == nullptr || args.count > 0xFFFFFFFFull - kQueryBlock ||
+        (setup != nullptr && (width == 0 || height == 0 || !CullBinnable(width, height) ||
+                              setup->tiles != CullTiles(width, height)))) {
+        return hipErrorInvalidValue;
+    }
+    QueryParams q{};
+    TraceParams& p = q.rec;
+    // Without a setup the records are recomputed from the scene's spatial inputs; TraceRecords<true>
+    // also loads the position's screen box, which the exact test does not use: the scene's edge
+    // allocation has room for one per padded record, so the address is valid whatever it holds.
+    const EdgeLayout e = setup != nullptr ? SetupRecords(*setup) : EdgeBuffers(d_edges, n);
+    p.screen_boxes = e.screen_boxes;
+    p.cull = e.cull;
+    p.svertices = d_svertices;
+    p.n = static_cast<unsigned>(n);
+    p.n_pad = static_cast<unsigned>(PaddedTriangleCount(n));
+    for (int k = 0; k < 3; ++k) {
+        p.base[k] = frame.base[k];
+        p.du[k] = frame.du[k];
+        p.dv[k] = frame.dv[k];
+        p.eye[k] = frame.origin[k];
+    }
+    bool recompute = true;
+    if (setup != nullptr) {
+        recompute = setup->recompute;
+        p.tile_info = static_cast<const TileInfo*>(setup->tile_info);
+        p.bin_lists = setup->lists;
+        p.bin_counts = setup->counts;
+        p.large_list = setup->large_list;
+        p.bin_capacity = setup->capacity;
+        p.tiles_x = static_cast<int>((width + kWave - 1) / kWave);
+        q.tiles_y = static_cast<int>((height + kTileRows - 1) / kTileRows);
+        p.tiles = static_cast<unsigned>(setup->tiles);
+        p.wf = static_cast<float>(width);
+        p.hf = static_cast<float>(height);
+    }
+    q.positions = reinterpret_cast<const float2*>(args.positions);
+    q.ids = args.ids;
+    q.t = args.t;
+    q.how = args.how;
+    q.count = static_cast<unsigned>(args.count);
+    q.stream_end = n == 0 ? 0u : p.n_pad;  // (an empty scene: every query misses)
+    const dim3 grid(static_cast<unsigned>((args.count + kQueryBlock - 1) / kQueryBlock));
+    if (recompute) {
+        hipLaunchKernelGGL(QueryKernel<true>, grid, dim3(kQueryThreads), 0, stream, q);
+    } else {
+        hipLaunchKernelGGL(QueryKernel<false>, grid, dim3(kQueryThreads), 0, stream, q);
+    }
     return hipGetLastError();
 }
 

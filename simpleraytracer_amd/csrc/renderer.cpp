@@ -711,10 +711,30 @@ void DeviceScene::TraceShared(const float* const* d_offsets, float* const* d_rgb
         cf[f].band = BandArgs{d_offsets[f], d_rgba != nullptr ? d_rgba[f] : nullptr, m_width, m_height, 0, m_height,
                               d_ids != nullptr ? d_ids[f] : nullptr, 1, id_planes, rgba_frame_rows};
     }
+    const CullSetup setup = EnsureSetup(bins[0].descs, stream);
+    const StageEvents ev = BindStageEvents(false, true);
+    ParamTable* table = frames > static_cast<std::size_t>(kMaxBatch) ? &AcquireTable(frames, stream) : nullptr;
+    const CullTable ct{table != nullptr ? table->device : nullptr, table != nullptr ? table->host : nullptr,
+                       table != nullptr ? table->frames : 0, table != nullptr ? table->host_device : nullptr,
+                       table != nullptr ? table->uploaded : nullptr};
+    HipCheck(LaunchSharedCullFrames(cf.data(), frames, setup, m_n, m_vertices, m_shade, m_frame, m_background, stream,
+                                    m_timing ? &ev : nullptr, table != nullptr ? &ct : nullptr),
+             "shared-setup trace launch");
+    if (table != nullptr) {
+        table->pending = true;  // (LaunchSharedCullFrames recorded `uploaded` after the upload)
+    }
+    m_setup_stats.shared_frames += frames;
+    LogSetupStats();
+    RecordOrder(stream);
+}
+
+// The shared setup of the prepared frame for a trace grid of `descs` descriptors: (re)allocated,
+// keyed and (re)built on `stream` if need be (after OrderAfterPrevious(stream)), counted in
+// SetupStats::builds. What TraceShared and Query have in common.
+CullSetup DeviceScene::EnsureSetup(unsigned descs, hipStream_t stream) const {
     // Stored records unless the env asks for recomputed ones: the engine's one-queue hint
     // (SetRecordMode) shortened a bin launch that this path does not run.
     const bool recompute = RecordModeFromEnv() == static_cast<int>(kRecordsRecompute);
-    const unsigned descs = bins[0].descs;
     const std::size_t bytes = CullSetupBytes(m_n, m_width, m_height, descs);
     if (bytes > m_setup_bytes) {
         // (earlier readers of the old copy ran before this stream's end: OrderAfterPrevious)
@@ -738,19 +758,32 @@ void DeviceScene::TraceShared(const float* const* d_offsets, float* const* d_rgb
         m_setup_pending = false;
         ++m_setup_stats.builds;
     }
-    const StageEvents ev = BindStageEvents(false, true);
-    ParamTable* table = frames > static_cast<std::size_t>(kMaxBatch) ? &AcquireTable(frames, stream) : nullptr;
-    const CullTable ct{table != nullptr ? table->device : nullptr, table != nullptr ? table->host : nullptr,
-                       table != nullptr ? table->frames : 0, table != nullptr ? table->host_device : nullptr,
-                       table != nullptr ? table->uploaded : nullptr};
-    HipCheck(LaunchSharedCullFrames(cf.data(), frames, setup, m_n, m_vertices, m_shade, m_frame, m_background, stream,
-                                    m_timing ? &ev : nullptr, table != nullptr ? &ct : nullptr),
-             "shared-setup trace launch");
-    if (table != nullptr) {
-        table->pending = true;  // (LaunchSharedCullFrames recorded `uploaded` after the upload)
+    return setup;
+}
+
+// Point queries on the prepared frame (render.h LaunchQuery). The setup is built for the one-frame
+// trace grid, so a one-frame whole-frame trace before or after shares the build. No usable setup
+// (SRT_SETUP=frame, SRT_CULL_BIN=0, a shape that cannot be binned): every query streams.
+void DeviceScene::Query(const float* d_positions, std::size_t count, int* d_ids, float* d_t, unsigned char* d_how,
+                        hipStream_t stream) const {
+    if (m_width == 0) {
+        throw std::runtime_error("Query: Prepare() has not been called");
     }
-    m_setup_stats.shared_frames += frames;
-    LogSetupStats();
+    if (count == 0) {
+        return;
+    }
+    OrderAfterPrevious(stream);
+    const bool shared = OnSharedSetup(0, m_height, 1) && CullBinningEnabled() && CullBinnable(m_width, m_height);
+    CullSetup setup{};
+    if (shared) {
+        // (a query reads no plan: a setup standing for another grid, a batch's, serves as it is)
+        const bool standing = !m_setup_pending && m_setup_key.width == m_width && m_setup_key.height == m_height;
+        setup = EnsureSetup(standing ? m_setup_key.descs : CullDescriptors(CullTiles(m_width, m_height), 1), stream);
+        LogSetupStats();
+    }
+    const QueryArgs args{d_positions, count, d_ids, d_t, d_how};
+    HipCheck(LaunchQuery(shared ? &setup : nullptr, m_n, m_frame, m_width, m_height, m_svertices, m_edges, args, stream),
+             "query launch");
     RecordOrder(stream);
 }
 

@@ -18,6 +18,7 @@
 namespace srt {
 
 struct CullBins;     // render.h
+struct CullSetup;    // render.h
 struct StageEvents;  // render.h
 
 // Throws std::runtime_error("HIP error: <what>: <reason>") on failure.
@@ -103,6 +104,13 @@ public:
     // row_begins: frame f's band starts at row_begins[f] instead -- one row count and pattern, so one
     // band shape, for every frame; cull variant, bands short of the whole frame.)
 
+    // Point queries: the closest hit at `count` image positions (fx, fy) of the prepared frame
+    // (d_positions: count x 2) into d_ids (-1 = miss), d_t (+inf = miss) and, non-null, d_how
+    // (render.h QueryArgs), answered from the shared setup's lists (built here if the prepared
+    // frame has none yet, for the one-frame trace grid).
+    void Query(const float* d_positions, std::size_t count, int* d_ids, float* d_t, unsigned char* d_how,
+               hipStream_t stream) const;
+
     std::size_t width() const { return m_width; }
     // The spatial order (device, triangles entries) and the time its build took at load (ms).
     const unsigned* order() const { return m_order; }
@@ -176,6 +184,8 @@ private:
     // Whole frames on the shared setup: the setup (re)built if need be, then tile facts + trace.
     void TraceShared(const float* const* d_offsets, float* const* d_rgba, int* const* d_ids, std::size_t frames,
                      hipStream_t stream, int id_planes, bool rgba_frame_rows) const;
+    // The setup for a trace grid of `descs` descriptors, (re)built on `stream` if need be.
+    CullSetup EnsureSetup(unsigned descs, hipStream_t stream) const;
     Frame m_frame{};
     std::size_t m_width = 0;
     std::size_t m_height = 0;

@@ -12,7 +12,9 @@
 #include "render.h"
 #include "renderer.h"
 #include "scene.h"
+#include "srt_query.h"
 #include "srt_render.h"
+#include "tile_lookup.h"
 
 namespace {
 
@@ -729,6 +731,57 @@ ML_API_ENTRY int srtScreenBoxHost(const float* c, int mode, float* box) {
         }
         if (!srt::HostScreenBox(c, mode, box)) {
             throw std::runtime_error("screen box: the float fast path does not apply");
+        }
+    });
+}
+
+// Point queries (include/srt_query.h): the rtq family.
+RTQ_API int rtqQueryAsync(srt_device_scene scene, const float* d_positions, size_t count, int* d_ids, float* d_t,
+                          unsigned char* d_how, void* stream) {
+    return Guarded([&] {
+        if (scene == nullptr) {
+            throw std::runtime_error("Bad scene handle");
+        }
+        if (count != 0) {
+            if (d_positions == nullptr) {
+                throw std::runtime_error("Bad buffer argument: d_positions is NULL");
+            }
+            if (d_ids == nullptr) {
+                throw std::runtime_error("Bad buffer argument: d_ids is NULL");
+            }
+            if (d_t == nullptr) {
+                throw std::runtime_error("Bad buffer argument: d_t is NULL");
+            }
+        }
+        srt::DeviceScene* s = FromHandle(scene);
+        Bind bind(s->device());
+        s->Query(d_positions, count, d_ids, d_t, d_how, static_cast<hipStream_t>(stream));
+    });
+}
+
+RTQ_API int rtqQueryHost(const char* scene_path, size_t width, size_t height, const float* positions, size_t count,
+                         int* ids, float* t) {
+    return Guarded([&] {
+        if (scene_path == nullptr || width == 0 || height == 0 ||
+            (count != 0 && (positions == nullptr || ids == nullptr || t == nullptr))) {
+            throw std::runtime_error("Bad argument");
+        }
+        const srt::Scene scene = srt::LoadScene(scene_path);
+        srt::HostClosestHits(scene, width, height, positions, count, ids, t);
+    });
+}
+
+RTQ_API int rtqTileHost(size_t width, size_t height, float fx, float fy, int* tile_col, int* tile_row) {
+    return Guarded([&] {
+        if (tile_col == nullptr || tile_row == nullptr || width == 0 || height == 0 ||
+            !srt::CullBinnable(width, height)) {
+            throw std::runtime_error("Bad argument");
+        }
+        const int nx = static_cast<int>((width + srt::kCullTileCols - 1) / srt::kCullTileCols);
+        const int ny = static_cast<int>((height + srt::kCullTileRows - 1) / srt::kCullTileRows);
+        if (!srt::TileOfPosition(fx, fy, static_cast<float>(width), static_cast<float>(height), srt::kCullTileCols,
+                                 srt::kCullTileRows, nx, ny, *tile_col, *tile_row)) {
+            throw std::runtime_error("Position outside [0, 1]^2: no tile");
         }
     });
 }

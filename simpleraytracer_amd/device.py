@@ -1,4 +1,5 @@
-"""Scene files and the device-level render stages (include/srt_render.h).
+"""Scene files, the device-level render stages (include/srt_render.h) and point queries
+(include/srt_query.h).
 
 ``DeviceScene`` keeps a scene resident on one GPU and launches the two stages on a caller's
 HIP stream with caller-owned device buffers (torch tensors or raw pointers):
@@ -6,6 +7,7 @@ HIP stream with caller-owned device buffers (torch tensors or raw pointers):
     scene = DeviceScene(path, device=0)
     scene.prepare(W, H, stream)                                  # edge records
     scene.trace(offsets, rgba, row_begin, row_count, stream=s)   # closest hit + shade
+    scene.query(positions, ids, t, stream=s)                     # closest hit at arbitrary image positions
 
 This is the path bench.py times (inputs resident in HBM) and the one-process-per-GPU
 band renderer uses; ``runner.render`` is the host-image ml* path.
@@ -79,6 +81,47 @@ def scene_frame(path: str, width: int, height: int):
     return tuple(tuple(vals[3 * k:3 * k + 3]) for k in range(4))
 
 
+def pixel_positions(width: int, height: int, offsets):
+    """The image positions ray generation produces for a frame's pixels: offsets (H, W, 2) (or a
+    scalar / anything broadcastable to it) -> (H * W, 2) float32, row-major, by the canonical
+    float32 expression fx = (float(x) + sx) / float(W), fy = (float(y) + sy) / float(H)."""
+    import numpy as np
+
+    off = np.broadcast_to(np.asarray(offsets, np.float32), (height, width, 2))
+    x = np.arange(width, dtype=np.float32)[None, :]
+    y = np.arange(height, dtype=np.float32)[:, None]
+    out = np.empty((height, width, 2), np.float32)
+    out[..., 0] = (x + off[..., 0]) / np.float32(width)
+    out[..., 1] = (y + off[..., 1]) / np.float32(height)
+    return out.reshape(height * width, 2)
+
+
+def query_host(path: str, width: int, height: int, positions):
+    """Point queries on the host (rtqQueryHost: brute force, the library's canonical math, no
+    device): positions (count, 2) float32 -> (ids int32, t float32), a miss as (-1, +inf)."""
+    import numpy as np
+
+    pos = np.ascontiguousarray(positions, np.float32)
+    if pos.ndim != 2 or pos.shape[1] != 2:
+        raise ValueError(f"positions must be (count, 2), got {pos.shape}")
+    ids = np.empty(pos.shape[0], np.int32)
+    t = np.empty(pos.shape[0], np.float32)
+    _check(_native.lib().rtqQueryHost(os.fsencode(path), width, height, pos.ctypes.data, pos.shape[0],
+                                      ids.ctypes.data, t.ctypes.data))
+    return ids, t
+
+
+def tile_of(width: int, height: int, fx: float, fy: float):
+    """The cull tile (col, row) the query kernel looks a position up in (rtqTileHost), or None
+    when the position is not in [0, 1]^2."""
+    c, r = ctypes.c_int(), ctypes.c_int()
+    if _native.lib().rtqTileHost(width, height, fx, fy, ctypes.byref(c), ctypes.byref(r)) != 0:
+        if _native.last_error().startswith("Position outside"):
+            return None
+        raise SrtError(_native.last_error())
+    return c.value, r.value
+
+
 def _ptr(x) -> int:
     if x is None:
         return 0
@@ -127,7 +170,7 @@ class DeviceScene:
         if hasattr(buf, "is_cuda"):
             import torch
 
-            want_dtype = {"f32": torch.float32, "i32": torch.int32}[dtype]
+            want_dtype = {"f32": torch.float32, "i32": torch.int32, "u8": torch.uint8}[dtype]
             if buf.dtype != want_dtype:
                 raise ValueError(f"{name} must be {want_dtype}, got {buf.dtype}")
             if not buf.is_cuda or buf.device.index != self.device:
@@ -238,6 +281,28 @@ class DeviceScene:
             self._check_tensor(name, buf, dtype)
         _check(self._lib.srtShadeBandsAsync(self.handle, _ptr(offsets), _ptr(ids), _ptr(rgba), frames, band_rows,
                                             interleaved, _stream(stream)))
+
+    def query(self, positions, ids, t, how=None, stream=None):
+        """Point queries (include/srt_query.h): the closest hit at arbitrary image positions of the
+        prepared frame. positions (count, 2) float32 -> ids (count,) int32 (-1 = miss), t (count,)
+        float32 (+inf = miss) and, optionally, how (count,) uint8: 0 = answered from the tile's
+        list, 1 = every record streamed. Device buffers, checked like trace()'s."""
+        count = None
+        for name, buf, tail, dtype in (("positions", positions, (2,), "f32"), ("ids", ids, (), "i32"),
+                                       ("t", t, (), "f32"), ("how", how, (), "u8")):
+            if buf is None and name == "how":
+                continue
+            if hasattr(buf, "shape"):
+                shape = tuple(buf.shape)
+                if len(shape) != 1 + len(tail) or shape[1:] != tail or (count is not None and shape[0] != count):
+                    want = ("count" if count is None else count,) + tail
+                    raise ValueError(f"{name} must be {want}, got {shape}")
+                count = shape[0]
+            self._check_tensor(name, buf, dtype)
+        if count is None:
+            raise ValueError("positions must have a shape (count, 2): raw pointers carry no count")
+        _check(self._lib.rtqQueryAsync(self.handle, _ptr(positions), count, _ptr(ids), _ptr(t), _ptr(how),
+                                       _stream(stream)))
 
     def spatial_order(self):
         """(order, build_ms): the record ids in spatial order (numpy uint32), built on the device
