@@ -1,4 +1,5 @@
-"""ctypes binding of libModelRunner.so (include/model_runner.h + include/srt_render.h + include/srt_query.h).
+"""ctypes binding of libModelRunner.so (include/model_runner.h + include/srt_render.h + include/srt_query.h +
+include/srt_gbuffer.h).
 
 The shared library is built in-tree by ``make`` (or ``__graft_entry__.build()``) into
 ``simpleraytracer_amd/lib/libModelRunner.so``. There is no fallback: importing the renderer
@@ -85,6 +86,18 @@ class EngineOptions(ctypes.Structure):
     ]
 
 
+class RtgOutputs(ctypes.Structure):
+    """``rtg_outputs`` (include/srt_gbuffer.h): the planes as raw addresses, 0 = not written."""
+
+    _fields_ = [
+        ("struct_size", ctypes.c_size_t),
+        ("depth", ctypes.c_void_p),
+        ("bary", ctypes.c_void_p),
+        ("normal", ctypes.c_void_p),
+        ("albedo", ctypes.c_void_p),
+    ]
+
+
 _SZ = ctypes.c_size_t
 _PSZ = ctypes.POINTER(ctypes.c_size_t)
 _PD = ctypes.POINTER(ctypes.c_double)
@@ -167,6 +180,13 @@ _SIGNATURES = {
     "rtqQueryHost": (ctypes.c_int, [ctypes.c_char_p, _SZ, _SZ, ctypes.c_void_p, _SZ, ctypes.c_void_p, ctypes.c_void_p]),
     "rtqTileHost": (ctypes.c_int, [_SZ, _SZ, ctypes.c_float, ctypes.c_float, ctypes.POINTER(ctypes.c_int),
                                    ctypes.POINTER(ctypes.c_int)]),
+    # include/srt_gbuffer.h: G-buffer outputs
+    "rtgFrameAsync": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, _SZ, _SZ,
+                                     ctypes.POINTER(RtgOutputs), ctypes.c_void_p]),
+    "rtgPointsAsync": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, _SZ,
+                                      ctypes.POINTER(RtgOutputs), ctypes.c_void_p]),
+    "rtgPointsHost": (ctypes.c_int, [ctypes.c_char_p, _SZ, _SZ, ctypes.c_void_p, ctypes.c_void_p, _SZ,
+                                     ctypes.POINTER(RtgOutputs)]),
 }
 
 _lib = None

@@ -1,5 +1,6 @@
 #include "cpu_render.h"
 
+#include "gbuffer_math.h"
 #include "screen_box.h"
 
 #include <algorithm>
@@ -220,6 +221,43 @@ void HostClosestHits(const Scene& scene, std::size_t width, std::size_t height, 
         }
         ids[q] = id;
         t[q] = best;
+    });
+}
+
+void HostGBuffer(const Scene& scene, std::size_t width, std::size_t height, const float* positions, const int* ids,
+                 std::size_t count, float* depth, float* bary, float* normal, float* albedo) {
+    if (width == 0 || height == 0) {
+        throw std::runtime_error("Host G-buffer: frame dimensions must be non-zero");
+    }
+    if (depth == nullptr && bary == nullptr && normal == nullptr && albedo == nullptr) {
+        return;  // (no plane: nothing is read either)
+    }
+    const Frame f = MakeFrame(scene.camera, width, height);
+    const std::size_t n = scene.triangle_count();
+    ParallelFor(count, 256, [&](std::size_t q) {
+        const int id = ids[q];
+        GBufferTexel o = GBufferMiss(scene.background);
+        if (id >= 0 && static_cast<std::size_t>(id) < n) {
+            const Rec r = MakeRecord(scene.vertices.data() + 9 * static_cast<std::size_t>(id), f);
+            const float* a = scene.albedo.data() + 3 * static_cast<std::size_t>(id);
+            o = GBufferHit(r.c, r.vol, f.base, f.du, f.dv, positions[2 * q], positions[2 * q + 1], id, r.n[0], r.n[1],
+                           r.n[2], r.n[3], a[0], a[1], a[2]);
+        }
+        if (depth != nullptr) {
+            depth[q] = o.depth;
+        }
+        if (bary != nullptr) {
+            bary[2 * q] = o.w1;
+            bary[2 * q + 1] = o.w2;
+        }
+        if (normal != nullptr) {
+            const float v[4] = {o.nx, o.ny, o.nz, o.cosv};
+            std::copy(v, v + 4, normal + 4 * q);
+        }
+        if (albedo != nullptr) {
+            const float v[4] = {o.r, o.g, o.b, o.a};
+            std::copy(v, v + 4, albedo + 4 * q);
+        }
     });
 }
 

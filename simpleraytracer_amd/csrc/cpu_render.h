@@ -31,6 +31,13 @@ bool HostScreenBox(const float c[9], int mode, float box[4]);
 void HostClosestHits(const Scene& scene, std::size_t width, std::size_t height, const float* positions,
                      std::size_t count, int* ids, float* t);
 
+// The surface attributes (gbuffer_math.h) of `count` (position, triangle id) pairs of the scene's
+// width x height frame (the host answer of the G-buffer: render.h LaunchGBuffer), into the planes
+// that are non-null: depth[count], bary[count][2], normal[count][4], albedo[count][4]. An id outside
+// the scene gives the miss values.
+void HostGBuffer(const Scene& scene, std::size_t width, std::size_t height, const float* positions, const int* ids,
+                 std::size_t count, float* depth, float* bary, float* normal, float* albedo);
+
 // Whether env ML_VISIBLE_DEVICES selects the CPU backend ("cpu", or set to the empty string).
 bool CpuBackendSelected();
 

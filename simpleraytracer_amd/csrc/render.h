@@ -356,6 +356,34 @@ hipError_t LaunchQuery(const CullSetup* setup, std::uint64_t n, const Frame& fra
                        std::size_t height, const float* d_svertices, const float* d_edges, const QueryArgs& args,
                        hipStream_t stream);
 
+// G-buffer (render.hip GBufferKernel): the surface attributes of (image position, triangle id)
+// pairs of the frame -- depth, barycentrics, normal + shading cosine, albedo + id (gbuffer_math.h;
+// DESIGN.md section 2 "Surface attributes") -- from hit ids, a deferred pass like LaunchShade with
+// more outputs. The record of an id is recomputed from the scene's vertices (ComputeEdges under
+// `frame`, the traces' bits): no edge buffer, no cull setup is read. An id outside [0, n) gives the
+// miss values and reads nothing through it.
+struct GBufferArgs {
+    // points: `where` = count x 2 positions (fx, fy), ids = count ids (count = width; height,
+    // row_begin unused, row_count 1). Else `where` = the band's sample offsets, row_count x width x 2,
+    // ids = row_count x width (band-local, as LaunchShade's): pixel (x, row_begin + y) of the
+    // width x height frame, its position ray generation's expression.
+    bool points;
+    const float* where;  // device
+    const int* ids;      // device
+    std::size_t width;
+    std::size_t height;
+    std::size_t row_begin;
+    std::size_t row_count;
+    // The planes (device; null: not written), each row_count x width elements, count-major.
+    float* depth;   // [1]
+    float* bary;    // [2]: (w1, w2)
+    float* normal;  // [4]: (unit normal towards the eye, cos)
+    float* albedo;  // [4]: (r, g, b, float(id))
+};
+// One launch; no elements or no plane: none.
+hipError_t LaunchGBuffer(const float* d_vertices, const float* d_shade, std::uint64_t n, const Frame& frame,
+                         const float background[3], const GBufferArgs& args, hipStream_t stream);
+
 // Deferred shading of a band from hit ids (band.ids) and sample offsets into band.rgba (normals
 // from the vertices, d_edges unused): bit-identical to the fused trace.
 // frames > 1 shades a batch whose ids are band-major, ids[band][frame][band_rows][width] (a

@@ -4,6 +4,7 @@
 // DESIGN.md. Built with -ffp-contract=off: every fused multiply-add below is an explicit
 // fmaf, so CPU (oracle/srt_oracle.c) and GPU evaluate bit-identical float expressions.
 #include "render.h"
+#include "gbuffer_math.h"
 #include "screen_box.h"
 #include "tile_lookup.h"
 
@@ -853,6 +854,136 @@ __global__ __launch_bounds__(kShadeThreads) void ShadeIdsKernel(TraceParams p, c
             const float4 v = ShadeRecord(p, fx, fy, hit[r], nr[r], al[r]);
             StoreNontemporal(reinterpret_cast<F4*>(p.out + g * pixels + static_cast<size_t>(y) * p.width + x),
                              F4{v.x, v.y, v.z, v.w});
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------------------
+// G-buffer (render.h LaunchGBuffer; DESIGN.md section 5 "G-buffer"): the surface attributes of
+// (position, hit id) pairs -- ShadeIdsKernel's deferred pass with more outputs. POINTS: element k's
+// position is read from `where`; else element (x, y) is pixel (x, row_begin + y) of the frame and its
+// position is ray generation's expression of its sample offset (as ShadeIdsKernel). The elements
+// form rows of `width` (points: one row of count); a block takes kGBufferThreads * PPT consecutive
+// elements of one row, a thread PPT of them kGBufferThreads apart, so every wave instruction loads
+// and stores consecutive elements. Three phases with no control flow that depends on loaded data
+// between the loads: (1) every element's id and position, (2) every element's gather -- the
+// triangle's 9 vertex floats (skipped when neither depth nor bary is asked for) and its shading
+// table row (skipped without normal and albedo), an id outside the scene gathers triangle 0's,
+// unused --, (3) the arithmetic (ComputeEdges + gbuffer_math.h) and the nontemporal stores of the
+// planes asked for (uniform branches). No LDS, no atomics, no scratch.
+// Elements per thread, measured at C3 (1 / 2 / 4 / 8: DESIGN.md; profiles/gbuffer/): a launch that
+// needs one of the two gathers is fastest with 4 (depth only 23.1 / 18.9 / 15.4 / 17.7 us), one that
+// needs both with 8 (all planes 35.8 / 35.0 / 33.3 / 28.8 us: 184 VGPRs, two waves per SIMD, and
+// twice the loads in flight per wave). SRT_GBUFFER_PIXELS, SRT_GBUFFER_PIXELS_BOTH: measurement builds.
+// ---------------------------------------------------------------------------------------
+#ifndef SRT_GBUFFER_PIXELS
+#define SRT_GBUFFER_PIXELS 4
+#endif
+#ifndef SRT_GBUFFER_PIXELS_BOTH
+#define SRT_GBUFFER_PIXELS_BOTH 8
+#endif
+constexpr int kGBufferPixels = SRT_GBUFFER_PIXELS;           // elements per thread, one gather
+constexpr int kGBufferPixelsBoth = SRT_GBUFFER_PIXELS_BOTH;  // ... both gathers
+constexpr int kGBufferThreads = 256;
+typedef float F2 __attribute__((ext_vector_type(2)));
+struct GBufferParams {
+    const float* __restrict__ vertices;
+    const float4* __restrict__ shade;
+    const float2* __restrict__ where;  // positions (POINTS) or sample offsets
+    const int* __restrict__ ids;
+    float* __restrict__ depth;
+    F2* __restrict__ bary;
+    F4* __restrict__ normal;
+    F4* __restrict__ albedo;
+    unsigned n;
+    unsigned width;   // elements per row
+    unsigned chunks;  // blocks per row
+    unsigned row_begin;
+    float wf, hf;
+    float eye[3], base[3], du[3], dv[3], bg[3];
+};
+
+template <bool POINTS, int PPT>
+__global__ __launch_bounds__(kGBufferThreads) void GBufferKernel(const GBufferParams q) {
+    const unsigned row = POINTS ? 0u : blockIdx.x / q.chunks;  // (uniform: scalar)
+    const unsigned chunk = blockIdx.x - row * q.chunks;
+    const unsigned x0 = chunk * (kGBufferThreads * PPT) + threadIdx.x;
+    const size_t row_at = static_cast<size_t>(row) * q.width;
+    const bool edges = q.depth != nullptr || q.bary != nullptr;
+    const bool table = q.normal != nullptr || q.albedo != nullptr;
+    // (1) An element past the row loads the row's last one and is not stored.
+    int code[PPT];
+    float2 w[PPT];
+#pragma unroll
+    for (int k = 0; k < PPT; ++k) {
+        const unsigned x = min(x0 + k * kGBufferThreads, q.width - 1u);
+        code[k] = __builtin_nontemporal_load(q.ids + row_at + x);
+        w[k] = q.where[row_at + x];
+    }
+    // (2)
+    int hit[PPT];
+    float v[PPT][9];
+    float4 nr[PPT], al[PPT];
+#pragma unroll
+    for (int k = 0; k < PPT; ++k) {
+        hit[k] = static_cast<unsigned>(code[k]) < q.n ? code[k] : -1;
+#pragma unroll
+        for (int j = 0; j < 9; ++j) {
+            v[k][j] = 0.f;
+        }
+        nr[k] = al[k] = float4{};
+    }
+    if (q.n != 0u) {  // (an empty scene has no triangle 0)
+        if (edges) {
+#pragma unroll
+            for (int k = 0; k < PPT; ++k) {
+                const float* at = q.vertices + 9ull * static_cast<unsigned>(max(hit[k], 0));
+#pragma unroll
+                for (int j = 0; j < 9; ++j) {
+                    v[k][j] = at[j];
+                }
+            }
+        }
+        if (table) {
+#pragma unroll
+            for (int k = 0; k < PPT; ++k) {
+                const float4* sr = q.shade + 2ull * static_cast<unsigned>(max(hit[k], 0));
+                nr[k] = sr[0];
+                al[k] = sr[1];
+            }
+        }
+    }
+    // (3)
+#pragma unroll
+    for (int k = 0; k < PPT; ++k) {
+        const unsigned x = x0 + k * kGBufferThreads;
+        if (x >= q.width) {
+            continue;
+        }
+        float fx = w[k].x, fy = w[k].y;
+        if constexpr (!POINTS) {
+            fx = (static_cast<float>(x) + w[k].x) / q.wf;
+            fy = (static_cast<float>(q.row_begin + row) + w[k].y) / q.hf;
+        }
+        GBufferTexel o = GBufferMiss(q.bg);
+        if (hit[k] >= 0) {
+            float c[9], vol;
+            ComputeEdges(q.eye, q.base, q.du, q.dv, v[k], true, c, vol);
+            o = GBufferHit(c, vol, q.base, q.du, q.dv, fx, fy, hit[k], nr[k].x, nr[k].y, nr[k].z, nr[k].w, al[k].x,
+                           al[k].y, al[k].z);
+        }
+        const size_t at = row_at + x;
+        if (q.depth != nullptr) {
+            __builtin_nontemporal_store(o.depth, q.depth + at);
+        }
+        if (q.bary != nullptr) {
+            __builtin_nontemporal_store(F2{o.w1, o.w2}, q.bary + at);
+        }
+        if (q.normal != nullptr) {
+            StoreNontemporal(q.normal + at, F4{o.nx, o.ny, o.nz, o.cosv});
+        }
+        if (q.albedo != nullptr) {
+            StoreNontemporal(q.albedo + at, F4{o.r, o.g, o.b, o.a});
         }
     }
 }
@@ -4352,6 +4483,54 @@ hipError_t LaunchQuery(const CullSetup* setup, std::uint64_t n, const Frame& fra
         hipLaunchKernelGGL(QueryKernel<true>, grid, dim3(kQueryThreads), 0, stream, q);
     } else {
         hipLaunchKernelGGL(QueryKernel<false>, grid, dim3(kQueryThreads), 0, stream, q);
+    }
+    return hipGetLastError();
+}
+
+hipError_t LaunchGBuffer(const float* d_vertices, const float* d_shade, std::uint64_t n, const Frame& frame,
+                         const float background[3], const GBufferArgs& args, hipStream_t stream) {
+    const bool planes = args.depth != nullptr || args.bary != nullptr || args.normal != nullptr || args.albedo != nullptr;
+    if (args.width == 0 || args.row_count == 0 || !planes) {
+        return hipSuccess;
+    }
+    // Both gathers (the vertices for depth / bary, the shading table row for normal / albedo)?
+    const bool both = (args.depth != nullptr || args.bary != nullptr) && (args.normal != nullptr || args.albedo != nullptr);
+    const std::size_t block = static_cast<std::size_t>(kGBufferThreads) * (both ? kGBufferPixelsBoth : kGBufferPixels);
+    const std::size_t chunks = (args.width + block - 1) / block;
+    if (args.where == nullptr || args.ids == nullptr || d_shade == nullptr || (n != 0 && d_vertices == nullptr) ||
+        n > 0xFFFFFFFFull || args.width > 0xFFFFFFFFull - block || (args.points && args.row_count != 1) ||
+        (!args.points && (args.height == 0 || args.row_begin + args.row_count > args.height)) ||
+        args.row_count > 0x7FFFFFFFull / chunks) {
+        return hipErrorInvalidValue;
+    }
+    GBufferParams q{};
+    q.vertices = d_vertices;
+    q.shade = reinterpret_cast<const float4*>(d_shade);
+    q.where = reinterpret_cast<const float2*>(args.where);
+    q.ids = args.ids;
+    q.depth = args.depth;
+    q.bary = reinterpret_cast<F2*>(args.bary);
+    q.normal = reinterpret_cast<F4*>(args.normal);
+    q.albedo = reinterpret_cast<F4*>(args.albedo);
+    q.n = static_cast<unsigned>(n);
+    q.width = static_cast<unsigned>(args.width);
+    q.chunks = static_cast<unsigned>(chunks);
+    q.row_begin = static_cast<unsigned>(args.row_begin);
+    q.wf = static_cast<float>(args.width);
+    q.hf = static_cast<float>(args.height);
+    for (int k = 0; k < 3; ++k) {
+        q.eye[k] = frame.origin[k];
+        q.base[k] = frame.base[k];
+        q.du[k] = frame.du[k];
+        q.dv[k] = frame.dv[k];
+        q.bg[k] = background[k];
+    }
+    const dim3 grid(static_cast<unsigned>(chunks * args.row_count));
+    const auto launch = [&](auto kernel) { hipLaunchKernelGGL(kernel, grid, dim3(kGBufferThreads), 0, stream, q); };
+    if (args.points) {
+        both ? launch(GBufferKernel<true, kGBufferPixelsBoth>) : launch(GBufferKernel<true, kGBufferPixels>);
+    } else {
+        both ? launch(GBufferKernel<false, kGBufferPixelsBoth>) : launch(GBufferKernel<false, kGBufferPixels>);
     }
     return hipGetLastError();
 }

@@ -312,6 +312,27 @@ void DeviceScene::Shade(const float* d_offsets, const int* d_ids, float* d_rgba,
     RecordOrder(stream);
 }
 
+void DeviceScene::GBuffer(bool points, const float* d_where, const int* d_ids, std::size_t row_begin,
+                          std::size_t count, float* d_depth, float* d_bary, float* d_normal, float* d_albedo,
+                          hipStream_t stream) const {
+    if (m_width == 0) {
+        throw std::runtime_error("GBuffer: Prepare() has not been called");
+    }
+    if (!points && (row_begin > m_height || count > m_height - row_begin)) {
+        throw std::runtime_error("GBuffer: row band outside the frame");
+    }
+    if (count == 0 || (d_depth == nullptr && d_bary == nullptr && d_normal == nullptr && d_albedo == nullptr)) {
+        return;
+    }
+    OrderAfterPrevious(stream);
+    // (points: one row of `count` elements)
+    const GBufferArgs args{points, d_where, d_ids, points ? count : m_width, m_height, points ? 0 : row_begin,
+                           points ? 1 : count, d_depth, d_bary, d_normal, d_albedo};
+    HipCheck(LaunchGBuffer(m_vertices, m_shade, m_n, m_frame, m_background, args, stream), "G-buffer launch");
+    LogSetupStats();  // (the counters as they stand: this call builds nothing)
+    RecordOrder(stream);
+}
+
 // Grow-only cull work for `slots` frame slots of one carve-up (render.h CullBins; counters reset
 // themselves, so a slot's counters are zero-filled only on its first use with this carve-up), in the
 // arena of this band shape.
@@ -676,8 +697,8 @@ bool DeviceScene::OnSharedSetup(std::size_t row_begin, std::size_t row_count, st
            CullFusedInfo(row_begin, row_count, m_height, row_interleave);
 }
 
-// Env SRT_SETUP_LOG (read per call; unset, empty or "0": off): after every binned cull call one line on
-// stderr with the scene's counters so far -- what tells a run on the shared setup from a silent
+// Env SRT_SETUP_LOG (read per call; unset, empty or "0": off): after every binned cull, query and
+// G-buffer call one line on stderr with the scene's counters so far -- what tells a run on the shared setup from a silent
 // per-frame one (tests/test_gpu_shared_setup.py; the C ABI has no entry for them).
 void DeviceScene::LogSetupStats() const {
     const char* e = std::getenv("SRT_SETUP_LOG");

@@ -111,6 +111,14 @@ public:
     void Query(const float* d_positions, std::size_t count, int* d_ids, float* d_t, unsigned char* d_how,
                hipStream_t stream) const;
 
+    // G-buffer: the surface attributes (render.h GBufferArgs: depth, bary, normal, albedo; a null
+    // plane is not written) of hit ids on the prepared frame. points: `count` positions d_where
+    // (count x 2) with d_ids (count), row_begin unused. Else the band rows [row_begin, row_begin +
+    // count) of the frame, d_where its sample offsets and d_ids its ids, band-local as Shade's.
+    // Reads the scene's vertices and shading table only: no cull setup is built or read.
+    void GBuffer(bool points, const float* d_where, const int* d_ids, std::size_t row_begin, std::size_t count,
+                 float* d_depth, float* d_bary, float* d_normal, float* d_albedo, hipStream_t stream) const;
+
     std::size_t width() const { return m_width; }
     // The spatial order (device, triangles entries) and the time its build took at load (ms).
     const unsigned* order() const { return m_order; }

@@ -12,6 +12,7 @@
 #include "render.h"
 #include "renderer.h"
 #include "scene.h"
+#include "srt_gbuffer.h"
 #include "srt_query.h"
 #include "srt_render.h"
 #include "tile_lookup.h"
@@ -783,6 +784,83 @@ RTQ_API int rtqTileHost(size_t width, size_t height, float fx, float fy, int* ti
                                  srt::kCullTileRows, nx, ny, *tile_col, *tile_row)) {
             throw std::runtime_error("Position outside [0, 1]^2: no tile");
         }
+    });
+}
+
+// G-buffer outputs (include/srt_gbuffer.h): the rtg family.
+namespace {
+
+rtg_outputs CheckedOutputs(const rtg_outputs* o) {
+    if (o == nullptr) {
+        throw std::runtime_error("Bad argument: outputs is NULL");
+    }
+    if (o->struct_size != sizeof(rtg_outputs)) {
+        throw std::runtime_error("rtg_outputs.struct_size is " + std::to_string(o->struct_size) + ", expected " +
+                                 std::to_string(sizeof(rtg_outputs)));
+    }
+    return *o;
+}
+
+bool NoPlane(const rtg_outputs& o) {
+    return o.depth == nullptr && o.bary == nullptr && o.normal == nullptr && o.albedo == nullptr;
+}
+
+}  // namespace
+
+RTG_API int rtgFrameAsync(srt_device_scene scene, const float* d_offsets, const int* d_ids, size_t row_begin,
+                          size_t row_count, const rtg_outputs* outputs, void* stream) {
+    return Guarded([&] {
+        if (scene == nullptr) {
+            throw std::runtime_error("Bad scene handle");
+        }
+        const rtg_outputs o = CheckedOutputs(outputs);
+        if (row_count != 0 && !NoPlane(o)) {
+            if (d_offsets == nullptr) {
+                throw std::runtime_error("Bad buffer argument: d_offsets is NULL");
+            }
+            if (d_ids == nullptr) {
+                throw std::runtime_error("Bad buffer argument: d_ids is NULL");
+            }
+        }
+        srt::DeviceScene* s = FromHandle(scene);
+        Bind bind(s->device());
+        s->GBuffer(false, d_offsets, d_ids, row_begin, row_count, o.depth, o.bary, o.normal, o.albedo,
+                   static_cast<hipStream_t>(stream));
+    });
+}
+
+RTG_API int rtgPointsAsync(srt_device_scene scene, const float* d_positions, const int* d_ids, size_t count,
+                           const rtg_outputs* outputs, void* stream) {
+    return Guarded([&] {
+        if (scene == nullptr) {
+            throw std::runtime_error("Bad scene handle");
+        }
+        const rtg_outputs o = CheckedOutputs(outputs);
+        if (count != 0 && !NoPlane(o)) {
+            if (d_positions == nullptr) {
+                throw std::runtime_error("Bad buffer argument: d_positions is NULL");
+            }
+            if (d_ids == nullptr) {
+                throw std::runtime_error("Bad buffer argument: d_ids is NULL");
+            }
+        }
+        srt::DeviceScene* s = FromHandle(scene);
+        Bind bind(s->device());
+        s->GBuffer(true, d_positions, d_ids, 0, count, o.depth, o.bary, o.normal, o.albedo,
+                   static_cast<hipStream_t>(stream));
+    });
+}
+
+RTG_API int rtgPointsHost(const char* scene_path, size_t width, size_t height, const float* positions,
+                          const int* ids, size_t count, const rtg_outputs* outputs) {
+    return Guarded([&] {
+        const rtg_outputs o = CheckedOutputs(outputs);
+        if (scene_path == nullptr || width == 0 || height == 0 ||
+            (count != 0 && !NoPlane(o) && (positions == nullptr || ids == nullptr))) {
+            throw std::runtime_error("Bad argument");
+        }
+        const srt::Scene scene = srt::LoadScene(scene_path);
+        srt::HostGBuffer(scene, width, height, positions, ids, count, o.depth, o.bary, o.normal, o.albedo);
     });
 }
 

@@ -1,5 +1,5 @@
-"""Scene files, the device-level render stages (include/srt_render.h) and point queries
-(include/srt_query.h).
+"""Scene files, the device-level render stages (include/srt_render.h), point queries
+(include/srt_query.h) and G-buffer outputs (include/srt_gbuffer.h).
 
 ``DeviceScene`` keeps a scene resident on one GPU and launches the two stages on a caller's
 HIP stream with caller-owned device buffers (torch tensors or raw pointers):
@@ -8,6 +8,7 @@ HIP stream with caller-owned device buffers (torch tensors or raw pointers):
     scene.prepare(W, H, stream)                                  # edge records
     scene.trace(offsets, rgba, row_begin, row_count, stream=s)   # closest hit + shade
     scene.query(positions, ids, t, stream=s)                     # closest hit at arbitrary image positions
+    scene.gbuffer(offsets, ids, depth=d, normal=n, albedo=a)     # the surface under the hits (also attributes())
 
 This is the path bench.py times (inputs resident in HBM) and the one-process-per-GPU
 band renderer uses; ``runner.render`` is the host-image ml* path.
@@ -109,6 +110,30 @@ def query_host(path: str, width: int, height: int, positions):
     _check(_native.lib().rtqQueryHost(os.fsencode(path), width, height, pos.ctypes.data, pos.shape[0],
                                       ids.ctypes.data, t.ctypes.data))
     return ids, t
+
+
+def attributes_host(path: str, width: int, height: int, positions, ids):
+    """The G-buffer on the host (rtgPointsHost: the library's canonical math, no device):
+    positions (count, 2) float32 and ids (count,) int32 -> (depth (count,), bary (count, 2),
+    normal (count, 4), albedo (count, 4)), float32 numpy arrays."""
+    import numpy as np
+
+    pos = np.ascontiguousarray(positions, np.float32)
+    idv = np.ascontiguousarray(ids, np.int32)
+    if pos.ndim != 2 or pos.shape[1] != 2:
+        raise ValueError(f"positions must be (count, 2), got {pos.shape}")
+    if idv.shape != (pos.shape[0],):
+        raise ValueError(f"ids must be {(pos.shape[0],)}, got {idv.shape}")
+    count = pos.shape[0]
+    depth = np.empty(count, np.float32)
+    bary = np.empty((count, 2), np.float32)
+    normal = np.empty((count, 4), np.float32)
+    albedo = np.empty((count, 4), np.float32)
+    out = _native.RtgOutputs(ctypes.sizeof(_native.RtgOutputs), depth.ctypes.data, bary.ctypes.data,
+                             normal.ctypes.data, albedo.ctypes.data)
+    _check(_native.lib().rtgPointsHost(os.fsencode(path), width, height, pos.ctypes.data, idv.ctypes.data, count,
+                                       ctypes.byref(out)))
+    return depth, bary, normal, albedo
 
 
 def tile_of(width: int, height: int, fx: float, fy: float):
@@ -303,6 +328,54 @@ class DeviceScene:
             raise ValueError("positions must have a shape (count, 2): raw pointers carry no count")
         _check(self._lib.rtqQueryAsync(self.handle, _ptr(positions), count, _ptr(ids), _ptr(t), _ptr(how),
                                        _stream(stream)))
+
+    def _outputs(self, planes, lead):
+        """rtg_outputs of the planes depth / bary / normal / albedo (None: not written), each
+        checked to be `lead` + its channel tail."""
+        out = _native.RtgOutputs(ctypes.sizeof(_native.RtgOutputs), 0, 0, 0, 0)
+        for name, buf, tail in planes:
+            if buf is None:
+                continue
+            if hasattr(buf, "shape") and tuple(buf.shape) != lead + tail:
+                raise ValueError(f"{name} must be {lead + tail}, got {tuple(buf.shape)}")
+            self._check_tensor(name, buf, "f32")
+            setattr(out, name, _ptr(buf))
+        return out
+
+    def gbuffer(self, offsets, ids, depth=None, bary=None, normal=None, albedo=None, row_begin: int = 0,
+                row_count: int | None = None, stream=None):
+        """G-buffer of the prepared frame's rows from hit ids (include/srt_gbuffer.h): offsets
+        (rows, W, 2) float32 and ids (rows, W) int32 -> any of depth (rows, W), bary (rows, W, 2),
+        normal (rows, W, 4) = (unit normal towards the eye, shading cosine), albedo (rows, W, 4) =
+        (r, g, b, float(id)), float32 device buffers; a plane left None is not written."""
+        if row_count is None:
+            row_count = self.height - row_begin
+        self._check_buffer("offsets", offsets, row_count, 2, "f32")
+        self._check_buffer("ids", ids, row_count, 0, "i32")
+        out = self._outputs((("depth", depth, ()), ("bary", bary, (2,)), ("normal", normal, (4,)),
+                             ("albedo", albedo, (4,))), (row_count, self.width))
+        _check(self._lib.rtgFrameAsync(self.handle, _ptr(offsets), _ptr(ids), row_begin, row_count, ctypes.byref(out),
+                                       _stream(stream)))
+
+    def attributes(self, positions, ids, depth=None, bary=None, normal=None, albedo=None, stream=None):
+        """G-buffer at arbitrary image positions: positions (count, 2) float32 and ids (count,)
+        int32 -- query()'s input and output -- -> any of depth (count,), bary (count, 2), normal
+        (count, 4), albedo (count, 4), as gbuffer()'s."""
+        count = None
+        for name, buf, tail, dtype in (("positions", positions, (2,), "f32"), ("ids", ids, (), "i32")):
+            if hasattr(buf, "shape"):
+                shape = tuple(buf.shape)
+                if len(shape) != 1 + len(tail) or shape[1:] != tail or (count is not None and shape[0] != count):
+                    want = ("count" if count is None else count,) + tail
+                    raise ValueError(f"{name} must be {want}, got {shape}")
+                count = shape[0]
+            self._check_tensor(name, buf, dtype)
+        if count is None:
+            raise ValueError("positions must have a shape (count, 2): raw pointers carry no count")
+        out = self._outputs((("depth", depth, ()), ("bary", bary, (2,)), ("normal", normal, (4,)),
+                             ("albedo", albedo, (4,))), (count,))
+        _check(self._lib.rtgPointsAsync(self.handle, _ptr(positions), _ptr(ids), count, ctypes.byref(out),
+                                        _stream(stream)))
 
     def spatial_order(self):
         """(order, build_ms): the record ids in spatial order (numpy uint32), built on the device
