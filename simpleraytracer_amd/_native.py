@@ -1,5 +1,5 @@
 """ctypes binding of libModelRunner.so (include/model_runner.h + include/srt_render.h + include/srt_query.h +
-include/srt_gbuffer.h).
+include/srt_gbuffer.h + include/srt_samples.h).
 
 The shared library is built in-tree by ``make`` (or ``__graft_entry__.build()``) into
 ``simpleraytracer_amd/lib/libModelRunner.so``. There is no fallback: importing the renderer
@@ -41,6 +41,7 @@ SRT_SPLIT_BANDS = 0
 SRT_SPLIT_FRAMES = 1
 SRT_ENGINE_RCCL_SELF = 1  # srt_engine_options.flags
 SRT_TILE_ROWS = 16  # include/srt_render.h: rows per tile row (interleaved bands deal these)
+RTS_MAX_SAMPLES = 16  # include/srt_samples.h: sample planes per rtsResolveAsync / rtsRenderAsync call
 
 
 class ImageInfo(ctypes.Structure):
@@ -101,6 +102,7 @@ class RtgOutputs(ctypes.Structure):
 _SZ = ctypes.c_size_t
 _PSZ = ctypes.POINTER(ctypes.c_size_t)
 _PD = ctypes.POINTER(ctypes.c_double)
+_PVP = ctypes.POINTER(ctypes.c_void_p)
 
 # name -> (restype, argtypes)
 _SIGNATURES = {
@@ -187,6 +189,11 @@ _SIGNATURES = {
                                       ctypes.POINTER(RtgOutputs), ctypes.c_void_p]),
     "rtgPointsHost": (ctypes.c_int, [ctypes.c_char_p, _SZ, _SZ, ctypes.c_void_p, ctypes.c_void_p, _SZ,
                                      ctypes.POINTER(RtgOutputs)]),
+    # include/srt_samples.h: multi-sample frames (the plane arrays: ctypes.c_void_p arrays, or None)
+    "rtsResolveAsync": (ctypes.c_int, [ctypes.c_void_p, _PVP, _PVP, _SZ, _SZ, _SZ, ctypes.c_void_p, ctypes.c_void_p]),
+    "rtsRenderAsync": (ctypes.c_int, [ctypes.c_void_p, _PVP, _PVP, _SZ, ctypes.c_void_p, ctypes.c_int,
+                                      ctypes.c_void_p]),
+    "rtsResolveHost": (ctypes.c_int, [ctypes.c_char_p, _SZ, _SZ, _PVP, _PVP, _SZ, _SZ, _SZ, ctypes.c_void_p]),
 }
 
 _lib = None

@@ -1,6 +1,7 @@
 #include "cpu_render.h"
 
 #include "gbuffer_math.h"
+#include "samples_math.h"
 #include "screen_box.h"
 
 #include <algorithm>
@@ -258,6 +259,43 @@ void HostGBuffer(const Scene& scene, std::size_t width, std::size_t height, cons
             const float v[4] = {o.r, o.g, o.b, o.a};
             std::copy(v, v + 4, albedo + 4 * q);
         }
+    });
+}
+
+void HostResolve(const Scene& scene, std::size_t width, std::size_t height, const float* const* offsets,
+                 const int* const* ids, std::size_t samples, std::size_t row_begin, std::size_t row_count, float* rgba) {
+    if (width == 0 || height == 0) {
+        throw std::runtime_error("Host resolve: frame dimensions must be non-zero");
+    }
+    if (samples == 0) {
+        throw std::runtime_error("Host resolve: samples must be positive");
+    }
+    if (row_begin > height || row_count > height - row_begin) {
+        throw std::runtime_error("Host resolve: row band outside the frame");
+    }
+    const Frame f = MakeFrame(scene.camera, width, height);
+    const std::size_t n = scene.triangle_count();
+    const float wf = static_cast<float>(width), hf = static_cast<float>(height);
+    const ResolveRgb miss{scene.background[0], scene.background[1], scene.background[2]};
+    ParallelFor(row_count * width, 1024, [&](std::size_t i) {
+        const unsigned x = static_cast<unsigned>(i % width), y = static_cast<unsigned>(row_begin + i / width);
+        ResolveAcc acc{};
+        for (std::size_t s = 0; s < samples; ++s) {
+            const int id = ids[s][i];
+            const bool hit = id >= 0 && static_cast<std::size_t>(id) < n;
+            ResolveRgb c = miss;
+            if (hit) {
+                const Rec r = MakeRecord(scene.vertices.data() + 9 * static_cast<std::size_t>(id), f);
+                const float* a = scene.albedo.data() + 3 * static_cast<std::size_t>(id);
+                float fx, fy;
+                ResolvePosition(x, y, offsets[s][2 * i], offsets[s][2 * i + 1], wf, hf, fx, fy);
+                c = ResolveShadeHit(f.base, f.du, f.dv, fx, fy, r.n[0], r.n[1], r.n[2], r.n[3], a[0], a[1], a[2]);
+            }
+            ResolveAdd(acc, static_cast<unsigned>(s), c, hit);
+        }
+        const ResolveTexel t = ResolveFinish(acc, static_cast<unsigned>(samples));
+        const float v[4] = {t.r, t.g, t.b, t.a};
+        std::copy(v, v + 4, rgba + 4 * i);
     });
 }
 

@@ -38,6 +38,14 @@ void HostClosestHits(const Scene& scene, std::size_t width, std::size_t height, 
 void HostGBuffer(const Scene& scene, std::size_t width, std::size_t height, const float* positions, const int* ids,
                  std::size_t count, float* depth, float* bary, float* normal, float* albedo);
 
+// The resolve of `samples` sample planes of the band rows [row_begin, row_begin + row_count) of the
+// scene's width x height frame (the host answer of render.h LaunchResolve; samples_math.h):
+// offsets[s] (row_count x width x 2) and ids[s] (row_count x width), band-local, into rgba
+// (row_count x width x 4) -- the mean of the shaded samples, alpha = the share that hit. An id
+// outside the scene is a miss.
+void HostResolve(const Scene& scene, std::size_t width, std::size_t height, const float* const* offsets,
+                 const int* const* ids, std::size_t samples, std::size_t row_begin, std::size_t row_count, float* rgba);
+
 // Whether env ML_VISIBLE_DEVICES selects the CPU backend ("cpu", or set to the empty string).
 bool CpuBackendSelected();
 

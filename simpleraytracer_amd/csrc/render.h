@@ -384,6 +384,28 @@ struct GBufferArgs {
 hipError_t LaunchGBuffer(const float* d_vertices, const float* d_shade, std::uint64_t n, const Frame& frame,
                          const float background[3], const GBufferArgs& args, hipStream_t stream);
 
+// Resolve (render.hip ResolveKernel): one RGBA pixel from `samples` (sample offset, hit id) planes
+// of a band -- every sample shaded as LaunchShade shades it, summed in ascending order and divided
+// by the count; alpha = the share of samples that hit (samples_math.h; DESIGN.md section 2
+// "Resolve"). Reads the shading table only. An id outside [0, n) is a miss and reads nothing
+// through it.
+constexpr int kMaxSamples = 16;
+struct ResolveArgs {
+    // Host arrays of `samples` (1 .. kMaxSamples) device pointers, band-local as LaunchShade's:
+    // offsets[s] = row_count x width x 2, ids[s] = row_count x width.
+    const float* const* offsets;
+    const int* const* ids;
+    std::size_t samples;
+    std::size_t width;
+    std::size_t height;
+    std::size_t row_begin;
+    std::size_t row_count;
+    float* rgba;  // device, row_count x width x 4
+};
+// One launch (the plane pointers travel in the kernel's arguments); no rows: none.
+hipError_t LaunchResolve(const float* d_shade, std::uint64_t n, const Frame& frame, const float background[3],
+                         const ResolveArgs& args, hipStream_t stream);
+
 // Deferred shading of a band from hit ids (band.ids) and sample offsets into band.rgba (normals
 // from the vertices, d_edges unused): bit-identical to the fused trace.
 // frames > 1 shades a batch whose ids are band-major, ids[band][frame][band_rows][width] (a

@@ -5,6 +5,7 @@
 // fmaf, so CPU (oracle/srt_oracle.c) and GPU evaluate bit-identical float expressions.
 #include "render.h"
 #include "gbuffer_math.h"
+#include "samples_math.h"
 #include "screen_box.h"
 #include "tile_lookup.h"
 
@@ -985,6 +986,116 @@ __global__ __launch_bounds__(kGBufferThreads) void GBufferKernel(const GBufferPa
         if (q.albedo != nullptr) {
             StoreNontemporal(q.albedo + at, F4{o.r, o.g, o.b, o.a});
         }
+    }
+}
+
+// ---------------------------------------------------------------------------------------
+// Resolve (render.h LaunchResolve; DESIGN.md section 5 "Multi-sample frames"): one RGBA pixel from
+// S sample planes -- S hit ids and S sample offsets per pixel in, the mean of the S shaded samples
+// and the coverage out (samples_math.h), instead of S RGBA frames written, read back and averaged.
+// The 2 x kMaxSamples plane pointers are kernel arguments. Element mapping as GBufferKernel's: a
+// block takes kResolveThreads consecutive pixels of one band row, a thread one pixel, so every wave
+// instruction loads consecutive ids and offsets and stores consecutive pixels. The samples are
+// taken in groups of G, each group in three phases with no control flow that depends on loaded data
+// between its loads: (1) the group's ids and offsets, (2) the group's shading table rows (an id
+// outside the scene gathers row 0, unused), (3) the arithmetic, strictly in ascending s. A thread
+// has G dependent chains (id -> table row) in flight. The samples that do not fill a group of G are
+// taken in groups of G / 2, G / 4, ... 1 (S = 9, G = 8: a group of 8 and one of 1; loading a padded
+// last group's planes twice cost S = 1 at G = 4 27.0 us against 19.4 at G = 1). No LDS, no atomics,
+// no scratch.
+// G, measured at C3 (1 / 2 / 4 / 8: DESIGN.md; profiles/samples/): 8 is fastest from S = 8 on (S = 8
+// 68.5 / 59.2 / 55.9 / 52.8 us, S = 16 128.0 / 106.9 / 103.2 / 99.4 us: 106 VGPRs, four waves per SIMD,
+// twice the loads in flight per wave), 4 below it (S = 4 40.7 / 35.9 / 33.4 / 36.5 us: 62 VGPRs, eight
+// waves, and no group of 8 to fill). SRT_RESOLVE_GROUP, SRT_RESOLVE_GROUP_LONG: measurement builds.
+// ---------------------------------------------------------------------------------------
+#ifndef SRT_RESOLVE_GROUP
+#define SRT_RESOLVE_GROUP 4
+#endif
+#ifndef SRT_RESOLVE_GROUP_LONG
+#define SRT_RESOLVE_GROUP_LONG 8
+#endif
+constexpr int kResolveGroup = SRT_RESOLVE_GROUP;           // samples per group, S < kResolveLong
+constexpr int kResolveGroupLong = SRT_RESOLVE_GROUP_LONG;  // ... S >= kResolveLong
+constexpr unsigned kResolveLong = 8;
+constexpr int kResolveThreads = 256;
+static_assert(kResolveGroup >= 1 && (kResolveGroup & (kResolveGroup - 1)) == 0 && kResolveGroupLong >= 1 &&
+                  (kResolveGroupLong & (kResolveGroupLong - 1)) == 0,
+              "groups halve down to 1");
+struct ResolveParams {
+    const float2* offsets[kMaxSamples];
+    const int* ids[kMaxSamples];
+    const float4* __restrict__ shade;
+    F4* __restrict__ out;
+    unsigned n;
+    unsigned samples;
+    unsigned width;
+    unsigned chunks;  // blocks per row
+    unsigned row_begin;
+    float wf, hf;
+    float base[3], du[3], dv[3], bg[3];
+};
+
+// The samples [s0, ...) of pixel (x, y) (its planes' element `at`) join acc in groups of G while G
+// of them are left, then in groups of G / 2, ... 1; s0 ends at q.samples.
+template <int G>
+__device__ __forceinline__ void ResolveGroups(const ResolveParams& q, size_t at, unsigned x, unsigned y, unsigned& s0,
+                                              ResolveAcc& acc) {
+    for (; s0 + G <= q.samples; s0 += G) {  // (uniform)
+        // (1)
+        int code[G];
+        float2 o[G];
+#pragma unroll
+        for (int k = 0; k < G; ++k) {
+            code[k] = __builtin_nontemporal_load(q.ids[s0 + k] + at);
+            o[k] = q.offsets[s0 + k][at];
+        }
+        // (2)
+        int hit[G];
+        float4 nr[G], al[G];
+#pragma unroll
+        for (int k = 0; k < G; ++k) {
+            hit[k] = static_cast<unsigned>(code[k]) < q.n ? code[k] : -1;
+            nr[k] = al[k] = float4{};
+        }
+        if (q.n != 0u) {  // (an empty scene has no row 0)
+#pragma unroll
+            for (int k = 0; k < G; ++k) {
+                const float4* sr = q.shade + 2ull * static_cast<unsigned>(max(hit[k], 0));
+                nr[k] = sr[0];
+                al[k] = sr[1];
+            }
+        }
+        // (3)
+#pragma unroll
+        for (int k = 0; k < G; ++k) {
+            ResolveRgb c{q.bg[0], q.bg[1], q.bg[2]};
+            if (hit[k] >= 0) {
+                float fx, fy;
+                ResolvePosition(x, y, o[k].x, o[k].y, q.wf, q.hf, fx, fy);
+                c = ResolveShadeHit(q.base, q.du, q.dv, fx, fy, nr[k].x, nr[k].y, nr[k].z, nr[k].w, al[k].x, al[k].y,
+                                    al[k].z);
+            }
+            ResolveAdd(acc, s0 + k, c, hit[k] >= 0);
+        }
+    }
+    if constexpr (G > 1) {
+        ResolveGroups<G / 2>(q, at, x, y, s0, acc);
+    }
+}
+
+template <int G>
+__global__ __launch_bounds__(kResolveThreads) void ResolveKernel(const ResolveParams q) {
+    const unsigned row = blockIdx.x / q.chunks;  // (uniform: scalar)
+    const unsigned chunk = blockIdx.x - row * q.chunks;
+    const unsigned x = chunk * kResolveThreads + threadIdx.x;
+    // A pixel past the row loads the row's last one and is not stored.
+    const size_t at = static_cast<size_t>(row) * q.width + min(x, q.width - 1u);
+    ResolveAcc acc{};
+    unsigned s0 = 0;
+    ResolveGroups<G>(q, at, x, q.row_begin + row, s0, acc);
+    if (x < q.width) {
+        const ResolveTexel t = ResolveFinish(acc, q.samples);
+        __builtin_nontemporal_store(F4{t.r, t.g, t.b, t.a}, q.out + at);
     }
 }
 
@@ -4531,6 +4642,51 @@ hipError_t LaunchGBuffer(const float* d_vertices, const float* d_shade, std::uin
         both ? launch(GBufferKernel<true, kGBufferPixelsBoth>) : launch(GBufferKernel<true, kGBufferPixels>);
     } else {
         both ? launch(GBufferKernel<false, kGBufferPixelsBoth>) : launch(GBufferKernel<false, kGBufferPixels>);
+    }
+    return hipGetLastError();
+}
+
+hipError_t LaunchResolve(const float* d_shade, std::uint64_t n, const Frame& frame, const float background[3],
+                         const ResolveArgs& args, hipStream_t stream) {
+    if (args.width == 0 || args.row_count == 0) {
+        return hipSuccess;
+    }
+    const std::size_t chunks = (args.width + kResolveThreads - 1) / kResolveThreads;
+    if (args.offsets == nullptr || args.ids == nullptr || args.rgba == nullptr || d_shade == nullptr ||
+        args.samples == 0 || args.samples > static_cast<std::size_t>(kMaxSamples) || n > 0xFFFFFFFFull ||
+        args.width > 0xFFFFFFFFull - kResolveThreads || args.height == 0 || args.row_begin > args.height ||
+        args.row_count > args.height - args.row_begin || args.height > 0x7FFFFFFFull ||
+        args.row_count > 0x7FFFFFFFull / chunks) {
+        return hipErrorInvalidValue;
+    }
+    ResolveParams q{};
+    for (std::size_t s = 0; s < args.samples; ++s) {
+        if (args.offsets[s] == nullptr || args.ids[s] == nullptr) {
+            return hipErrorInvalidValue;
+        }
+        q.offsets[s] = reinterpret_cast<const float2*>(args.offsets[s]);
+        q.ids[s] = args.ids[s];
+    }
+    q.shade = reinterpret_cast<const float4*>(d_shade);
+    q.out = reinterpret_cast<F4*>(args.rgba);
+    q.n = static_cast<unsigned>(n);
+    q.samples = static_cast<unsigned>(args.samples);
+    q.width = static_cast<unsigned>(args.width);
+    q.chunks = static_cast<unsigned>(chunks);
+    q.row_begin = static_cast<unsigned>(args.row_begin);
+    q.wf = static_cast<float>(args.width);
+    q.hf = static_cast<float>(args.height);
+    for (int k = 0; k < 3; ++k) {
+        q.base[k] = frame.base[k];
+        q.du[k] = frame.du[k];
+        q.dv[k] = frame.dv[k];
+        q.bg[k] = background[k];
+    }
+    const dim3 grid(static_cast<unsigned>(chunks * args.row_count));
+    if (q.samples >= kResolveLong) {
+        hipLaunchKernelGGL(ResolveKernel<kResolveGroupLong>, grid, dim3(kResolveThreads), 0, stream, q);
+    } else {
+        hipLaunchKernelGGL(ResolveKernel<kResolveGroup>, grid, dim3(kResolveThreads), 0, stream, q);
     }
     return hipGetLastError();
 }

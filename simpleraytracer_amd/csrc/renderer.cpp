@@ -333,6 +333,47 @@ void DeviceScene::GBuffer(bool points, const float* d_where, const int* d_ids, s
     RecordOrder(stream);
 }
 
+void DeviceScene::Resolve(const float* const* d_offsets, const int* const* d_ids, std::size_t samples,
+                          std::size_t row_begin, std::size_t row_count, float* d_rgba, hipStream_t stream) const {
+    if (m_width == 0) {
+        throw std::runtime_error("Resolve: Prepare() has not been called");
+    }
+    if (samples == 0 || samples > static_cast<std::size_t>(kMaxSamples)) {
+        throw std::runtime_error("Resolve: samples must be 1 to " + std::to_string(kMaxSamples) + ", got " +
+                                 std::to_string(samples));
+    }
+    if (row_begin > m_height || row_count > m_height - row_begin) {
+        throw std::runtime_error("Resolve: row band outside the frame");
+    }
+    if (row_count == 0) {
+        return;
+    }
+    OrderAfterPrevious(stream);
+    const ResolveArgs args{d_offsets, d_ids, samples, m_width, m_height, row_begin, row_count, d_rgba};
+    HipCheck(LaunchResolve(m_shade, m_n, m_frame, m_background, args, stream), "resolve launch");
+    LogSetupStats();  // (the counters as they stand: this call builds nothing)
+    RecordOrder(stream);
+}
+
+void DeviceScene::RenderSamples(const float* const* d_offsets, int* const* d_ids, std::size_t samples, float* d_rgba,
+                                int variant, hipStream_t stream) const {
+    if (m_width == 0) {
+        throw std::runtime_error("RenderSamples: Prepare() has not been called");
+    }
+    if (samples == 0 || samples > static_cast<std::size_t>(kMaxSamples)) {
+        throw std::runtime_error("RenderSamples: samples must be 1 to " + std::to_string(kMaxSamples) + ", got " +
+                                 std::to_string(samples));
+    }
+    // Every chunk on the trace grid of the largest one: the shared setup is keyed by it, so a
+    // remainder chunk with a grid of its own would build the setup again.
+    const std::size_t chunk = std::min(samples, static_cast<std::size_t>(kMaxBatch));
+    for (std::size_t s = 0; s < samples; s += chunk) {
+        TraceBatch(d_offsets + s, nullptr, d_ids + s, std::min(chunk, samples - s), 0, m_height, variant, stream, 1, -1,
+                   false, nullptr, chunk);
+    }
+    Resolve(d_offsets, d_ids, samples, 0, m_height, d_rgba, stream);
+}
+
 // Grow-only cull work for `slots` frame slots of one carve-up (render.h CullBins; counters reset
 // themselves, so a slot's counters are zero-filled only on its first use with this carve-up), in the
 // arena of this band shape.
@@ -469,7 +510,7 @@ DeviceScene::ParamTable& DeviceScene::AcquireTable(std::size_t frames, hipStream
 void DeviceScene::TraceBatch(const float* const* d_offsets, float* const* d_rgba, int* const* d_ids, std::size_t frames,
                              std::size_t row_begin, std::size_t row_count, int variant, hipStream_t stream,
                              std::size_t row_interleave, int id_planes, bool rgba_frame_rows,
-                             const std::size_t* row_begins) const {
+                             const std::size_t* row_begins, std::size_t plan_frames) const {
     if (id_planes >= 0 && (id_planes != IdPlanes(m_n) || variant != kTraceCull)) {
         throw std::runtime_error("TraceBatch: packed ids need the cull variant and " + std::to_string(IdPlanes(m_n)) +
                                  " bit planes for this scene");
@@ -506,7 +547,8 @@ void DeviceScene::TraceBatch(const float* const* d_offsets, float* const* d_rgba
         return;
     }
     if (row_begins == nullptr && OnSharedSetup(row_begin, row_count, row_interleave)) {
-        TraceShared(d_offsets, d_rgba, d_ids, frames, stream, id_planes, rgba_frame_rows);
+        TraceShared(d_offsets, d_rgba, d_ids, frames, stream, id_planes, rgba_frame_rows,
+                    std::max(frames, plan_frames));
         return;
     }
     m_setup_stats.per_frame_frames += frames;
@@ -568,7 +610,7 @@ void DeviceScene::Trace(const float* d_offsets, float* d_rgba, std::size_t row_b
     if (binned && OnSharedSetup(row_begin, row_count, row_interleave)) {
         float* const rgba1[1] = {d_rgba};
         int* const ids1[1] = {d_ids};
-        TraceShared(&d_offsets, rgba1, d_ids != nullptr ? ids1 : nullptr, 1, stream, id_planes, rgba_frame_rows);
+        TraceShared(&d_offsets, rgba1, d_ids != nullptr ? ids1 : nullptr, 1, stream, id_planes, rgba_frame_rows, 1);
         return;
     }
     OrderAfterPrevious(stream);
@@ -697,8 +739,8 @@ bool DeviceScene::OnSharedSetup(std::size_t row_begin, std::size_t row_count, st
            CullFusedInfo(row_begin, row_count, m_height, row_interleave);
 }
 
-// Env SRT_SETUP_LOG (read per call; unset, empty or "0": off): after every binned cull, query and
-// G-buffer call one line on stderr with the scene's counters so far -- what tells a run on the shared setup from a silent
+// Env SRT_SETUP_LOG (read per call; unset, empty or "0": off): after every binned cull, query,
+// G-buffer and resolve call one line on stderr with the scene's counters so far -- what tells a run on the shared setup from a silent
 // per-frame one (tests/test_gpu_shared_setup.py; the C ABI has no entry for them).
 void DeviceScene::LogSetupStats() const {
     const char* e = std::getenv("SRT_SETUP_LOG");
@@ -712,7 +754,8 @@ void DeviceScene::LogSetupStats() const {
 }
 
 void DeviceScene::TraceShared(const float* const* d_offsets, float* const* d_rgba, int* const* d_ids,
-                              std::size_t frames, hipStream_t stream, int id_planes, bool rgba_frame_rows) const {
+                              std::size_t frames, hipStream_t stream, int id_planes, bool rgba_frame_rows,
+                              std::size_t plan_frames) const {
     OrderAfterPrevious(stream);
     // The frame slots' own state (tile facts, split key slices, arrival counters) lives in the cull
     // work of the whole-frame shape; no edge slots: the records are the setup's.
@@ -724,7 +767,7 @@ void DeviceScene::TraceShared(const float* const* d_offsets, float* const* d_rgb
     for (std::size_t f = 0; f < frames; ++f) {
         // (not CullSlot: the slot's count parity and its per-frame plan stay as the per-frame path left them)
         bins[f] = CullBinLayout(a.work + f * a.layout, m_n, m_width, m_height);
-        bins[f].descs = std::min(bins[f].descs, CullDescriptors(tiles, frames));
+        bins[f].descs = std::min(bins[f].descs, CullDescriptors(tiles, plan_frames));
         bins[f].order = m_order;
         bins[f].svertices = m_svertices;
         cf[f].edges = nullptr;

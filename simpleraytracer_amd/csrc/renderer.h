@@ -98,11 +98,13 @@ public:
     void TraceBatch(const float* const* d_offsets, float* const* d_rgba, int* const* d_ids, std::size_t frames,
                     std::size_t row_begin, std::size_t row_count, int variant, hipStream_t stream,
                     std::size_t row_interleave = 1, int id_planes = -1, bool rgba_frame_rows = false,
-                    const std::size_t* row_begins = nullptr) const;
+                    const std::size_t* row_begins = nullptr, std::size_t plan_frames = 0) const;
     // (A frame f with d_ids non-null but d_ids[f] null and d_rgba[f] non-null is traced to RGBA;
     // rgba_frame_rows: RGBA outputs are whole frames, band rows stored at their frame rows;
     // row_begins: frame f's band starts at row_begins[f] instead -- one row count and pattern, so one
-    // band shape, for every frame; cull variant, bands short of the whole frame.)
+    // band shape, for every frame; cull variant, bands short of the whole frame.
+    // plan_frames > frames: on the shared setup the trace grid is the one of a plan_frames-frame
+    // call, so the chunks of a longer frame set -- RenderSamples' -- share one setup build.)
 
     // Point queries: the closest hit at `count` image positions (fx, fy) of the prepared frame
     // (d_positions: count x 2) into d_ids (-1 = miss), d_t (+inf = miss) and, non-null, d_how
@@ -118,6 +120,18 @@ public:
     // Reads the scene's vertices and shading table only: no cull setup is built or read.
     void GBuffer(bool points, const float* d_where, const int* d_ids, std::size_t row_begin, std::size_t count,
                  float* d_depth, float* d_bary, float* d_normal, float* d_albedo, hipStream_t stream) const;
+
+    // Multi-sample frames (render.h LaunchResolve). Resolve: the band rows [row_begin, row_begin +
+    // row_count) of the prepared frame from `samples` (1 .. kMaxSamples) planes of sample offsets
+    // and hit ids -- host arrays of device pointers, band-local as Shade's -- into d_rgba: the mean
+    // of the shaded samples, alpha = the share that hit. Reads the shading table only: no cull
+    // setup is built or read. RenderSamples: the whole frame -- the id planes traced into the
+    // caller's d_ids through TraceBatch in chunks of at most kMaxBatch (one setup build for all of
+    // them on the shared setup), then resolved.
+    void Resolve(const float* const* d_offsets, const int* const* d_ids, std::size_t samples, std::size_t row_begin,
+                 std::size_t row_count, float* d_rgba, hipStream_t stream) const;
+    void RenderSamples(const float* const* d_offsets, int* const* d_ids, std::size_t samples, float* d_rgba,
+                       int variant, hipStream_t stream) const;
 
     std::size_t width() const { return m_width; }
     // The spatial order (device, triangles entries) and the time its build took at load (ms).
@@ -190,8 +204,9 @@ private:
     // Whether a binned cull trace of this band runs on the shared setup (env SRT_SETUP).
     bool OnSharedSetup(std::size_t row_begin, std::size_t row_count, std::size_t row_interleave) const;
     // Whole frames on the shared setup: the setup (re)built if need be, then tile facts + trace.
+    // plan_frames: the call whose trace grid is used (TraceBatch; at least `frames`).
     void TraceShared(const float* const* d_offsets, float* const* d_rgba, int* const* d_ids, std::size_t frames,
-                     hipStream_t stream, int id_planes, bool rgba_frame_rows) const;
+                     hipStream_t stream, int id_planes, bool rgba_frame_rows, std::size_t plan_frames) const;
     // The setup for a trace grid of `descs` descriptors, (re)built on `stream` if need be.
     CullSetup EnsureSetup(unsigned descs, hipStream_t stream) const;
     Frame m_frame{};

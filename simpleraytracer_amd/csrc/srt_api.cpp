@@ -15,6 +15,7 @@
 #include "srt_gbuffer.h"
 #include "srt_query.h"
 #include "srt_render.h"
+#include "srt_samples.h"
 #include "tile_lookup.h"
 
 namespace {
@@ -861,6 +862,103 @@ RTG_API int rtgPointsHost(const char* scene_path, size_t width, size_t height, c
         }
         const srt::Scene scene = srt::LoadScene(scene_path);
         srt::HostGBuffer(scene, width, height, positions, ids, count, o.depth, o.bary, o.normal, o.albedo);
+    });
+}
+
+// Multi-sample frames (include/srt_samples.h): the rts family.
+static_assert(RTS_MAX_SAMPLES == srt::kMaxSamples, "include/srt_samples.h RTS_MAX_SAMPLES");
+
+namespace {
+
+void CheckSamples(size_t samples) {
+    if (samples == 0 || samples > RTS_MAX_SAMPLES) {
+        throw std::runtime_error("Bad argument: samples must be 1 to " + std::to_string(RTS_MAX_SAMPLES) + ", got " +
+                                 std::to_string(samples));
+    }
+}
+
+// The plane pointer arrays and the output of a call that has pixels to resolve.
+void CheckPlanes(const char* offsets_name, const float* const* offsets, const char* ids_name, const int* const* ids,
+                 size_t samples, const char* rgba_name, const float* rgba) {
+    if (offsets == nullptr) {
+        throw std::runtime_error(std::string("Bad buffer argument: ") + offsets_name + " is NULL");
+    }
+    if (ids == nullptr) {
+        throw std::runtime_error(std::string("Bad buffer argument: ") + ids_name + " is NULL");
+    }
+    for (size_t s = 0; s < samples; ++s) {
+        if (offsets[s] == nullptr) {
+            throw std::runtime_error(std::string("Bad buffer argument: ") + offsets_name + "[" + std::to_string(s) +
+                                     "] is NULL");
+        }
+        if (ids[s] == nullptr) {
+            throw std::runtime_error(std::string("Bad buffer argument: ") + ids_name + "[" + std::to_string(s) +
+                                     "] is NULL");
+        }
+    }
+    if (rgba == nullptr) {
+        throw std::runtime_error(std::string("Bad buffer argument: ") + rgba_name + " is NULL");
+    }
+}
+
+}  // namespace
+
+RTS_API int rtsResolveAsync(srt_device_scene scene, const float* const* d_offsets, const int* const* d_ids,
+                            size_t samples, size_t row_begin, size_t row_count, float* d_rgba, void* stream) {
+    return Guarded([&] {
+        if (scene == nullptr) {
+            throw std::runtime_error("Bad scene handle");
+        }
+        CheckSamples(samples);
+        if (row_count != 0) {
+            CheckPlanes("d_offsets", d_offsets, "d_ids", d_ids, samples, "d_rgba", d_rgba);
+        }
+        srt::DeviceScene* s = FromHandle(scene);
+        Bind bind(s->device());
+        s->Resolve(d_offsets, d_ids, samples, row_begin, row_count, d_rgba, static_cast<hipStream_t>(stream));
+    });
+}
+
+RTS_API int rtsRenderAsync(srt_device_scene scene, const float* const* d_offsets, int* const* d_ids, size_t samples,
+                           float* d_rgba, int variant, void* stream) {
+    return Guarded([&] {
+        if (scene == nullptr) {
+            throw std::runtime_error("Bad scene handle");
+        }
+        CheckSamples(samples);
+        srt::DeviceScene* s = FromHandle(scene);
+        if (s->width() == 0) {
+            throw std::runtime_error("RenderSamples: Prepare() has not been called");
+        }
+        CheckPlanes("d_offsets", d_offsets, "d_ids", d_ids, samples, "d_rgba", d_rgba);
+        if (variant != SRT_TRACE_LDS && variant != SRT_TRACE_SCALAR && variant != SRT_TRACE_CULL &&
+            variant != SRT_TRACE_BVH) {
+            throw std::runtime_error("Unknown trace variant " + std::to_string(variant));
+        }
+        Bind bind(s->device());
+        s->RenderSamples(d_offsets, d_ids, samples, d_rgba, variant, static_cast<hipStream_t>(stream));
+    });
+}
+
+RTS_API int rtsResolveHost(const char* scene_path, size_t width, size_t height, const float* const* offsets,
+                           const int* const* ids, size_t samples, size_t row_begin, size_t row_count, float* rgba) {
+    return Guarded([&] {
+        if (scene_path == nullptr) {
+            throw std::runtime_error("Bad argument: scene_path is NULL");
+        }
+        if (width == 0 || height == 0) {
+            throw std::runtime_error("Bad argument: width and height must be non-zero");
+        }
+        CheckSamples(samples);
+        if (row_begin > height || row_count > height - row_begin) {
+            throw std::runtime_error("Bad argument: row band outside the frame");
+        }
+        if (row_count == 0) {
+            return;
+        }
+        CheckPlanes("offsets", offsets, "ids", ids, samples, "rgba", rgba);
+        const srt::Scene scene = srt::LoadScene(scene_path);
+        srt::HostResolve(scene, width, height, offsets, ids, samples, row_begin, row_count, rgba);
     });
 }
 

@@ -1,5 +1,6 @@
 """Scene files, the device-level render stages (include/srt_render.h), point queries
-(include/srt_query.h) and G-buffer outputs (include/srt_gbuffer.h).
+(include/srt_query.h), G-buffer outputs (include/srt_gbuffer.h) and multi-sample frames
+(include/srt_samples.h).
 
 ``DeviceScene`` keeps a scene resident on one GPU and launches the two stages on a caller's
 HIP stream with caller-owned device buffers (torch tensors or raw pointers):
@@ -9,6 +10,7 @@ HIP stream with caller-owned device buffers (torch tensors or raw pointers):
     scene.trace(offsets, rgba, row_begin, row_count, stream=s)   # closest hit + shade
     scene.query(positions, ids, t, stream=s)                     # closest hit at arbitrary image positions
     scene.gbuffer(offsets, ids, depth=d, normal=n, albedo=a)     # the surface under the hits (also attributes())
+    scene.render_samples(offsets_s, ids_s, rgba, stream=s)       # S samples per pixel, resolved (also resolve())
 
 This is the path bench.py times (inputs resident in HBM) and the one-process-per-GPU
 band renderer uses; ``runner.render`` is the host-image ml* path.
@@ -19,7 +21,7 @@ import ctypes
 import os
 
 from . import _native
-from ._native import (SRT_MAX_BATCH, SRT_SCENE_CORNELL, SRT_SCENE_SOUP, SRT_SCENE_TRIANGLE, SRT_TRACE_BVH,
+from ._native import (RTS_MAX_SAMPLES, SRT_MAX_BATCH, SRT_SCENE_CORNELL, SRT_SCENE_SOUP, SRT_SCENE_TRIANGLE, SRT_TRACE_BVH,
                       SRT_TRACE_CULL, SRT_TRACE_LDS, SRT_TRACE_SCALAR)
 
 SCENE_KINDS = {"triangle": SRT_SCENE_TRIANGLE, "cornell": SRT_SCENE_CORNELL, "soup": SRT_SCENE_SOUP}
@@ -134,6 +136,35 @@ def attributes_host(path: str, width: int, height: int, positions, ids):
     _check(_native.lib().rtgPointsHost(os.fsencode(path), width, height, pos.ctypes.data, idv.ctypes.data, count,
                                        ctypes.byref(out)))
     return depth, bary, normal, albedo
+
+
+def resolve_host(path: str, width: int, height: int, offsets, ids, row_begin: int = 0, row_count: int | None = None):
+    """The resolve of S sample planes on the host (rtsResolveHost: the library's canonical math, no
+    device): offsets, S arrays (rows, W, 2) float32, and ids, S arrays (rows, W) int32, of the band
+    rows [row_begin, row_begin + row_count) -> rgba (rows, W, 4) float32: the mean of the shaded
+    samples, alpha = the share that hit."""
+    import numpy as np
+
+    if row_count is None:
+        row_count = height - row_begin
+    if len(offsets) != len(ids):
+        raise ValueError(f"one ids plane per offsets plane, got {len(offsets)} and {len(ids)}")
+    samples = len(ids)
+    if not 1 <= samples <= RTS_MAX_SAMPLES:
+        raise ValueError(f"1 to {RTS_MAX_SAMPLES} sample planes, got {samples}")
+    off = [np.ascontiguousarray(o, np.float32) for o in offsets]
+    idv = [np.ascontiguousarray(i, np.int32) for i in ids]
+    for s in range(samples):
+        if off[s].shape != (row_count, width, 2):
+            raise ValueError(f"offsets[{s}] must be {(row_count, width, 2)}, got {off[s].shape}")
+        if idv[s].shape != (row_count, width):
+            raise ValueError(f"ids[{s}] must be {(row_count, width)}, got {idv[s].shape}")
+    rgba = np.empty((row_count, width, 4), np.float32)
+    arr = ctypes.c_void_p * samples
+    _check(_native.lib().rtsResolveHost(os.fsencode(path), width, height, arr(*[o.ctypes.data for o in off]),
+                                        arr(*[i.ctypes.data for i in idv]), samples, row_begin, row_count,
+                                        rgba.ctypes.data))
+    return rgba
 
 
 def tile_of(width: int, height: int, fx: float, fy: float):
@@ -375,6 +406,42 @@ class DeviceScene:
         out = self._outputs((("depth", depth, ()), ("bary", bary, (2,)), ("normal", normal, (4,)),
                              ("albedo", albedo, (4,))), (count,))
         _check(self._lib.rtgPointsAsync(self.handle, _ptr(positions), _ptr(ids), count, ctypes.byref(out),
+                                        _stream(stream)))
+
+    def _sample_planes(self, offsets, ids, rows):
+        """The pointer arrays of S sample planes: offsets[s] (rows, W, 2) float32 and ids[s]
+        (rows, W) int32, checked like trace_ids()'s."""
+        if len(offsets) != len(ids):
+            raise ValueError(f"one ids plane per offsets plane, got {len(offsets)} and {len(ids)}")
+        samples = len(ids)
+        if not 1 <= samples <= RTS_MAX_SAMPLES:
+            raise ValueError(f"1 to {RTS_MAX_SAMPLES} sample planes, got {samples}")
+        for s in range(samples):
+            self._check_buffer(f"offsets[{s}]", offsets[s], rows, 2, "f32")
+            self._check_buffer(f"ids[{s}]", ids[s], rows, 0, "i32")
+        arr = ctypes.c_void_p * samples
+        return arr(*[_ptr(o) for o in offsets]), arr(*[_ptr(i) for i in ids]), samples
+
+    def resolve(self, offsets, ids, rgba, row_begin: int = 0, row_count: int | None = None, stream=None):
+        """Resolve of the prepared frame's rows from S sample planes (include/srt_samples.h):
+        offsets, a sequence of S (rows, W, 2) float32 buffers, and ids, S (rows, W) int32 buffers
+        as trace_ids() stores them -> rgba (rows, W, 4) float32: the mean of the S shaded samples
+        (summed in order), alpha = the share of the samples that hit. Device buffers: tensors or
+        raw pointers."""
+        if row_count is None:
+            row_count = self.height - row_begin
+        offs, idp, samples = self._sample_planes(offsets, ids, row_count)
+        self._check_buffer("rgba", rgba, row_count, 4, "f32")
+        _check(self._lib.rtsResolveAsync(self.handle, offs, idp, samples, row_begin, row_count, _ptr(rgba),
+                                         _stream(stream)))
+
+    def render_samples(self, offsets, ids, rgba, variant: str = "cull", stream=None):
+        """S samples per pixel of the whole prepared frame (rtsRenderAsync): traces the S id planes
+        into ids[s] ((H, W) int32; they stay available) for offsets[s] ((H, W, 2) float32), then
+        resolves them into rgba (H, W, 4) as resolve() does."""
+        offs, idp, samples = self._sample_planes(offsets, ids, self.height)
+        self._check_buffer("rgba", rgba, self.height, 4, "f32")
+        _check(self._lib.rtsRenderAsync(self.handle, offs, idp, samples, _ptr(rgba), TRACE_VARIANTS[variant],
                                         _stream(stream)))
 
     def spatial_order(self):
