@@ -194,6 +194,14 @@ _SIGNATURES = {
     "rtsRenderAsync": (ctypes.c_int, [ctypes.c_void_p, _PVP, _PVP, _SZ, ctypes.c_void_p, ctypes.c_int,
                                       ctypes.c_void_p]),
     "rtsResolveHost": (ctypes.c_int, [ctypes.c_char_p, _SZ, _SZ, _PVP, _PVP, _SZ, _SZ, _SZ, ctypes.c_void_p]),
+    # include/srt_light.h: spot-light shadow masks (camera10: a ctypes float array, or None)
+    "rtlSceneCreate": (ctypes.c_void_p, [ctypes.c_char_p, ctypes.c_int, ctypes.POINTER(ctypes.c_float)]),
+    "rtlShadowAsync": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, _SZ, _SZ,
+                                      ctypes.c_float, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_float, ctypes.c_void_p]),
+    "rtlShadowHost": (ctypes.c_int, [ctypes.c_char_p, _SZ, _SZ, ctypes.POINTER(ctypes.c_float), _SZ, _SZ,
+                                     ctypes.c_void_p, ctypes.c_void_p, _SZ, _SZ, ctypes.c_float, ctypes.c_void_p,
+                                     ctypes.c_void_p, ctypes.c_float]),
+    "rtlProjectionHost": (ctypes.c_int, [ctypes.POINTER(ctypes.c_float), _SZ, _SZ, ctypes.POINTER(ctypes.c_float)]),
 }
 
 _lib = None

@@ -3,6 +3,7 @@
 #include "gbuffer_math.h"
 #include "samples_math.h"
 #include "screen_box.h"
+#include "shadow_math.h"
 
 #include <algorithm>
 #include <atomic>
@@ -296,6 +297,83 @@ void HostResolve(const Scene& scene, std::size_t width, std::size_t height, cons
         const ResolveTexel t = ResolveFinish(acc, static_cast<unsigned>(samples));
         const float v[4] = {t.r, t.g, t.b, t.a};
         std::copy(v, v + 4, rgba + 4 * i);
+    });
+}
+
+void HostShadowRows(const Camera& light_camera, std::size_t light_width, std::size_t light_height, float rows[9]) {
+    if (light_width == 0 || light_height == 0) {
+        throw std::runtime_error("Host shadow: light frame dimensions must be non-zero");
+    }
+    const Frame lf = MakeFrame(light_camera, light_width, light_height);
+    ShadowProjectionRows(lf.base, lf.du, lf.dv, rows);
+}
+
+void HostShadow(const Scene& scene, std::size_t width, std::size_t height, const Camera& light_camera,
+                std::size_t light_width, std::size_t light_height, const float* offsets, const int* ids,
+                std::size_t row_begin, std::size_t row_count, float bias, unsigned char* mask, float* rgba, float dim) {
+    if (width == 0 || height == 0 || light_width == 0 || light_height == 0) {
+        throw std::runtime_error("Host shadow: frame dimensions must be non-zero");
+    }
+    if (row_begin > height || row_count > height - row_begin) {
+        throw std::runtime_error("Host shadow: row band outside the frame");
+    }
+    const Frame f = MakeFrame(scene.camera, width, height);
+    const Frame lf = MakeFrame(light_camera, light_width, light_height);
+    float rows[9];
+    ShadowProjectionRows(lf.base, lf.du, lf.dv, rows);
+    const std::size_t n = scene.triangle_count();
+    std::vector<Rec> lrecs(n);  // every triangle's record under the light frame
+    ParallelFor(n, 1024, [&](std::size_t i) { lrecs[i] = MakeRecord(scene.vertices.data() + 9 * i, lf); });
+    const float wf = static_cast<float>(width), hf = static_cast<float>(height);
+    const float inf = std::numeric_limits<float>::infinity();
+    ParallelFor(row_count * width, 64, [&](std::size_t i) {
+        const std::size_t x = i % width, y = row_begin + i / width;
+        const int id = ids[i];
+        const float fx = (static_cast<float>(x) + offsets[2 * i]) / wf;
+        const float fy = (static_cast<float>(y) + offsets[2 * i + 1]) / hf;
+        const bool surface = id >= 0 && static_cast<std::size_t>(id) < n;
+        unsigned char cls = kShadowNoSurface;
+        float out[4] = {scene.background[0], scene.background[1], scene.background[2], -1.f};
+        if (surface) {
+            const Rec r = MakeRecord(scene.vertices.data() + 9 * static_cast<std::size_t>(id), f);
+            const float t = ShadowDepth(r.c, r.vol, fx, fy);
+            const ShadowPoint sp = ShadowProject(f.origin, f.base, f.du, f.dv, fx, fy, t, lf.origin, rows, bias);
+            cls = kShadowOutside;
+            if (sp.inside) {
+                float best = inf;
+                int lid = -1;
+                for (std::size_t k = 0; k < n; ++k) {  // ascending ids: strict < keeps the lowest on ties
+                    const float* c = lrecs[k].c;
+                    const float eA = std::fma(sp.gy, c[2], std::fma(sp.gx, c[1], c[0]));
+                    const float eB = std::fma(sp.gy, c[5], std::fma(sp.gx, c[4], c[3]));
+                    const float eC = std::fma(sp.gy, c[8], std::fma(sp.gx, c[7], c[6]));
+                    if (eA >= 0.f && eB >= 0.f && eC >= 0.f) {
+                        const float det = (eA + eB) + eC;
+                        if (det > 0.f) {
+                            const float tt = lrecs[k].vol / det;
+                            if (tt < best) {
+                                best = tt;
+                                lid = static_cast<int>(k);
+                            }
+                        }
+                    }
+                }
+                cls = ShadowClass(id, lid, best, sp.thr);
+            }
+            if (rgba != nullptr) {
+                const float* a = scene.albedo.data() + 3 * static_cast<std::size_t>(id);
+                const ResolveRgb c = ResolveShadeHit(f.base, f.du, f.dv, fx, fy, r.n[0], r.n[1], r.n[2], r.n[3], a[0], a[1], a[2]);
+                const float k = ShadowScale(cls, dim);
+                out[0] = c.r * k;
+                out[1] = c.g * k;
+                out[2] = c.b * k;
+                out[3] = static_cast<float>(id);
+            }
+        }
+        mask[i] = cls;
+        if (rgba != nullptr) {
+            std::copy(out, out + 4, rgba + 4 * i);
+        }
     });
 }
 

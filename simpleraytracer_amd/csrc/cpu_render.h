@@ -46,6 +46,17 @@ void HostGBuffer(const Scene& scene, std::size_t width, std::size_t height, cons
 void HostResolve(const Scene& scene, std::size_t width, std::size_t height, const float* const* offsets,
                  const int* const* ids, std::size_t samples, std::size_t row_begin, std::size_t row_count, float* rgba);
 
+// The spot-light shadow mask (shadow_math.h; the host answer of render.h LaunchShadow) of the band
+// rows [row_begin, row_begin + row_count) of the scene's width x height frame, the light being the
+// same triangles' light_width x light_height frame under light_camera: offsets (row_count x width x
+// 2) and ids (row_count x width), band-local, into mask (row_count x width classes) and -- non-null --
+// rgba (row_count x width x 4). The light frame's closest hit by brute force over every record.
+void HostShadow(const Scene& scene, std::size_t width, std::size_t height, const Camera& light_camera,
+                std::size_t light_width, std::size_t light_height, const float* offsets, const int* ids,
+                std::size_t row_begin, std::size_t row_count, float bias, unsigned char* mask, float* rgba, float dim);
+// The light frame's projection rows (px, py, pz) as HostShadow and LaunchShadow compute them.
+void HostShadowRows(const Camera& light_camera, std::size_t light_width, std::size_t light_height, float rows[9]);
+
 // Whether env ML_VISIBLE_DEVICES selects the CPU backend ("cpu", or set to the empty string).
 bool CpuBackendSelected();
 

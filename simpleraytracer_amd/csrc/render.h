@@ -356,6 +356,40 @@ hipError_t LaunchQuery(const CullSetup* setup, std::uint64_t n, const Frame& fra
                        std::size_t height, const float* d_svertices, const float* d_edges, const QueryArgs& args,
                        hipStream_t stream);
 
+// Spot-light shadow mask (render.hip ShadowKernel; shadow_math.h; DESIGN.md section 2 "Shadow"): the
+// class of every pixel of a band of the view frame -- 0 shadowed, 1 lit, 2 outside the light's
+// frustum, 3 no surface -- from its hit id, the light being a second prepared frame of a scene with
+// the same triangles: the canonical closest hit of the light frame at the position the pixel's
+// surface point projects to, compared with the pixel's own triangle and depth. Exact: bit for bit
+// the composition of the G-buffer's depth, shadow_math.h's projection and a point query.
+struct ShadowLight {
+    const CullSetup* setup;  // the light frame's built shared setup (read-only here), or null: pixels stream
+    Frame frame;             // the light's prepared frame, width x height
+    std::size_t width;
+    std::size_t height;
+    const float* svertices;  // the light scene's, as LaunchQuery's
+    const float* edges;
+    const unsigned* rank;    // the light scene's record id -> spatial-order position
+};
+struct ShadowArgs {
+    // Band-local, as LaunchShade's: pixel (x, row_begin + y) of the width x height view frame.
+    const float* offsets;  // device, row_count x width x 2
+    const int* ids;        // device, row_count x width
+    std::size_t width;
+    std::size_t height;
+    std::size_t row_begin;
+    std::size_t row_count;
+    float bias;            // relative depth bias, finite, >= 0
+    unsigned char* mask;   // device, row_count x width classes
+    float* rgba;           // device, row_count x width x 4, or null: the shaded pixel, rgb times
+    float dim;             //   1 (class 1) or dim (classes 0, 2); class 3: the background pixel
+};
+// d_vertices, d_shade, n, frame, background: the view scene's (n: of both scenes). One launch; no
+// rows: none.
+hipError_t LaunchShadow(const float* d_vertices, const float* d_shade, std::uint64_t n, const Frame& frame,
+                        const float background[3], const ShadowLight& light, const ShadowArgs& args,
+                        hipStream_t stream);
+
 // G-buffer (render.hip GBufferKernel): the surface attributes of (image position, triangle id)
 // pairs of the frame -- depth, barycentrics, normal + shading cosine, albedo + id (gbuffer_math.h;
 // DESIGN.md section 2 "Surface attributes") -- from hit ids, a deferred pass like LaunchShade with

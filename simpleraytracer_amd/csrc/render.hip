@@ -7,6 +7,7 @@
 #include "gbuffer_math.h"
 #include "samples_math.h"
 #include "screen_box.h"
+#include "shadow_math.h"
 #include "tile_lookup.h"
 
 #include <hip/hip_ext.h>
@@ -3496,6 +3497,185 @@ __global__ __launch_bounds__(kQueryThreads) void QueryKernel(const QueryParams q
 }
 
 // ---------------------------------------------------------------------------------------
+// Spot-light shadow mask (render.h LaunchShadow; DESIGN.md section 5 "Shadow"): the class of every
+// pixel of a band of the view frame -- shadowed, lit, outside the light's frustum, no surface
+// (shadow_math.h) -- from its hit id, with the light given as a second prepared frame: a point query
+// in the light's frame at the position the pixel's surface point projects to, fused with the
+// projection and stopped at the first occluder.
+// A group of kShadowLanes lanes per pixel, QueryKernel's mapping. Every lane of the group computes
+// the pixel's facts (its own loads are the group's: one address, one request): the depth of the hit
+// from the view scene's vertices (ComputeEdges, the traces' bits), the surface point and its
+// light-frame position (gx, gy), z and thr. Then the light's tile, and the exact test of the pixel's
+// OWN triangle under the light's records (position = the light scene's rank of the id): its t_id
+// there, +inf if it does not pass. The pixel is shadowed iff some record j != id passes the exact
+// test at (gx, gy) with t_j < thr and (t_j, j) < (t_id, id) -- ExactTestAnyOrder started from the
+// bound min((thr, lowest id), (t_id, id)) takes a candidate exactly then (the own triangle's entry in
+// the list ties with the bound and is not taken) -- so the lanes stride the tile's list and the
+// large list as the query does and the group leaves at the end of the first round in which a lane
+// took one: a ballot, so the exit is uniform for the group whatever the wave's other groups do.
+// No LDS, no atomics, no scratch. Lane 0 stores the class byte and, asked for, the shaded pixel
+// times the class's scale. Lanes x candidates per round, measured at C3 under two lights and two
+// light-frame sizes (64 ... 2 lanes, 1 / 2 / 4 candidates: DESIGN.md; profiles/shadow/): most pixels
+// of a frame carry no surface or leave after a round or two, so lanes beyond the first few idle --
+// 2 x 2 is the fastest or within 2 % of it on three of the four workloads (34 % ahead of 8 x 2 with
+// the light at the eye) and 15 % behind 16 x 2 on the fourth (512 x 512 light frame, long lists,
+// early exits). SRT_SHADOW_LANES, SRT_SHADOW_AHEAD: measurement builds.
+// ---------------------------------------------------------------------------------------
+#ifndef SRT_SHADOW_LANES
+#define SRT_SHADOW_LANES 2
+#endif
+constexpr int kShadowLanes = SRT_SHADOW_LANES;  // lanes per pixel (a divisor of the wave)
+#ifndef SRT_SHADOW_AHEAD
+#define SRT_SHADOW_AHEAD 2
+#endif
+constexpr int kShadowAhead = SRT_SHADOW_AHEAD;  // candidates per lane and round
+constexpr int kShadowThreads = 256;
+constexpr int kShadowBlock = kShadowThreads / kShadowLanes;  // pixels per block
+static_assert(kShadowLanes >= 2 && kWave % kShadowLanes == 0, "a pixel's lanes share a wave");
+struct ShadowParams {
+    TraceParams rec;  // the light: its records (TraceRecords), frame vectors, setup tiles, lists and counts
+    const unsigned* __restrict__ rank;   // the light scene's record id -> position
+    const float* __restrict__ vertices;  // the view scene's, by id
+    const float4* __restrict__ shade;    // the view scene's shading table
+    const float2* __restrict__ offsets;  // band-local
+    const int* __restrict__ ids;         // band-local
+    unsigned char* __restrict__ mask;
+    F4* __restrict__ rgba;  // null: not stored
+    unsigned n;             // triangles of either scene
+    unsigned width;
+    unsigned row_begin;
+    unsigned pixels;        // of the band
+    unsigned stream_end;    // records of a streamed pixel: positions [0, stream_end)
+    int tiles_y;
+    float wf, hf;           // the view frame's
+    float eye[3], base[3], du[3], dv[3], bg[3];
+    float rows[9];          // the light's projection rows (px, py, pz)
+    float light_origin[3];
+    float bias, dim;
+};
+
+// Whether a lane of the caller's group holds `mine` (the same value in every lane of the group).
+__device__ __forceinline__ bool ShadowGroupAny(bool mine) {
+    const unsigned long long b = __ballot(mine);
+    if constexpr (kShadowLanes == kWave) {
+        return b != 0ull;
+    } else {
+        const unsigned first = (threadIdx.x & (kWave - 1)) & ~static_cast<unsigned>(kShadowLanes - 1);
+        return ((b >> first) & ((1ull << kShadowLanes) - 1ull)) != 0ull;
+    }
+}
+
+template <bool RC>
+__global__ __launch_bounds__(kShadowThreads) void ShadowKernel(const ShadowParams q) {
+    const TraceParams& p = q.rec;
+    using Recs = TraceRecords<RC>;
+    const unsigned lane = threadIdx.x & (kShadowLanes - 1);
+    const unsigned pixel = blockIdx.x * kShadowBlock + threadIdx.x / kShadowLanes;
+    if (pixel >= q.pixels) {
+        return;
+    }
+    const int code = q.ids[pixel];
+    const float2 o = q.offsets[pixel];
+    const unsigned y = pixel / q.width, x = pixel - y * q.width;
+    const float fx = (static_cast<float>(x) + o.x) / q.wf;
+    const float fy = (static_cast<float>(q.row_begin + y) + o.y) / q.hf;
+    const bool surface = static_cast<unsigned>(code) < q.n;
+    unsigned char cls = kShadowNoSurface;
+    ShadowPoint sp{false, 0.f, 0.f, 0.f};
+    if (surface) {
+        const float* at = q.vertices + 9ull * static_cast<unsigned>(code);
+        float v[9], c[9], vol;
+#pragma unroll
+        for (int j = 0; j < 9; ++j) {
+            v[j] = at[j];
+        }
+        ComputeEdges(q.eye, q.base, q.du, q.dv, v, true, c, vol);
+        const float t = ShadowDepth(c, vol, fx, fy);
+        sp = ShadowProject(q.eye, q.base, q.du, q.dv, fx, fy, t, q.light_origin, q.rows, q.bias);
+        cls = kShadowOutside;
+    }
+    // The shaded pixel, before the scan: the view frame's vectors need not stay live across it.
+    F4 out{q.bg[0], q.bg[1], q.bg[2], -1.f};
+    if (q.rgba != nullptr && surface) {
+        const float4* sr = q.shade + 2ull * static_cast<unsigned>(code);
+        const float4 nr = sr[0], al = sr[1];
+        const ResolveRgb c = ResolveShadeHit(q.base, q.du, q.dv, fx, fy, nr.x, nr.y, nr.z, nr.w, al.x, al.y, al.z);
+        out = F4{c.r, c.g, c.b, static_cast<float>(code)};
+    }
+    if (sp.inside) {
+        Rays<1> s;
+        s.fx[0] = sp.gx;
+        s.fy[0] = sp.gy;
+        s.bt[0] = __builtin_inff();
+        s.bi[0] = -1;
+        int col = 0, row = 0;
+        bool listed = p.tile_info != nullptr &&
+                      TileOfPosition(sp.gx, sp.gy, p.wf, p.hf, kCullTileCols, kTileRows, p.tiles_x, q.tiles_y, col, row);
+        unsigned cnt = 0u, large = 0u;
+        const unsigned* list = nullptr;
+        if (listed) {
+            const unsigned tile = static_cast<unsigned>(row) * static_cast<unsigned>(p.tiles_x) + static_cast<unsigned>(col);
+            cnt = p.bin_counts[tile];
+            large = p.bin_counts[p.tiles];
+            list = p.bin_lists + static_cast<size_t>(tile) * p.bin_capacity;
+            listed = cnt <= p.bin_capacity && p.tile_info[tile].usable != 0u;
+        }
+        const unsigned total = listed ? cnt + large : q.stream_end;
+        auto entry = [&](unsigned k) {
+            if (!listed) {
+                return k;
+            }
+            const unsigned* at = k < cnt ? list + k : p.large_list + (k - cnt);
+            return *at;
+        };
+        auto test = [&](const typename Recs::Raw& raw) {
+            const CullRecord r = Recs::Make(p, raw);
+            const Record rec{r.a.x, r.a.y, r.a.z, r.a.w, r.b.x, r.b.y, r.b.z, r.b.w, r.x.x};
+            ExactTestAnyOrder<1, false>(s, rec, r.x.y, static_cast<int>(__float_as_uint(r.x.z)));
+        };
+        // The own triangle under the light's records: (t_id, id), or (+inf, -1) if it does not pass.
+        test(Recs::Load(p, q.rank[static_cast<unsigned>(code)]));
+        if (sp.thr <= s.bt[0]) {  // the bound: (thr, below every id) or (t_id, id), whichever is lower
+            s.bt[0] = sp.thr;
+            s.bi[0] = static_cast<int>(0x80000000u);
+        }
+        const int bound_id = s.bi[0];
+        bool occluded = false;
+        for (unsigned base = 0u; base < total; base += kShadowAhead * kShadowLanes) {
+            unsigned pos[kShadowAhead];
+            typename Recs::Raw raw[kShadowAhead];
+#pragma unroll
+            for (int a = 0; a < kShadowAhead; ++a) {
+                pos[a] = entry(min(base + a * kShadowLanes + lane, total - 1u));
+            }
+#pragma unroll
+            for (int a = 0; a < kShadowAhead; ++a) {
+                raw[a] = Recs::Load(p, pos[a]);
+            }
+#pragma unroll
+            for (int a = 0; a < kShadowAhead; ++a) {
+                test(raw[a]);
+            }
+            if (ShadowGroupAny(s.bi[0] != bound_id)) {  // a candidate below the bound: an occluder
+                occluded = true;
+                break;
+            }
+        }
+        cls = occluded ? kShadowShadowed : kShadowLit;
+    }
+    if (lane == 0u) {
+        q.mask[pixel] = cls;
+        if (q.rgba != nullptr) {
+            if (surface) {
+                const float k = ShadowScale(cls, q.dim);
+                out = F4{out.x * k, out.y * k, out.z * k, out.w};
+            }
+            StoreNontemporal(q.rgba + pixel, out);
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------------------
 // BVH variant: primary rays share the eye, so the closest-hit search
 // is a 2-D query over the records' screen boxes. The tree is implicit and 8 wide over the
 // cull records in the scene's spatial (Morton) order -- no sort, no topology arrays; only the
@@ -4540,20 +4720,11 @@ hipError_t LaunchSharedCullFrames(const CullFrame* frames, std::size_t count, co
     return hipGetLastError();
 }
 
-hipError_t LaunchQuery(const CullSetup* setup, std::uint64_t n, const Frame& frame, std::size_t width,
-                       std::size_t height, const float* d_svertices, const float* d_edges, const QueryArgs& args,
-                       hipStream_t stream) {
-    if (args.count == 0) {
-        return hipSuccess;
-    }
-    if (args.positions == nullptr || args.ids == nullptr || args.t == nullptr || d_svertices == nullptr ||
-        d_edges == nullptr || args.count > 0xFFFFFFFFull - kQueryBlock ||
-        (setup != nullptr && (width == 0 || height == 0 || !CullBinnable(width, height) ||
-                              setup->tiles != CullTiles(width, height)))) {
-        return hipErrorInvalidValue;
-    }
-    QueryParams q{};
-    TraceParams& p = q.rec;
+// The records a point query (or a shadow test) reads, as TraceParams: the setup's, or -- setup ==
+// null -- the scene's spatial inputs for TraceRecords<true>. Returns whether the records are
+// recomputed (the kernel's RC).
+static bool QueryRecords(TraceParams& p, int& tiles_y, const CullSetup* setup, std::uint64_t n, const Frame& frame,
+                         std::size_t width, std::size_t height, const float* d_svertices, const float* d_edges) {
     // Without a setup the records are recomputed from the scene's spatial inputs; TraceRecords<true>
     // also loads the position's screen box, which the exact test does not use: the scene's edge
     // allocation has room for one per padded record, so the address is valid whatever it holds.
@@ -4570,6 +4741,7 @@ hipError_t LaunchQuery(const CullSetup* setup, std::uint64_t n, const Frame& fra
         p.eye[k] = frame.origin[k];
     }
     bool recompute = true;
+    tiles_y = 0;
     if (setup != nullptr) {
         recompute = setup->recompute;
         p.tile_info = static_cast<const TileInfo*>(setup->tile_info);
@@ -4578,11 +4750,29 @@ hipError_t LaunchQuery(const CullSetup* setup, std::uint64_t n, const Frame& fra
         p.large_list = setup->large_list;
         p.bin_capacity = setup->capacity;
         p.tiles_x = static_cast<int>((width + kWave - 1) / kWave);
-        q.tiles_y = static_cast<int>((height + kTileRows - 1) / kTileRows);
+        tiles_y = static_cast<int>((height + kTileRows - 1) / kTileRows);
         p.tiles = static_cast<unsigned>(setup->tiles);
         p.wf = static_cast<float>(width);
         p.hf = static_cast<float>(height);
     }
+    return recompute;
+}
+
+hipError_t LaunchQuery(const CullSetup* setup, std::uint64_t n, const Frame& frame, std::size_t width,
+                       std::size_t height, const float* d_svertices, const float* d_edges, const QueryArgs& args,
+                       hipStream_t stream) {
+    if (args.count == 0) {
+        return hipSuccess;
+    }
+    if (args.positions == nullptr || args.ids == nullptr || args.t == nullptr || d_svertices == nullptr ||
+        d_edges == nullptr || args.count > 0xFFFFFFFFull - kQueryBlock ||
+        (setup != nullptr && (width == 0 || height == 0 || !CullBinnable(width, height) ||
+                              setup->tiles != CullTiles(width, height)))) {
+        return hipErrorInvalidValue;
+    }
+    QueryParams q{};
+    const bool recompute = QueryRecords(q.rec, q.tiles_y, setup, n, frame, width, height, d_svertices, d_edges);
+    const TraceParams& p = q.rec;
     q.positions = reinterpret_cast<const float2*>(args.positions);
     q.ids = args.ids;
     q.t = args.t;
@@ -4594,6 +4784,60 @@ hipError_t LaunchQuery(const CullSetup* setup, std::uint64_t n, const Frame& fra
         hipLaunchKernelGGL(QueryKernel<true>, grid, dim3(kQueryThreads), 0, stream, q);
     } else {
         hipLaunchKernelGGL(QueryKernel<false>, grid, dim3(kQueryThreads), 0, stream, q);
+    }
+    return hipGetLastError();
+}
+
+hipError_t LaunchShadow(const float* d_vertices, const float* d_shade, std::uint64_t n, const Frame& frame,
+                        const float background[3], const ShadowLight& light, const ShadowArgs& args,
+                        hipStream_t stream) {
+    if (args.width == 0 || args.row_count == 0) {
+        return hipSuccess;
+    }
+    const std::size_t pixels = args.width * args.row_count;
+    if (args.offsets == nullptr || args.ids == nullptr || args.mask == nullptr || d_shade == nullptr ||
+        (n != 0 && (d_vertices == nullptr || light.rank == nullptr)) || light.svertices == nullptr ||
+        light.edges == nullptr || n > 0x7FFFFFFFull || args.height == 0 || args.height > 0x7FFFFFFFull ||
+        args.row_begin > args.height || args.row_count > args.height - args.row_begin ||
+        args.width > 0xFFFFFFFFull || args.row_count > (0xFFFFFFFFull - kShadowBlock) / args.width ||
+        !(args.bias >= 0.f) || !std::isfinite(args.bias) || !std::isfinite(args.dim) ||
+        (light.setup != nullptr && (light.width == 0 || light.height == 0 || !CullBinnable(light.width, light.height) ||
+                                    light.setup->tiles != CullTiles(light.width, light.height)))) {
+        return hipErrorInvalidValue;
+    }
+    ShadowParams q{};
+    const bool recompute = QueryRecords(q.rec, q.tiles_y, light.setup, n, light.frame, light.width, light.height,
+                                        light.svertices, light.edges);
+    q.rank = light.rank;
+    q.vertices = d_vertices;
+    q.shade = reinterpret_cast<const float4*>(d_shade);
+    q.offsets = reinterpret_cast<const float2*>(args.offsets);
+    q.ids = args.ids;
+    q.mask = args.mask;
+    q.rgba = reinterpret_cast<F4*>(args.rgba);
+    q.n = static_cast<unsigned>(n);
+    q.width = static_cast<unsigned>(args.width);
+    q.row_begin = static_cast<unsigned>(args.row_begin);
+    q.pixels = static_cast<unsigned>(pixels);
+    q.stream_end = n == 0 ? 0u : q.rec.n_pad;
+    q.wf = static_cast<float>(args.width);
+    q.hf = static_cast<float>(args.height);
+    for (int k = 0; k < 3; ++k) {
+        q.eye[k] = frame.origin[k];
+        q.base[k] = frame.base[k];
+        q.du[k] = frame.du[k];
+        q.dv[k] = frame.dv[k];
+        q.bg[k] = background[k];
+        q.light_origin[k] = light.frame.origin[k];
+    }
+    ShadowProjectionRows(light.frame.base, light.frame.du, light.frame.dv, q.rows);
+    q.bias = args.bias;
+    q.dim = args.dim;
+    const dim3 grid(static_cast<unsigned>((pixels + kShadowBlock - 1) / kShadowBlock));
+    if (recompute) {
+        hipLaunchKernelGGL(ShadowKernel<true>, grid, dim3(kShadowThreads), 0, stream, q);
+    } else {
+        hipLaunchKernelGGL(ShadowKernel<false>, grid, dim3(kShadowThreads), 0, stream, q);
     }
     return hipGetLastError();
 }

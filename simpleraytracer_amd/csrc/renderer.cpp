@@ -837,18 +837,72 @@ void DeviceScene::Query(const float* d_positions, std::size_t count, int* d_ids,
         return;
     }
     OrderAfterPrevious(stream);
-    const bool shared = OnSharedSetup(0, m_height, 1) && CullBinningEnabled() && CullBinnable(m_width, m_height);
     CullSetup setup{};
+    const bool shared = QuerySetup(setup, stream);
+    const QueryArgs args{d_positions, count, d_ids, d_t, d_how};
+    HipCheck(LaunchQuery(shared ? &setup : nullptr, m_n, m_frame, m_width, m_height, m_svertices, m_edges, args, stream),
+             "query launch");
+    RecordOrder(stream);
+}
+
+bool DeviceScene::QuerySetup(CullSetup& setup, hipStream_t stream) const {
+    const bool shared = OnSharedSetup(0, m_height, 1) && CullBinningEnabled() && CullBinnable(m_width, m_height);
     if (shared) {
         // (a query reads no plan: a setup standing for another grid, a batch's, serves as it is)
         const bool standing = !m_setup_pending && m_setup_key.width == m_width && m_setup_key.height == m_height;
         setup = EnsureSetup(standing ? m_setup_key.descs : CullDescriptors(CullTiles(m_width, m_height), 1), stream);
         LogSetupStats();
     }
-    const QueryArgs args{d_positions, count, d_ids, d_t, d_how};
-    HipCheck(LaunchQuery(shared ? &setup : nullptr, m_n, m_frame, m_width, m_height, m_svertices, m_edges, args, stream),
-             "query launch");
+    return shared;
+}
+
+// The shadow mask of a band of this scene's prepared frame under `light`'s prepared frame (render.h
+// LaunchShadow). The launch reads both scenes' buffers, so it is ordered after the previous call
+// of either and both record it. The light's vertices are a second copy of this scene's (the scenes
+// are loaded separately).
+void DeviceScene::Shadow(const DeviceScene& light, const float* d_offsets, const int* d_ids, std::size_t row_begin,
+                         std::size_t row_count, float bias, unsigned char* d_mask, float* d_rgba, float dim,
+                         hipStream_t stream) const {
+    if (m_width == 0) {
+        throw std::runtime_error("Shadow: Prepare() has not been called on the view scene");
+    }
+    if (light.m_width == 0) {
+        throw std::runtime_error("Shadow: Prepare() has not been called on the light scene");
+    }
+    if (light.m_device != m_device) {
+        throw std::runtime_error("Shadow: the view scene lives on device " + std::to_string(m_device) +
+                                 ", the light scene on device " + std::to_string(light.m_device));
+    }
+    if (light.m_n != m_n) {
+        throw std::runtime_error("Shadow: the view scene has " + std::to_string(m_n) + " triangles, the light scene " +
+                                 std::to_string(light.m_n));
+    }
+    if (!(bias >= 0.f) || !std::isfinite(bias)) {
+        throw std::runtime_error("Shadow: bias must be finite and >= 0");
+    }
+    if (!std::isfinite(dim)) {
+        throw std::runtime_error("Shadow: dim must be finite");
+    }
+    if (row_begin > m_height || row_count > m_height - row_begin) {
+        throw std::runtime_error("Shadow: row band outside the frame");
+    }
+    if (row_count == 0) {
+        return;
+    }
+    OrderAfterPrevious(stream);
+    if (&light != this) {
+        light.OrderAfterPrevious(stream);
+    }
+    CullSetup setup{};
+    const bool shared = light.QuerySetup(setup, stream);
+    const ShadowLight sl{shared ? &setup : nullptr, light.m_frame, light.m_width, light.m_height,
+                         light.m_svertices, light.m_edges, light.m_rank};
+    const ShadowArgs args{d_offsets, d_ids, m_width, m_height, row_begin, row_count, bias, d_mask, d_rgba, dim};
+    HipCheck(LaunchShadow(m_vertices, m_shade, m_n, m_frame, m_background, sl, args, stream), "shadow launch");
     RecordOrder(stream);
+    if (&light != this) {
+        light.RecordOrder(stream);
+    }
 }
 
 DeviceScene::StageTimes DeviceScene::TakeTimes() {

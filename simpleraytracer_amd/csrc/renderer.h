@@ -113,6 +113,16 @@ public:
     void Query(const float* d_positions, std::size_t count, int* d_ids, float* d_t, unsigned char* d_how,
                hipStream_t stream) const;
 
+    // Spot-light shadow mask (render.h LaunchShadow) of the band rows [row_begin, row_begin +
+    // row_count) of this scene's prepared frame, the light being `light`'s prepared frame: d_offsets
+    // and d_ids band-local as Shade's, d_mask row_count x width class bytes, d_rgba (may be null)
+    // the shaded pixels dimmed by class. Both scenes are prepared, on one device, with the same
+    // number of triangles. Builds the light's shared setup if its prepared frame has none yet, as
+    // Query does; both scenes' calls are ordered against this one (OrderAfterPrevious / RecordOrder).
+    void Shadow(const DeviceScene& light, const float* d_offsets, const int* d_ids, std::size_t row_begin,
+                std::size_t row_count, float bias, unsigned char* d_mask, float* d_rgba, float dim,
+                hipStream_t stream) const;
+
     // G-buffer: the surface attributes (render.h GBufferArgs: depth, bary, normal, albedo; a null
     // plane is not written) of hit ids on the prepared frame. points: `count` positions d_where
     // (count x 2) with d_ids (count), row_begin unused. Else the band rows [row_begin, row_begin +
@@ -209,6 +219,9 @@ private:
                      hipStream_t stream, int id_planes, bool rgba_frame_rows, std::size_t plan_frames) const;
     // The setup for a trace grid of `descs` descriptors, (re)built on `stream` if need be.
     CullSetup EnsureSetup(unsigned descs, hipStream_t stream) const;
+    // The setup a point query of the prepared frame reads (Query, Shadow), (re)built on `stream` if
+    // need be; false: no usable setup (SRT_SETUP=frame, SRT_CULL_BIN=0, a shape that cannot be binned).
+    bool QuerySetup(CullSetup& setup, hipStream_t stream) const;
     Frame m_frame{};
     std::size_t m_width = 0;
     std::size_t m_height = 0;

@@ -2,6 +2,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cmath>
 #include <cstring>
 #include <exception>
 #include <string>
@@ -13,6 +14,7 @@
 #include "renderer.h"
 #include "scene.h"
 #include "srt_gbuffer.h"
+#include "srt_light.h"
 #include "srt_query.h"
 #include "srt_render.h"
 #include "srt_samples.h"
@@ -959,6 +961,142 @@ RTS_API int rtsResolveHost(const char* scene_path, size_t width, size_t height, 
         CheckPlanes("offsets", offsets, "ids", ids, samples, "rgba", rgba);
         const srt::Scene scene = srt::LoadScene(scene_path);
         srt::HostResolve(scene, width, height, offsets, ids, samples, row_begin, row_count, rgba);
+    });
+}
+
+// Spot-light shadow masks (include/srt_light.h): the rtl family.
+namespace {
+
+// camera10 = eye, lookat, up, vfov_deg, validated: what MakeFrame needs to give a finite frame.
+srt::Camera CheckedCamera(const float camera10[10]) {
+    for (int k = 0; k < 10; ++k) {
+        if (!std::isfinite(camera10[k])) {
+            throw std::runtime_error("Bad camera: value " + std::to_string(k) + " is not finite");
+        }
+    }
+    srt::Camera c{};
+    std::copy(camera10, camera10 + 3, c.eye);
+    std::copy(camera10 + 3, camera10 + 6, c.lookat);
+    std::copy(camera10 + 6, camera10 + 9, c.up);
+    c.vfov_deg = camera10[9];
+    if (!(c.vfov_deg > 0.f && c.vfov_deg < 180.f)) {
+        throw std::runtime_error("Bad camera: vfov must be in (0, 180) degrees");
+    }
+    double f[3];
+    for (int k = 0; k < 3; ++k) {
+        f[k] = static_cast<double>(c.lookat[k]) - static_cast<double>(c.eye[k]);
+    }
+    if (f[0] == 0.0 && f[1] == 0.0 && f[2] == 0.0) {
+        throw std::runtime_error("Bad camera: eye equals lookat");
+    }
+    const double r[3] = {f[1] * c.up[2] - f[2] * c.up[1], f[2] * c.up[0] - f[0] * c.up[2],
+                         f[0] * c.up[1] - f[1] * c.up[0]};
+    if (r[0] == 0.0 && r[1] == 0.0 && r[2] == 0.0) {
+        throw std::runtime_error("Bad camera: up is parallel to the view direction");
+    }
+    return c;
+}
+
+}  // namespace
+
+RTL_API srt_device_scene rtlSceneCreate(const char* path, int device, const float camera10[10]) {
+    srt::DeviceScene* out = nullptr;
+    Guarded([&] {
+        if (path == nullptr) {
+            throw std::runtime_error("Bad path argument");
+        }
+        srt::Scene scene = srt::LoadScene(path);
+        if (camera10 != nullptr) {
+            scene.camera = CheckedCamera(camera10);
+        }
+        int count = 0;
+        if (hipGetDeviceCount(&count) != hipSuccess || device < 0 || device >= count) {
+            throw std::runtime_error("HIP error: device " + std::to_string(device) + " not available (" +
+                                     std::to_string(count) + " present); the device stages have no CPU path");
+        }
+        out = new srt::DeviceScene(scene, device);
+    });
+    return reinterpret_cast<srt_device_scene>(out);
+}
+
+RTL_API int rtlShadowAsync(srt_device_scene view, srt_device_scene light, const float* d_offsets, const int* d_ids,
+                           size_t row_begin, size_t row_count, float bias, unsigned char* d_mask, float* d_rgba,
+                           float dim, void* stream) {
+    return Guarded([&] {
+        if (view == nullptr) {
+            throw std::runtime_error("Bad scene handle: view is NULL");
+        }
+        if (light == nullptr) {
+            throw std::runtime_error("Bad scene handle: light is NULL");
+        }
+        if (row_count != 0) {
+            if (d_offsets == nullptr) {
+                throw std::runtime_error("Bad buffer argument: d_offsets is NULL");
+            }
+            if (d_ids == nullptr) {
+                throw std::runtime_error("Bad buffer argument: d_ids is NULL");
+            }
+            if (d_mask == nullptr) {
+                throw std::runtime_error("Bad buffer argument: d_mask is NULL");
+            }
+        }
+        srt::DeviceScene* s = FromHandle(view);
+        Bind bind(s->device());
+        s->Shadow(*FromHandle(light), d_offsets, d_ids, row_begin, row_count, bias, d_mask, d_rgba, dim,
+                  static_cast<hipStream_t>(stream));
+    });
+}
+
+RTL_API int rtlShadowHost(const char* scene_path, size_t width, size_t height, const float light_camera10[10],
+                          size_t light_width, size_t light_height, const float* offsets, const int* ids,
+                          size_t row_begin, size_t row_count, float bias, unsigned char* mask, float* rgba, float dim) {
+    return Guarded([&] {
+        if (scene_path == nullptr) {
+            throw std::runtime_error("Bad argument: scene_path is NULL");
+        }
+        if (light_camera10 == nullptr) {
+            throw std::runtime_error("Bad argument: light_camera10 is NULL");
+        }
+        if (width == 0 || height == 0 || light_width == 0 || light_height == 0) {
+            throw std::runtime_error("Bad argument: frame dimensions must be non-zero");
+        }
+        const srt::Camera lc = CheckedCamera(light_camera10);
+        if (!(bias >= 0.f) || !std::isfinite(bias)) {
+            throw std::runtime_error("Shadow: bias must be finite and >= 0");
+        }
+        if (!std::isfinite(dim)) {
+            throw std::runtime_error("Shadow: dim must be finite");
+        }
+        if (row_begin > height || row_count > height - row_begin) {
+            throw std::runtime_error("Bad argument: row band outside the frame");
+        }
+        if (row_count == 0) {
+            return;
+        }
+        if (offsets == nullptr) {
+            throw std::runtime_error("Bad buffer argument: offsets is NULL");
+        }
+        if (ids == nullptr) {
+            throw std::runtime_error("Bad buffer argument: ids is NULL");
+        }
+        if (mask == nullptr) {
+            throw std::runtime_error("Bad buffer argument: mask is NULL");
+        }
+        const srt::Scene scene = srt::LoadScene(scene_path);
+        srt::HostShadow(scene, width, height, lc, light_width, light_height, offsets, ids, row_begin, row_count, bias,
+                        mask, rgba, dim);
+    });
+}
+
+RTL_API int rtlProjectionHost(const float camera10[10], size_t light_width, size_t light_height, float rows9[9]) {
+    return Guarded([&] {
+        if (camera10 == nullptr || rows9 == nullptr) {
+            throw std::runtime_error("Bad argument");
+        }
+        if (light_width == 0 || light_height == 0) {
+            throw std::runtime_error("Bad argument: frame dimensions must be non-zero");
+        }
+        srt::HostShadowRows(CheckedCamera(camera10), light_width, light_height, rows9);
     });
 }
 

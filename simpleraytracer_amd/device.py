@@ -1,6 +1,6 @@
 """Scene files, the device-level render stages (include/srt_render.h), point queries
-(include/srt_query.h), G-buffer outputs (include/srt_gbuffer.h) and multi-sample frames
-(include/srt_samples.h).
+(include/srt_query.h), G-buffer outputs (include/srt_gbuffer.h), multi-sample frames
+(include/srt_samples.h) and spot-light shadow masks (include/srt_light.h).
 
 ``DeviceScene`` keeps a scene resident on one GPU and launches the two stages on a caller's
 HIP stream with caller-owned device buffers (torch tensors or raw pointers):
@@ -11,6 +11,7 @@ HIP stream with caller-owned device buffers (torch tensors or raw pointers):
     scene.query(positions, ids, t, stream=s)                     # closest hit at arbitrary image positions
     scene.gbuffer(offsets, ids, depth=d, normal=n, albedo=a)     # the surface under the hits (also attributes())
     scene.render_samples(offsets_s, ids_s, rgba, stream=s)       # S samples per pixel, resolved (also resolve())
+    scene.shadow(light, offsets, ids, mask, rgba, stream=s)      # which pixels a spot light (a second scene) reaches
 
 This is the path bench.py times (inputs resident in HBM) and the one-process-per-GPU
 band renderer uses; ``runner.render`` is the host-image ml* path.
@@ -167,6 +168,50 @@ def resolve_host(path: str, width: int, height: int, offsets, ids, row_begin: in
     return rgba
 
 
+def _camera10(camera):
+    """camera (10 floats: eye, lookat, up, vfov_deg) as the C array the rtl calls take."""
+    vals = [float(v) for v in camera]
+    if len(vals) != 10:
+        raise ValueError(f"camera must be 10 floats (eye, lookat, up, vfov_deg), got {len(vals)}")
+    return (ctypes.c_float * 10)(*vals)
+
+
+def light_projection(camera, light_width: int, light_height: int):
+    """The projection rows (px, py, pz) of a light camera at its resolution (rtlProjectionHost):
+    (3, 3) float32. A world point X lies at light-frame position (px.q / pz.q, py.q / pz.q),
+    q = X - eye, at planar depth pz.q."""
+    import numpy as np
+
+    rows = (ctypes.c_float * 9)()
+    _check(_native.lib().rtlProjectionHost(_camera10(camera), light_width, light_height, rows))
+    return np.array(list(rows), np.float32).reshape(3, 3)
+
+
+def shadow_host(path: str, width: int, height: int, light_camera, light_width: int, light_height: int, offsets, ids,
+                bias: float = 0.0, dim: float = 0.0, row_begin: int = 0, row_count: int | None = None):
+    """The shadow mask on the host (rtlShadowHost: brute force, the library's canonical math, no
+    device): the band rows of path's width x height frame under the light camera's light_width x
+    light_height frame, offsets (rows, W, 2) float32 and ids (rows, W) int32 -> (mask (rows, W)
+    uint8 of classes 0 shadowed / 1 lit / 2 outside the light's frustum / 3 no surface, rgba
+    (rows, W, 4) float32: the shaded pixel, rgb times 1 (class 1) or dim (classes 0 and 2))."""
+    import numpy as np
+
+    if row_count is None:
+        row_count = height - row_begin
+    off = np.ascontiguousarray(offsets, np.float32)
+    idv = np.ascontiguousarray(ids, np.int32)
+    if off.shape != (row_count, width, 2):
+        raise ValueError(f"offsets must be {(row_count, width, 2)}, got {off.shape}")
+    if idv.shape != (row_count, width):
+        raise ValueError(f"ids must be {(row_count, width)}, got {idv.shape}")
+    mask = np.empty((row_count, width), np.uint8)
+    rgba = np.empty((row_count, width, 4), np.float32)
+    _check(_native.lib().rtlShadowHost(os.fsencode(path), width, height, _camera10(light_camera), light_width,
+                                       light_height, off.ctypes.data, idv.ctypes.data, row_begin, row_count, bias,
+                                       mask.ctypes.data, rgba.ctypes.data, dim))
+    return mask, rgba
+
+
 def tile_of(width: int, height: int, fx: float, fy: float):
     """The cull tile (col, row) the query kernel looks a position up in (rtqTileHost), or None
     when the position is not in [0, 1]^2."""
@@ -197,9 +242,15 @@ def _stream(s) -> int:
 class DeviceScene:
     """A scene resident on one HIP device."""
 
-    def __init__(self, path: str, device: int = 0):
+    def __init__(self, path: str, device: int = 0, camera=None):
+        """camera: 10 floats (eye, lookat, up, vfov_deg) replacing the file's camera (rtlSceneCreate),
+        a spot light's for instance; None keeps the file's."""
         self._lib = _native.lib()
-        self.handle = self._lib.srtDeviceSceneCreate(os.fsencode(path), device)
+        self.handle = None
+        if camera is None:
+            self.handle = self._lib.srtDeviceSceneCreate(os.fsencode(path), device)
+        else:
+            self.handle = self._lib.rtlSceneCreate(os.fsencode(path), device, _camera10(camera))
         if not self.handle:
             raise SrtError(_native.last_error())
         self.device = device
@@ -407,6 +458,24 @@ class DeviceScene:
                              ("albedo", albedo, (4,))), (count,))
         _check(self._lib.rtgPointsAsync(self.handle, _ptr(positions), _ptr(ids), count, ctypes.byref(out),
                                         _stream(stream)))
+
+    def shadow(self, light, offsets, ids, mask, rgba=None, bias: float = 0.0, dim: float = 0.0, row_begin: int = 0,
+               row_count: int | None = None, stream=None):
+        """Spot-light shadow mask of the prepared frame's rows (include/srt_light.h): `light` is a
+        prepared DeviceScene of the same triangles under the light's camera (DeviceScene(path,
+        device, camera=...)). offsets (rows, W, 2) float32 and ids (rows, W) int32 as trace_ids()
+        stores them -> mask (rows, W) uint8: 0 shadowed, 1 lit, 2 outside the light's frustum, 3 no
+        surface; rgba (rows, W, 4) float32, optional: shade()'s pixel, rgb times 1 (class 1) or dim
+        (classes 0 and 2). bias: relative depth bias >= 0. Device buffers, checked like trace()'s."""
+        if row_count is None:
+            row_count = self.height - row_begin
+        self._check_buffer("offsets", offsets, row_count, 2, "f32")
+        self._check_buffer("ids", ids, row_count, 0, "i32")
+        self._check_buffer("mask", mask, row_count, 0, "u8")
+        if rgba is not None:
+            self._check_buffer("rgba", rgba, row_count, 4, "f32")
+        _check(self._lib.rtlShadowAsync(self.handle, light.handle, _ptr(offsets), _ptr(ids), row_begin, row_count, bias,
+                                        _ptr(mask), _ptr(rgba), dim, _stream(stream)))
 
     def _sample_planes(self, offsets, ids, rows):
         """The pointer arrays of S sample planes: offsets[s] (rows, W, 2) float32 and ids[s]
