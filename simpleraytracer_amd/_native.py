@@ -42,6 +42,7 @@ SRT_SPLIT_FRAMES = 1
 SRT_ENGINE_RCCL_SELF = 1  # srt_engine_options.flags
 SRT_TILE_ROWS = 16  # include/srt_render.h: rows per tile row (interleaved bands deal these)
 RTS_MAX_SAMPLES = 16  # include/srt_samples.h: sample planes per rtsResolveAsync / rtsRenderAsync call
+RTK_MAX_LAYERS = 8  # include/srt_layers.h: layers per rtkLayersAsync / rtkFrameAsync / rtkCompositeAsync call
 
 
 class ImageInfo(ctypes.Structure):
@@ -202,6 +203,17 @@ _SIGNATURES = {
                                      ctypes.c_void_p, ctypes.c_void_p, _SZ, _SZ, ctypes.c_float, ctypes.c_void_p,
                                      ctypes.c_void_p, ctypes.c_float]),
     "rtlProjectionHost": (ctypes.c_int, [ctypes.POINTER(ctypes.c_float), _SZ, _SZ, ctypes.POINTER(ctypes.c_float)]),
+    # include/srt_layers.h: depth layers and their over-composite
+    "rtkLayersAsync": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, _SZ, _SZ, ctypes.c_void_p, ctypes.c_void_p,
+                                      ctypes.c_void_p, ctypes.c_void_p]),
+    "rtkFrameAsync": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, _SZ, _SZ, _SZ, ctypes.c_void_p, ctypes.c_void_p,
+                                     ctypes.c_void_p, ctypes.c_void_p]),
+    "rtkCompositeAsync": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, _SZ, ctypes.c_void_p, _SZ, _SZ,
+                                         ctypes.c_void_p, ctypes.c_void_p]),
+    "rtkLayersHost": (ctypes.c_int, [ctypes.c_char_p, _SZ, _SZ, ctypes.c_void_p, _SZ, _SZ, ctypes.c_void_p,
+                                     ctypes.c_void_p]),
+    "rtkCompositeHost": (ctypes.c_int, [ctypes.c_char_p, _SZ, _SZ, ctypes.c_void_p, ctypes.c_void_p, _SZ, ctypes.c_void_p,
+                                        _SZ, _SZ, ctypes.c_void_p]),
 }
 
 _lib = None

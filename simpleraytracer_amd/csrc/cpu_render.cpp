@@ -1,6 +1,7 @@
 #include "cpu_render.h"
 
 #include "gbuffer_math.h"
+#include "layers_math.h"
 #include "samples_math.h"
 #include "screen_box.h"
 #include "shadow_math.h"
@@ -296,6 +297,92 @@ void HostResolve(const Scene& scene, std::size_t width, std::size_t height, cons
         }
         const ResolveTexel t = ResolveFinish(acc, static_cast<unsigned>(samples));
         const float v[4] = {t.r, t.g, t.b, t.a};
+        std::copy(v, v + 4, rgba + 4 * i);
+    });
+}
+
+void HostLayers(const Scene& scene, std::size_t width, std::size_t height, const float* positions, std::size_t count,
+                std::size_t layers, int* ids, float* t) {
+    if (width == 0 || height == 0) {
+        throw std::runtime_error("Host layers: frame dimensions must be non-zero");
+    }
+    if (layers == 0) {
+        throw std::runtime_error("Host layers: layers must be positive");
+    }
+    const Frame f = MakeFrame(scene.camera, width, height);
+    const std::size_t n = scene.triangle_count();
+    std::vector<Rec> recs(n);
+    ParallelFor(n, 1024, [&](std::size_t i) { recs[i] = MakeRecord(scene.vertices.data() + 9 * i, f); });
+    const float inf = std::numeric_limits<float>::infinity();
+    ParallelFor(count, 64, [&](std::size_t q) {
+        const float px = positions[2 * q], py = positions[2 * q + 1];
+        // The `layers` smallest (t, id) so far, ascending; ids ascend, so a later record goes behind
+        // every held one of equal t (strict <).
+        std::vector<float> bt(layers, inf);
+        std::vector<int> bi(layers, -1);
+        for (std::size_t k = 0; k < n; ++k) {
+            const float* c = recs[k].c;
+            const float eA = std::fma(py, c[2], std::fma(px, c[1], c[0]));
+            const float eB = std::fma(py, c[5], std::fma(px, c[4], c[3]));
+            const float eC = std::fma(py, c[8], std::fma(px, c[7], c[6]));
+            if (eA >= 0.f && eB >= 0.f && eC >= 0.f) {
+                const float det = (eA + eB) + eC;
+                if (det > 0.f) {
+                    const float tt = recs[k].vol / det;
+                    if (tt < bt[layers - 1]) {
+                        std::size_t j = layers - 1;
+                        for (; j > 0 && tt < bt[j - 1]; --j) {
+                            bt[j] = bt[j - 1];
+                            bi[j] = bi[j - 1];
+                        }
+                        bt[j] = tt;
+                        bi[j] = static_cast<int>(k);
+                    }
+                }
+            }
+        }
+        for (std::size_t k = 0; k < layers; ++k) {
+            ids[k * count + q] = bi[k];
+            if (t != nullptr) {
+                t[k * count + q] = bt[k];
+            }
+        }
+    });
+}
+
+void HostComposite(const Scene& scene, std::size_t width, std::size_t height, const float* offsets, const int* ids,
+                   std::size_t layers, const float* opacity, std::size_t row_begin, std::size_t row_count,
+                   float* rgba) {
+    if (width == 0 || height == 0) {
+        throw std::runtime_error("Host composite: frame dimensions must be non-zero");
+    }
+    if (layers == 0) {
+        throw std::runtime_error("Host composite: layers must be positive");
+    }
+    if (row_begin > height || row_count > height - row_begin) {
+        throw std::runtime_error("Host composite: row band outside the frame");
+    }
+    const Frame f = MakeFrame(scene.camera, width, height);
+    const std::size_t n = scene.triangle_count();
+    const float wf = static_cast<float>(width), hf = static_cast<float>(height);
+    const std::size_t plane = row_count * width;
+    ParallelFor(plane, 1024, [&](std::size_t i) {
+        const unsigned x = static_cast<unsigned>(i % width), y = static_cast<unsigned>(row_begin + i / width);
+        float fx, fy;
+        ResolvePosition(x, y, offsets[2 * i], offsets[2 * i + 1], wf, hf, fx, fy);
+        CompositeAcc acc = CompositeStart();
+        for (std::size_t k = 0; k < layers; ++k) {
+            const int id = ids[k * plane + i];
+            if (id < 0 || static_cast<std::size_t>(id) >= n) {
+                break;
+            }
+            const Rec r = MakeRecord(scene.vertices.data() + 9 * static_cast<std::size_t>(id), f);
+            const float* a = scene.albedo.data() + 3 * static_cast<std::size_t>(id);
+            const ResolveRgb c = ResolveShadeHit(f.base, f.du, f.dv, fx, fy, r.n[0], r.n[1], r.n[2], r.n[3], a[0], a[1], a[2]);
+            CompositeAdd(acc, opacity[id], c);
+        }
+        const ResolveTexel o = CompositeFinish(acc, scene.background);
+        const float v[4] = {o.r, o.g, o.b, o.a};
         std::copy(v, v + 4, rgba + 4 * i);
     });
 }

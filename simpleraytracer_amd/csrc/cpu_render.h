@@ -46,6 +46,21 @@ void HostGBuffer(const Scene& scene, std::size_t width, std::size_t height, cons
 void HostResolve(const Scene& scene, std::size_t width, std::size_t height, const float* const* offsets,
                  const int* const* ids, std::size_t samples, std::size_t row_begin, std::size_t row_count, float* rgba);
 
+// The `layers` nearest hits, front to back, at `count` image positions of the scene's width x
+// height frame, brute force over every record with the canonical math (the host answer of render.h
+// LaunchLayers): ids[k * count + i] = layer k's triangle or -1, t[...] (null: not stored) = its t or
+// +inf -- the k-th smallest (t, id) among the triangles passing the exact test.
+void HostLayers(const Scene& scene, std::size_t width, std::size_t height, const float* positions, std::size_t count,
+                std::size_t layers, int* ids, float* t);
+
+// The over-composite (layers_math.h; the host answer of render.h LaunchComposite) of `layers` id
+// planes (ids: layers x row_count x width) of the band rows [row_begin, row_begin + row_count) of
+// the scene's width x height frame under the opacity table (one float per triangle): offsets
+// (row_count x width x 2), band-local, into rgba (row_count x width x 4).
+void HostComposite(const Scene& scene, std::size_t width, std::size_t height, const float* offsets, const int* ids,
+                   std::size_t layers, const float* opacity, std::size_t row_begin, std::size_t row_count,
+                   float* rgba);
+
 // The spot-light shadow mask (shadow_math.h; the host answer of render.h LaunchShadow) of the band
 // rows [row_begin, row_begin + row_count) of the scene's width x height frame, the light being the
 // same triangles' light_width x light_height frame under light_camera: offsets (row_count x width x

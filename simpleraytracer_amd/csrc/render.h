@@ -356,6 +356,51 @@ hipError_t LaunchQuery(const CullSetup* setup, std::uint64_t n, const Frame& fra
                        std::size_t height, const float* d_svertices, const float* d_edges, const QueryArgs& args,
                        hipStream_t stream);
 
+// Depth layers (render.hip LayersKernel; DESIGN.md section 2 "Layers"): at every position the
+// `layers` (1 .. kMaxLayers) lexicographically smallest (t, id) keys among the records passing the
+// exact test, front to back: ids[k * E + i] = layer k's id at element i of E, or -1, t[...] = its t
+// or +inf (t null: not stored). Layer 0 is LaunchQuery's answer. how[i] as QueryArgs::how.
+constexpr int kMaxLayers = 8;
+struct LayersArgs {
+    // points: `where` = count x 2 positions, E = count (row_begin, row_count unused). Else `where` =
+    // the band's sample offsets, row_count x width x 2, element (x, y) is pixel (x, row_begin + y) of
+    // the frame at ray generation's position, E = row_count x width (band-local, as LaunchShade's).
+    bool points;
+    const float* where;  // device
+    std::size_t count;
+    std::size_t row_begin;
+    std::size_t row_count;
+    std::size_t layers;
+    int* ids;            // device, layers x E
+    float* t;            // device, layers x E, or null
+    unsigned char* how;  // device, E, or null
+};
+// `setup`, d_svertices, d_edges: as LaunchQuery's. One launch; no elements: none.
+hipError_t LaunchLayers(const CullSetup* setup, std::uint64_t n, const Frame& frame, std::size_t width,
+                        std::size_t height, const float* d_svertices, const float* d_edges, const LayersArgs& args,
+                        hipStream_t stream);
+
+// Composite (render.hip CompositeKernel; layers_math.h; DESIGN.md section 2 "Composite"): one RGBA
+// pixel from `layers` id planes of a band -- each layer shaded as LaunchShade shades it and
+// composited front to back under the per-triangle opacity table; alpha = 1 - the transmittance
+// left. Reads the shading table and the opacity table only. The composite of a pixel stops at its
+// first id outside [0, n); nothing is read through such an id.
+struct CompositeArgs {
+    // Band-local, as LaunchShade's: pixel (x, row_begin + y) of the width x height frame.
+    const float* offsets;  // device, row_count x width x 2
+    const int* ids;        // device, layers x row_count x width, layer-major (LaunchLayers' ids)
+    std::size_t layers;
+    const float* opacity;  // device, n
+    std::size_t width;
+    std::size_t height;
+    std::size_t row_begin;
+    std::size_t row_count;
+    float* rgba;  // device, row_count x width x 4
+};
+// One launch; no rows: none.
+hipError_t LaunchComposite(const float* d_shade, std::uint64_t n, const Frame& frame, const float background[3],
+                           const CompositeArgs& args, hipStream_t stream);
+
 // Spot-light shadow mask (render.hip ShadowKernel; shadow_math.h; DESIGN.md section 2 "Shadow"): the
 // class of every pixel of a band of the view frame -- 0 shadowed, 1 lit, 2 outside the light's
 // frustum, 3 no surface -- from its hit id, the light being a second prepared frame of a scene with

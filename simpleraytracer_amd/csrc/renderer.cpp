@@ -845,6 +845,55 @@ void DeviceScene::Query(const float* d_positions, std::size_t count, int* d_ids,
     RecordOrder(stream);
 }
 
+// Depth layers on the prepared frame (render.h LaunchLayers): Query keeping K hits. The setup is
+// Query's, shared with it, Shadow and a one-frame whole-frame trace.
+void DeviceScene::Layers(bool points, const float* d_where, std::size_t row_begin, std::size_t count,
+                         std::size_t layers, int* d_ids, float* d_t, unsigned char* d_how, hipStream_t stream) const {
+    if (m_width == 0) {
+        throw std::runtime_error("Layers: Prepare() has not been called");
+    }
+    if (layers == 0 || layers > static_cast<std::size_t>(kMaxLayers)) {
+        throw std::runtime_error("Layers: layers must be 1 to " + std::to_string(kMaxLayers) + ", got " +
+                                 std::to_string(layers));
+    }
+    if (!points && (row_begin > m_height || count > m_height - row_begin)) {
+        throw std::runtime_error("Layers: row band outside the frame");
+    }
+    if (count == 0) {
+        return;
+    }
+    OrderAfterPrevious(stream);
+    CullSetup setup{};
+    const bool shared = QuerySetup(setup, stream);
+    const LayersArgs args{points, d_where, points ? count : 0, points ? 0 : row_begin, points ? 0 : count, layers,
+                          d_ids,  d_t,     d_how};
+    HipCheck(LaunchLayers(shared ? &setup : nullptr, m_n, m_frame, m_width, m_height, m_svertices, m_edges, args, stream),
+             "layers launch");
+    RecordOrder(stream);
+}
+
+void DeviceScene::Composite(const float* d_offsets, const int* d_ids, std::size_t layers, const float* d_opacity,
+                            std::size_t row_begin, std::size_t row_count, float* d_rgba, hipStream_t stream) const {
+    if (m_width == 0) {
+        throw std::runtime_error("Composite: Prepare() has not been called");
+    }
+    if (layers == 0 || layers > static_cast<std::size_t>(kMaxLayers)) {
+        throw std::runtime_error("Composite: layers must be 1 to " + std::to_string(kMaxLayers) + ", got " +
+                                 std::to_string(layers));
+    }
+    if (row_begin > m_height || row_count > m_height - row_begin) {
+        throw std::runtime_error("Composite: row band outside the frame");
+    }
+    if (row_count == 0) {
+        return;
+    }
+    OrderAfterPrevious(stream);
+    const CompositeArgs args{d_offsets, d_ids, layers, d_opacity, m_width, m_height, row_begin, row_count, d_rgba};
+    HipCheck(LaunchComposite(m_shade, m_n, m_frame, m_background, args, stream), "composite launch");
+    LogSetupStats();  // (the counters as they stand: this call builds nothing)
+    RecordOrder(stream);
+}
+
 bool DeviceScene::QuerySetup(CullSetup& setup, hipStream_t stream) const {
     const bool shared = OnSharedSetup(0, m_height, 1) && CullBinningEnabled() && CullBinnable(m_width, m_height);
     if (shared) {

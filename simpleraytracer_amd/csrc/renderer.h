@@ -113,6 +113,19 @@ public:
     void Query(const float* d_positions, std::size_t count, int* d_ids, float* d_t, unsigned char* d_how,
                hipStream_t stream) const;
 
+    // Depth layers (render.h LaunchLayers): the `layers` (1 .. kMaxLayers) nearest hits, front to
+    // back, at `count` image positions (points: d_where = count x 2 positions, row_begin unused) or
+    // at the pixels of the band rows [row_begin, row_begin + count) (d_where = the band's sample
+    // offsets, band-local as Shade's) into d_ids (layers x elements, layer-major), d_t (the same
+    // shape, may be null) and d_how (elements, may be null). The shared setup is Query's.
+    void Layers(bool points, const float* d_where, std::size_t row_begin, std::size_t count, std::size_t layers,
+                int* d_ids, float* d_t, unsigned char* d_how, hipStream_t stream) const;
+    // Composite (render.h LaunchComposite): the band rows [row_begin, row_begin + row_count) from
+    // `layers` id planes (d_ids: layers x row_count x width) under the opacity table d_opacity (one
+    // float per triangle) into d_rgba. Reads the shading table only: no cull setup is built or read.
+    void Composite(const float* d_offsets, const int* d_ids, std::size_t layers, const float* d_opacity,
+                   std::size_t row_begin, std::size_t row_count, float* d_rgba, hipStream_t stream) const;
+
     // Spot-light shadow mask (render.h LaunchShadow) of the band rows [row_begin, row_begin +
     // row_count) of this scene's prepared frame, the light being `light`'s prepared frame: d_offsets
     // and d_ids band-local as Shade's, d_mask row_count x width class bytes, d_rgba (may be null)

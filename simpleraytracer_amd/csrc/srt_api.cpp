@@ -14,6 +14,7 @@
 #include "renderer.h"
 #include "scene.h"
 #include "srt_gbuffer.h"
+#include "srt_layers.h"
 #include "srt_light.h"
 #include "srt_query.h"
 #include "srt_render.h"
@@ -961,6 +962,124 @@ RTS_API int rtsResolveHost(const char* scene_path, size_t width, size_t height, 
         CheckPlanes("offsets", offsets, "ids", ids, samples, "rgba", rgba);
         const srt::Scene scene = srt::LoadScene(scene_path);
         srt::HostResolve(scene, width, height, offsets, ids, samples, row_begin, row_count, rgba);
+    });
+}
+
+// Depth layers (include/srt_layers.h): the rtk family.
+static_assert(RTK_MAX_LAYERS == srt::kMaxLayers, "include/srt_layers.h RTK_MAX_LAYERS");
+
+namespace {
+
+void CheckLayers(size_t layers) {
+    if (layers == 0 || layers > RTK_MAX_LAYERS) {
+        throw std::runtime_error("Bad argument: layers must be 1 to " + std::to_string(RTK_MAX_LAYERS) + ", got " +
+                                 std::to_string(layers));
+    }
+}
+
+void CheckBuffer(const char* name, const void* p) {
+    if (p == nullptr) {
+        throw std::runtime_error(std::string("Bad buffer argument: ") + name + " is NULL");
+    }
+}
+
+}  // namespace
+
+RTK_API int rtkLayersAsync(srt_device_scene scene, const float* d_positions, size_t count, size_t layers, int* d_ids,
+                           float* d_t, unsigned char* d_how, void* stream) {
+    return Guarded([&] {
+        if (scene == nullptr) {
+            throw std::runtime_error("Bad scene handle");
+        }
+        CheckLayers(layers);
+        if (count != 0) {
+            CheckBuffer("d_positions", d_positions);
+            CheckBuffer("d_ids", d_ids);
+        }
+        srt::DeviceScene* s = FromHandle(scene);
+        Bind bind(s->device());
+        s->Layers(true, d_positions, 0, count, layers, d_ids, d_t, d_how, static_cast<hipStream_t>(stream));
+    });
+}
+
+RTK_API int rtkFrameAsync(srt_device_scene scene, const float* d_offsets, size_t row_begin, size_t row_count,
+                          size_t layers, int* d_ids, float* d_t, unsigned char* d_how, void* stream) {
+    return Guarded([&] {
+        if (scene == nullptr) {
+            throw std::runtime_error("Bad scene handle");
+        }
+        CheckLayers(layers);
+        if (row_count != 0) {
+            CheckBuffer("d_offsets", d_offsets);
+            CheckBuffer("d_ids", d_ids);
+        }
+        srt::DeviceScene* s = FromHandle(scene);
+        Bind bind(s->device());
+        s->Layers(false, d_offsets, row_begin, row_count, layers, d_ids, d_t, d_how, static_cast<hipStream_t>(stream));
+    });
+}
+
+RTK_API int rtkCompositeAsync(srt_device_scene scene, const float* d_offsets, const int* d_ids, size_t layers,
+                              const float* d_opacity, size_t row_begin, size_t row_count, float* d_rgba, void* stream) {
+    return Guarded([&] {
+        if (scene == nullptr) {
+            throw std::runtime_error("Bad scene handle");
+        }
+        CheckLayers(layers);
+        if (row_count != 0) {
+            CheckBuffer("d_offsets", d_offsets);
+            CheckBuffer("d_ids", d_ids);
+            CheckBuffer("d_opacity", d_opacity);
+            CheckBuffer("d_rgba", d_rgba);
+        }
+        srt::DeviceScene* s = FromHandle(scene);
+        Bind bind(s->device());
+        s->Composite(d_offsets, d_ids, layers, d_opacity, row_begin, row_count, d_rgba, static_cast<hipStream_t>(stream));
+    });
+}
+
+RTK_API int rtkLayersHost(const char* scene_path, size_t width, size_t height, const float* positions, size_t count,
+                          size_t layers, int* ids, float* t) {
+    return Guarded([&] {
+        if (scene_path == nullptr) {
+            throw std::runtime_error("Bad argument: scene_path is NULL");
+        }
+        if (width == 0 || height == 0) {
+            throw std::runtime_error("Bad argument: width and height must be non-zero");
+        }
+        CheckLayers(layers);
+        if (count == 0) {
+            return;
+        }
+        CheckBuffer("positions", positions);
+        CheckBuffer("ids", ids);
+        const srt::Scene scene = srt::LoadScene(scene_path);
+        srt::HostLayers(scene, width, height, positions, count, layers, ids, t);
+    });
+}
+
+RTK_API int rtkCompositeHost(const char* scene_path, size_t width, size_t height, const float* offsets, const int* ids,
+                             size_t layers, const float* opacity, size_t row_begin, size_t row_count, float* rgba) {
+    return Guarded([&] {
+        if (scene_path == nullptr) {
+            throw std::runtime_error("Bad argument: scene_path is NULL");
+        }
+        if (width == 0 || height == 0) {
+            throw std::runtime_error("Bad argument: width and height must be non-zero");
+        }
+        CheckLayers(layers);
+        if (row_begin > height || row_count > height - row_begin) {
+            throw std::runtime_error("Bad argument: row band outside the frame");
+        }
+        if (row_count == 0) {
+            return;
+        }
+        CheckBuffer("offsets", offsets);
+        CheckBuffer("ids", ids);
+        CheckBuffer("opacity", opacity);
+        CheckBuffer("rgba", rgba);
+        const srt::Scene scene = srt::LoadScene(scene_path);
+        srt::HostComposite(scene, width, height, offsets, ids, layers, opacity, row_begin, row_count, rgba);
     });
 }
 

@@ -12,6 +12,7 @@ HIP stream with caller-owned device buffers (torch tensors or raw pointers):
     scene.gbuffer(offsets, ids, depth=d, normal=n, albedo=a)     # the surface under the hits (also attributes())
     scene.render_samples(offsets_s, ids_s, rgba, stream=s)       # S samples per pixel, resolved (also resolve())
     scene.shadow(light, offsets, ids, mask, rgba, stream=s)      # which pixels a spot light (a second scene) reaches
+    scene.layer_frame(offsets, ids_k, t_k, stream=s)             # the K nearest hits per pixel (also layers(), composite())
 
 This is the path bench.py times (inputs resident in HBM) and the one-process-per-GPU
 band renderer uses; ``runner.render`` is the host-image ml* path.
@@ -22,7 +23,7 @@ import ctypes
 import os
 
 from . import _native
-from ._native import (RTS_MAX_SAMPLES, SRT_MAX_BATCH, SRT_SCENE_CORNELL, SRT_SCENE_SOUP, SRT_SCENE_TRIANGLE, SRT_TRACE_BVH,
+from ._native import (RTK_MAX_LAYERS, RTS_MAX_SAMPLES, SRT_MAX_BATCH, SRT_SCENE_CORNELL, SRT_SCENE_SOUP, SRT_SCENE_TRIANGLE, SRT_TRACE_BVH,
                       SRT_TRACE_CULL, SRT_TRACE_LDS, SRT_TRACE_SCALAR)
 
 SCENE_KINDS = {"triangle": SRT_SCENE_TRIANGLE, "cornell": SRT_SCENE_CORNELL, "soup": SRT_SCENE_SOUP}
@@ -165,6 +166,49 @@ def resolve_host(path: str, width: int, height: int, offsets, ids, row_begin: in
     _check(_native.lib().rtsResolveHost(os.fsencode(path), width, height, arr(*[o.ctypes.data for o in off]),
                                         arr(*[i.ctypes.data for i in idv]), samples, row_begin, row_count,
                                         rgba.ctypes.data))
+    return rgba
+
+
+def layers_host(path: str, width: int, height: int, positions, layers: int):
+    """Depth layers on the host (rtkLayersHost: brute force, the library's canonical math, no
+    device): positions (count, 2) float32 -> (ids (layers, count) int32, t (layers, count) float32),
+    front to back, a missing layer as (-1, +inf)."""
+    import numpy as np
+
+    pos = np.ascontiguousarray(positions, np.float32)
+    if pos.ndim != 2 or pos.shape[1] != 2:
+        raise ValueError(f"positions must be (count, 2), got {pos.shape}")
+    if not 1 <= layers <= RTK_MAX_LAYERS:
+        raise ValueError(f"1 to {RTK_MAX_LAYERS} layers, got {layers}")
+    ids = np.empty((layers, pos.shape[0]), np.int32)
+    t = np.empty((layers, pos.shape[0]), np.float32)
+    _check(_native.lib().rtkLayersHost(os.fsencode(path), width, height, pos.ctypes.data, pos.shape[0], layers,
+                                       ids.ctypes.data, t.ctypes.data))
+    return ids, t
+
+
+def composite_host(path: str, width: int, height: int, offsets, ids, opacity, row_begin: int = 0,
+                   row_count: int | None = None):
+    """The over-composite of depth layers on the host (rtkCompositeHost: the library's canonical
+    math, no device): offsets (rows, W, 2) float32, ids (K, rows, W) int32 and opacity
+    (triangles,) float32 of the band rows [row_begin, row_begin + row_count) -> rgba (rows, W, 4)."""
+    import numpy as np
+
+    if row_count is None:
+        row_count = height - row_begin
+    off = np.ascontiguousarray(offsets, np.float32)
+    idv = np.ascontiguousarray(ids, np.int32)
+    opa = np.ascontiguousarray(opacity, np.float32)
+    if off.shape != (row_count, width, 2):
+        raise ValueError(f"offsets must be {(row_count, width, 2)}, got {off.shape}")
+    if idv.ndim != 3 or idv.shape[1:] != (row_count, width) or not 1 <= idv.shape[0] <= RTK_MAX_LAYERS:
+        raise ValueError(f"ids must be (1..{RTK_MAX_LAYERS} layers, {row_count}, {width}), got {idv.shape}")
+    n = scene_triangles(path)
+    if opa.shape != (n,):
+        raise ValueError(f"opacity must be {(n,)}, got {opa.shape}")
+    rgba = np.empty((row_count, width, 4), np.float32)
+    _check(_native.lib().rtkCompositeHost(os.fsencode(path), width, height, off.ctypes.data, idv.ctypes.data,
+                                          idv.shape[0], opa.ctypes.data, row_begin, row_count, rgba.ctypes.data))
     return rgba
 
 
@@ -410,6 +454,69 @@ class DeviceScene:
             raise ValueError("positions must have a shape (count, 2): raw pointers carry no count")
         _check(self._lib.rtqQueryAsync(self.handle, _ptr(positions), count, _ptr(ids), _ptr(t), _ptr(how),
                                        _stream(stream)))
+
+    def _layer_planes(self, ids, t, lead):
+        """The layer count K of ids (K,) + lead int32, with t (the same shape, float32) checked
+        against it."""
+        if not hasattr(ids, "shape"):
+            raise ValueError(f"ids must have a shape {('layers',) + lead}: raw pointers carry no layer count")
+        shape = tuple(ids.shape)
+        if len(shape) != 1 + len(lead) or shape[1:] != lead or not 1 <= shape[0] <= RTK_MAX_LAYERS:
+            raise ValueError(f"ids must be {(f'1..{RTK_MAX_LAYERS} layers',) + lead}, got {shape}")
+        self._check_tensor("ids", ids, "i32")
+        if t is not None:
+            if hasattr(t, "shape") and tuple(t.shape) != shape:
+                raise ValueError(f"t must be {shape}, got {tuple(t.shape)}")
+            self._check_tensor("t", t, "f32")
+        return shape[0]
+
+    def layers(self, positions, ids, t=None, how=None, stream=None):
+        """Depth layers (include/srt_layers.h): the K nearest hits, front to back, at arbitrary
+        image positions of the prepared frame. positions (count, 2) float32 -> ids (K, count) int32
+        (-1 = no such layer) and, optionally, t (K, count) float32 (+inf) and how (count,) uint8 as
+        query()'s; K = ids.shape[0], 1 to 8. Layer 0 is query()'s answer."""
+        if not hasattr(positions, "shape") or len(positions.shape) != 2 or positions.shape[1] != 2:
+            raise ValueError("positions must have a shape (count, 2): raw pointers carry no count")
+        count = positions.shape[0]
+        self._check_tensor("positions", positions, "f32")
+        layers = self._layer_planes(ids, t, (count,))
+        if how is not None:
+            if hasattr(how, "shape") and tuple(how.shape) != (count,):
+                raise ValueError(f"how must be {(count,)}, got {tuple(how.shape)}")
+            self._check_tensor("how", how, "u8")
+        _check(self._lib.rtkLayersAsync(self.handle, _ptr(positions), count, layers, _ptr(ids), _ptr(t), _ptr(how),
+                                        _stream(stream)))
+
+    def layer_frame(self, offsets, ids, t=None, how=None, row_begin: int = 0, row_count: int | None = None,
+                    stream=None):
+        """Depth layers at the pixels of the prepared frame's rows (rtkFrameAsync): offsets (rows, W,
+        2) float32 -> ids (K, rows, W) int32, t (K, rows, W) float32 and how (rows, W) uint8, the
+        last two optional. Plane ids[k] is what trace_ids() would store if the k nearer surfaces
+        were not there: it feeds shade(), gbuffer() and composite()."""
+        if row_count is None:
+            row_count = self.height - row_begin
+        self._check_buffer("offsets", offsets, row_count, 2, "f32")
+        layers = self._layer_planes(ids, t, (row_count, self.width))
+        if how is not None:
+            self._check_buffer("how", how, row_count, 0, "u8")
+        _check(self._lib.rtkFrameAsync(self.handle, _ptr(offsets), row_begin, row_count, layers, _ptr(ids), _ptr(t),
+                                       _ptr(how), _stream(stream)))
+
+    def composite(self, offsets, ids, opacity, rgba, row_begin: int = 0, row_count: int | None = None, stream=None):
+        """Over-composite of the rows' depth layers (rtkCompositeAsync): offsets (rows, W, 2) float32,
+        ids (K, rows, W) int32 as layer_frame() stores them and opacity (triangles,) float32, one
+        value per triangle -> rgba (rows, W, 4) float32: the layers' shades composited front to back
+        over the background, alpha = 1 - the transmittance left."""
+        if row_count is None:
+            row_count = self.height - row_begin
+        self._check_buffer("offsets", offsets, row_count, 2, "f32")
+        layers = self._layer_planes(ids, None, (row_count, self.width))
+        if hasattr(opacity, "shape") and tuple(opacity.shape) != (self.triangles,):
+            raise ValueError(f"opacity must be {(self.triangles,)}, got {tuple(opacity.shape)}")
+        self._check_tensor("opacity", opacity, "f32")
+        self._check_buffer("rgba", rgba, row_count, 4, "f32")
+        _check(self._lib.rtkCompositeAsync(self.handle, _ptr(offsets), _ptr(ids), layers, _ptr(opacity), row_begin,
+                                           row_count, _ptr(rgba), _stream(stream)))
 
     def _outputs(self, planes, lead):
         """rtg_outputs of the planes depth / bary / normal / albedo (None: not written), each

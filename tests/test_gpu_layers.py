@@ -1,0 +1,452 @@
+"""Depth layers on the device (include/srt_layers.h rtkLayersAsync, rtkFrameAsync,
+rtkCompositeAsync; render.hip LayersKernel, CompositeKernel): the K nearest hits per position from
+the shared setup's per-tile lists, and their over-composite.
+
+Every layer comparison is exact -- ids equal, t equal on the uint32 view -- against the CPU oracle's
+closest hit peeled K times (tests/layers_cases.py); composites against the numpy restatement over
+the oracle's shades, on the bits. `how` (0 = answered from the tile's list, 1 = every record
+streamed) keeps the tests from passing on a kernel that streams everything, the setup counters
+(SRT_SETUP_LOG=1) from passing on a build per call.
+"""
+from __future__ import annotations
+
+import re
+
+import numpy as np
+import pytest
+
+import layers_cases as lc
+import query_cases as qc
+
+pytestmark = pytest.mark.gpu
+
+CASES = ("stack", "twins", "q")
+KS = (1, 3, 8)
+ENV = ("SRT_SETUP", "SRT_CULL_BIN", "SRT_CULL_BIN_CAP", "SRT_TRACE_RECORDS")
+
+
+@pytest.fixture(scope="module")
+def paths(tmp_path_factory):
+    d = tmp_path_factory.mktemp("layers")
+    return {name: lc.write_case(name, d / f"{name}.srt") for name in CASES}
+
+
+def default_env(monkeypatch):
+    for name in ENV:
+        monkeypatch.delenv(name, raising=False)
+
+
+class Rig:
+    """One scene on cuda:0 and its stream; the calls return numpy arrays. Outputs start poisoned."""
+
+    def __init__(self, path, w, h):
+        import torch
+
+        import simpleraytracer_amd as srt
+
+        self.torch = torch
+        self.scene = srt.DeviceScene(path, 0)
+        self.stream = torch.cuda.current_stream()
+        self.w, self.h = w, h
+        self.scene.prepare(w, h, self.stream)
+
+    def _outputs(self, layers, lead):
+        torch = self.torch
+        ids = torch.full((layers,) + lead, -7, dtype=torch.int32, device="cuda")
+        t = torch.full((layers,) + lead, float("nan"), dtype=torch.float32, device="cuda")
+        how = torch.full(lead, 9, dtype=torch.uint8, device="cuda")
+        return ids, t, how
+
+    def layers(self, pos, layers):
+        p = self.torch.from_numpy(np.array(pos, np.float32)).cuda()  # (a copy: the shared cases are read-only)
+        ids, t, how = self._outputs(layers, (len(pos),))
+        self.torch.cuda.synchronize()
+        self.scene.layers(p, ids, t, how, stream=self.stream)
+        self.torch.cuda.synchronize()
+        return ids.cpu().numpy(), t.cpu().numpy(), how.cpu().numpy()
+
+    def layer_frame(self, offsets, layers, r0=0, rows=None):
+        rows = self.h - r0 if rows is None else rows
+        off = self.torch.from_numpy(np.array(offsets[r0:r0 + rows], np.float32)).cuda()
+        ids, t, how = self._outputs(layers, (rows, self.w))
+        self.torch.cuda.synchronize()
+        self.scene.layer_frame(off, ids, t, how, row_begin=r0, row_count=rows, stream=self.stream)
+        self.torch.cuda.synchronize()
+        return ids.cpu().numpy(), t.cpu().numpy(), how.cpu().numpy()
+
+    def query(self, pos):
+        torch = self.torch
+        p = torch.from_numpy(np.array(pos, np.float32)).cuda()
+        ids = torch.full((len(pos),), -7, dtype=torch.int32, device="cuda")
+        t = torch.full((len(pos),), float("nan"), dtype=torch.float32, device="cuda")
+        self.scene.query(p, ids, t, stream=self.stream)
+        torch.cuda.synchronize()
+        return ids.cpu().numpy(), t.cpu().numpy()
+
+    def trace_ids(self, offsets):
+        torch = self.torch
+        off = torch.from_numpy(np.array(offsets, np.float32)).cuda()
+        out = torch.full((self.h, self.w), -7, dtype=torch.int32, device="cuda")
+        self.scene.trace_ids(off, out, 0, self.h, variant="cull", stream=self.stream)
+        torch.cuda.synchronize()
+        return out.cpu().numpy()
+
+    def composite(self, offsets, ids, opacity, r0=0, rows=None):
+        torch = self.torch
+        rows = self.h - r0 if rows is None else rows
+        off = torch.from_numpy(np.array(offsets[r0:r0 + rows], np.float32)).cuda()
+        idp = torch.from_numpy(np.array(ids, np.int32)).cuda()
+        opa = torch.from_numpy(np.array(opacity, np.float32)).cuda()
+        out = torch.full((rows, self.w, 4), float("nan"), dtype=torch.float32, device="cuda")
+        self.scene.composite(off, idp, opa, out, row_begin=r0, row_count=rows, stream=self.stream)
+        torch.cuda.synchronize()
+        return out.cpu().numpy()
+
+    def depth(self, offsets, ids):
+        torch = self.torch
+        off = torch.from_numpy(np.array(offsets, np.float32)).cuda()
+        idp = torch.from_numpy(np.array(ids, np.int32)).cuda()
+        out = torch.full((self.h, self.w), float("nan"), dtype=torch.float32, device="cuda")
+        self.scene.gbuffer(off, idp, depth=out, stream=self.stream)
+        torch.cuda.synchronize()
+        return out.cpu().numpy()
+
+    def stats(self, capfd):
+        lines = re.findall(r"srt setup: scene \S+ builds (\d+) shared_frames (\d+) per_frame_frames (\d+)",
+                           capfd.readouterr().err)
+        assert lines, "no setup counters on stderr: is SRT_SETUP_LOG honoured?"
+        return tuple(int(v) for v in lines[-1])
+
+    def close(self):
+        self.scene.close()
+
+
+@pytest.mark.parametrize("name", CASES)
+def test_point_mode_equals_the_oracle(gpu, paths, monkeypatch, name):
+    """The mixed positions (random, every tile boundary with its float neighbours, out of range,
+    NaN), K = 1, 3, 8: the oracle's layers; from the lists exactly for positions in [0, 1]^2; layer
+    0 is rtqQueryAsync's answer."""
+    default_env(monkeypatch)
+    w, h = lc.FRAMES[name]
+    pos, want_ids, want_t = lc.cached_layers(paths[name], name, "mixed")
+    lc.assert_conditions(name, want_ids, want_t)
+    inside = qc.in_range(pos)
+    assert inside.sum() >= 2000 and (~inside).sum() >= len(qc.OUT_OF_RANGE) ** 2
+    rig = Rig(paths[name], w, h)
+    got = {k: rig.layers(pos, k) for k in KS}
+    q_ids, q_t = rig.query(pos)
+    rig.close()
+    for k in KS:
+        ids, t, how = got[k]
+        lc.assert_same(ids, t, want_ids[:k], want_t[:k])
+        assert np.array_equal(how, np.where(inside, 0, 1).astype(np.uint8))
+        lc.assert_same(ids[0], t[0], q_ids, q_t)
+    nan = np.isnan(pos).any(axis=1)
+    assert nan.any() and np.all(got[8][0][:, nan] == -1)
+
+
+@pytest.mark.parametrize("name", CASES)
+def test_frame_mode_equals_the_oracle(gpu, paths, monkeypatch, capfd, name):
+    """Every pixel of a frame with random offsets, K = 1, 3, 8, and a band short of the frame: the
+    oracle's layers, all answered from the lists; layer 0 is the id the cull trace stores, and the
+    trace that follows shares the layers call's setup build."""
+    default_env(monkeypatch)
+    monkeypatch.setenv("SRT_SETUP_LOG", "1")
+    w, h = lc.FRAMES[name]
+    r0, rows = lc.BANDS[name]
+    off = lc.offsets(w, h)
+    _, want_ids, want_t = lc.cached_layers(paths[name], name, "pixels")
+    lc.assert_conditions(name, want_ids, want_t)
+    want_ids, want_t = want_ids.reshape(-1, h, w), want_t.reshape(-1, h, w)
+    rig = Rig(paths[name], w, h)
+    got = {k: rig.layer_frame(off, k) for k in KS}
+    band = rig.layer_frame(off, 3, r0, rows)
+    traced = rig.trace_ids(off)
+    builds = rig.stats(capfd)[0]
+    rig.close()
+    for k in KS:
+        ids, t, how = got[k]
+        lc.assert_same(ids, t, want_ids[:k], want_t[:k])
+        assert np.all(how == 0)
+        assert np.array_equal(ids[0], traced)
+    assert 0 < r0 and r0 + rows < h and r0 % 16 != 0
+    lc.assert_same(band[0], band[1], want_ids[:3, r0:r0 + rows], want_t[:3, r0:r0 + rows])
+    assert np.all(band[2] == 0)
+    assert builds == 1
+
+
+def test_optional_outputs(gpu, paths, monkeypatch):
+    """t and how may be left out; the ids do not change."""
+    import torch
+
+    default_env(monkeypatch)
+    w, h = lc.FRAMES["stack"]
+    pos, want_ids, _ = lc.cached_layers(paths["stack"], "stack", "mixed")
+    rig = Rig(paths["stack"], w, h)
+    p = torch.from_numpy(np.array(pos, np.float32)).cuda()
+    ids = torch.full((3, len(pos)), -7, dtype=torch.int32, device="cuda")
+    rig.scene.layers(p, ids, stream=rig.stream)
+    torch.cuda.synchronize()
+    rig.close()
+    assert np.array_equal(ids.cpu().numpy(), want_ids[:3])
+
+
+def test_overflowed_lists_stream(gpu, paths, monkeypatch):
+    """Lists capped at 8 entries: a position in an overflowed tile streams, one in a short tile does
+    not, and both answer right."""
+    default_env(monkeypatch)
+    monkeypatch.setenv("SRT_CULL_BIN_CAP", "8")
+    w, h = lc.FRAMES["stack"]
+    pos, want_ids, want_t = lc.cached_layers(paths["stack"], "stack", "mixed")
+    rig = Rig(paths["stack"], w, h)
+    ids, t, how = rig.layers(pos, 8)
+    rig.close()
+    lc.assert_same(ids, t, want_ids[:8], want_t[:8])
+    inside = qc.in_range(pos)
+    assert (how[inside] == 1).any() and (how[inside] == 0).any()
+    assert np.all(how[~inside] == 1)
+
+
+@pytest.mark.parametrize("records", ["stored", "recompute"])
+def test_record_sources(gpu, paths, monkeypatch, records):
+    default_env(monkeypatch)
+    monkeypatch.setenv("SRT_TRACE_RECORDS", records)
+    w, h = lc.FRAMES["q"]
+    pos, want_ids, want_t = lc.cached_layers(paths["q"], "q", "mixed")
+    off = lc.offsets(w, h)
+    _, pix_ids, pix_t = lc.cached_layers(paths["q"], "q", "pixels")
+    rig = Rig(paths["q"], w, h)
+    ids, t, how = rig.layers(pos, 8)
+    fids, ft, fhow = rig.layer_frame(off, 3)
+    rig.close()
+    lc.assert_same(ids, t, want_ids[:8], want_t[:8])
+    assert np.array_equal(how == 0, qc.in_range(pos))
+    lc.assert_same(fids, ft, pix_ids[:3], pix_t[:3])
+    assert np.all(fhow == 0)
+
+
+@pytest.mark.parametrize("env_name,value", [("SRT_SETUP", "frame"), ("SRT_CULL_BIN", "0")])
+def test_no_usable_setup_streams_every_position(gpu, paths, monkeypatch, env_name, value):
+    default_env(monkeypatch)
+    monkeypatch.setenv(env_name, value)
+    w, h = lc.FRAMES["twins"]
+    pos, want_ids, want_t = lc.cached_layers(paths["twins"], "twins", "mixed")
+    pos, want_ids, want_t = pos[:2000], want_ids[:, :2000], want_t[:, :2000]  # the random in-range positions
+    assert qc.in_range(pos).all() and (want_ids[7] >= 0).any()
+    rig = Rig(paths["twins"], w, h)
+    ids, t, how = rig.layers(pos, 8)
+    rig.close()
+    lc.assert_same(ids, t, want_ids[:8], want_t[:8])
+    assert np.all(how == 1)
+
+
+def deep_vertices(quads=150):
+    """2 x quads triangles: nested quads one behind the other, every one covering the image centre,
+    their triangles stored in a shuffled order -- keys arrive at a lane neither ascending nor
+    descending, so a full list both refuses and evicts."""
+    tri = []
+    for i in range(quads):
+        z, s = 2.0 + 0.02 * i, 0.4 + 0.004 * i
+        a, b, c, d = (-s, -s, z), (s, -s, z), (s, s, z), (-s, s, z)
+        tri += [[a, b, c], [a, c, d]]
+    v = np.array(tri, np.float32)
+    return v[np.random.default_rng(51).permutation(len(v))]
+
+
+def test_a_lanes_list_fills_and_evicts(gpu, tmp_path, monkeypatch):
+    """150 surfaces behind one another at the centre positions: far more passing candidates than a
+    group's lanes hold slots (16 lanes x 8), so by pigeonhole lanes fill up, refuse and evict."""
+    from scenefile import write_custom_scene
+
+    default_env(monkeypatch)
+    w, h = 160, 96
+    path = write_custom_scene(tmp_path / "deep.srt", deep_vertices().reshape(-1, 9))
+    rng = np.random.default_rng(52)
+    pos = np.concatenate([rng.uniform(0.42, 0.58, (1500, 2)), rng.random((500, 2))]).astype(np.float32)
+    want_ids, want_t = lc.oracle_layers(path, w, h, pos)
+    full_ids, _ = lc.oracle_layers(path, w, h, pos[:4], layers=160)
+    assert np.all((full_ids >= 0).sum(axis=0) >= 140)  # (the centre: ~150 hits per position)
+    assert (want_ids[8] >= 0).sum() >= 1500 and (want_ids[0] < 0).any()
+    rig = Rig(path, w, h)
+    got = {k: rig.layers(pos, k) for k in (1, 2, 3, 4, 5, 8)}
+    rig.close()
+    for k, (ids, t, how) in got.items():
+        lc.assert_same(ids, t, want_ids[:k], want_t[:k])
+        assert np.all(how == 0)
+
+
+def test_long_lists(gpu, scenes, monkeypatch):
+    """soup-100k at 1920 x 1080: the centre tiles' lists hold several hundred candidates, so a
+    group walks many rounds. 512 random positions and 512 pixels of row 538."""
+    import simpleraytracer_amd.device as device
+
+    default_env(monkeypatch)
+    w, h = 1920, 1080
+    rng = np.random.default_rng(17)
+    pixels = device.pixel_positions(w, h, 0.5).reshape(h, w, 2)[538, 700:1212]
+    pos = np.concatenate([rng.random((512, 2), dtype=np.float32), pixels])
+    want_ids, want_t = lc.oracle_layers(scenes["soup100k"], w, h, pos)
+    hits = (want_ids >= 0).sum(axis=0)
+    assert (hits == 0).any() and (hits >= 3).sum() >= 0.05 * len(pos)
+    rig = Rig(scenes["soup100k"], w, h)
+    ids, t, how = rig.layers(pos, 8)
+    rig.close()
+    lc.assert_same(ids, t, want_ids[:8], want_t[:8])
+    assert np.all(how == 0)
+
+
+@pytest.fixture(scope="module")
+def frame_case(paths):
+    """The stack case's frame: offsets, the oracle's 8 id planes and t, their oracle shades, the
+    opacity table. Read-only."""
+    import simpleraytracer_amd.device as device
+
+    name = "stack"
+    w, h = lc.FRAMES[name]
+    off = lc.offsets(w, h)
+    _, ids, t = lc.cached_layers(paths[name], name, "pixels")
+    ids = ids[:lc.MAX_LAYERS].reshape(lc.MAX_LAYERS, h, w)
+    t = t[:lc.MAX_LAYERS].reshape(lc.MAX_LAYERS, h, w)
+    shaded = lc.shaded_layers(paths[name], w, h, ids, off)
+    opa = lc.opacity(device.scene_triangles(paths[name]))
+    for a in (off, shaded, opa):
+        a.setflags(write=False)
+    return paths[name], w, h, off, ids, t, shaded, opa
+
+
+def test_composite_equals_the_host_path_and_the_restatement(gpu, frame_case, monkeypatch):
+    """Whole frame, K = 1, 3, 8, and a band of K = 4: the device's pixels are the host path's and
+    the numpy restatement's over the oracle's shades, on the bits. The ids are the device's own
+    layers (equal to the oracle's: the tests above)."""
+    import simpleraytracer_amd.device as device
+
+    default_env(monkeypatch)
+    path, w, h, off, ids, _, shaded, opa = frame_case
+    r0, rows = lc.BANDS["stack"]
+    rig = Rig(path, w, h)
+    own, _, _ = rig.layer_frame(off, 8)
+    got = {k: rig.composite(off, own[:k], opa) for k in KS}
+    band = rig.composite(off, own[:4, r0:r0 + rows], opa, r0, rows)
+    rig.close()
+    assert np.array_equal(own, ids)
+    for k in KS:
+        lc.same_bits(f"composite K={k} vs host", got[k], device.composite_host(path, w, h, off, ids[:k], opa))
+        lc.same_bits(f"composite K={k}", got[k], lc.expected_composite(shaded[:k], ids[:k], opa, lc.BACKGROUND))
+    lc.same_bits("composite band", band,
+                 lc.expected_composite(shaded[:4, r0:r0 + rows], ids[:4, r0:r0 + rows], opa, lc.BACKGROUND))
+
+
+def test_composite_opaque_clear_and_foreign_ids(gpu, frame_case, monkeypatch):
+    """Opacity 1 everywhere: the shaded frame's rgb, alpha 1 or 0. Opacity 0: the background. Ids
+    outside the scene end a pixel's composite and nothing is read through them."""
+    default_env(monkeypatch)
+    path, w, h, off, ids, _, shaded, opa = frame_case
+    n = len(opa)
+    mixed = ids[:4].copy()
+    bad = np.array([-1, -5, n, n + 7, 2**31 - 1, -2**31], np.int64).astype(np.int32)
+    mixed[1].reshape(-1)[::7] = np.resize(bad, mixed[1].reshape(-1)[::7].size)
+    rig = Rig(path, w, h)
+    opaque = rig.composite(off, ids, np.ones_like(opa))
+    clear = rig.composite(off, ids, np.zeros_like(opa))
+    foreign = rig.composite(off, mixed, opa)
+    rig.close()
+    hit = ids[0] >= 0
+    assert hit.any() and (~hit).any()
+    lc.same_bits("opaque rgb", opaque[..., :3], shaded[0, ..., :3])
+    assert np.array_equal(opaque[..., 3], hit.astype(np.float32))
+    lc.same_bits("clear", clear, np.broadcast_to(np.float32(lc.BACKGROUND + (0.0,)), (h, w, 4)))
+    lc.same_bits("foreign ids", foreign, lc.expected_composite(shaded[:4], mixed, opa, lc.BACKGROUND))
+
+
+def test_each_plane_feeds_the_gbuffer(gpu, frame_case, monkeypatch):
+    """Plane k of the ids into rtgFrameAsync: its depth is layer k's t, bit for bit (+inf: none)."""
+    default_env(monkeypatch)
+    path, w, h, off, ids, t, _, _ = frame_case
+    rig = Rig(path, w, h)
+    own_ids, own_t, _ = rig.layer_frame(off, 8)
+    depth = np.stack([rig.depth(off, own_ids[k]) for k in range(8)])
+    rig.close()
+    lc.assert_same(own_ids, own_t, ids, t)
+    lc.same_bits("depth of the planes", depth, t)
+
+
+def test_edge_cases(gpu, paths, monkeypatch):
+    import torch
+
+    import simpleraytracer_amd as srt
+    from simpleraytracer_amd import SrtError, _native
+
+    default_env(monkeypatch)
+    L = _native.lib()
+    w, h = lc.FRAMES["stack"]
+    scene = srt.DeviceScene(paths["stack"], 0)
+    p = torch.zeros((4, 2), dtype=torch.float32, device="cuda")
+    ids = torch.zeros((2, 4), dtype=torch.int32, device="cuda")
+    t = torch.zeros((2, 4), dtype=torch.float32, device="cuda")
+    off = torch.full((h, w, 2), 0.5, dtype=torch.float32, device="cuda")
+    fids = torch.zeros((2, h, w), dtype=torch.int32, device="cuda")
+    opa = torch.ones((scene.triangles,), dtype=torch.float32, device="cuda")
+    rgba = torch.zeros((h, w, 4), dtype=torch.float32, device="cuda")
+    # a scene that was never prepared
+    assert L.rtkLayersAsync(scene.handle, p.data_ptr(), 4, 2, ids.data_ptr(), None, None, None) == -1
+    assert re.search(r"Layers: Prepare\(\) has not been called", _native.last_error())
+    assert L.rtkCompositeAsync(scene.handle, off.data_ptr(), fids.data_ptr(), 2, opa.data_ptr(), 0, 1,
+                               rgba.data_ptr(), None) == -1
+    assert re.search(r"Composite: Prepare\(\) has not been called", _native.last_error())
+    scene.prepare(w, h)
+    # nothing to do: nothing enqueued, no buffer needed
+    assert L.rtkLayersAsync(scene.handle, None, 0, 1, None, None, None, None) == 0
+    assert L.rtkFrameAsync(scene.handle, None, h, 0, 1, None, None, None, None) == 0
+    assert L.rtkCompositeAsync(scene.handle, None, None, 1, None, h, 0, None, None) == 0
+    # the layer count
+    for layers in (0, 9):
+        assert L.rtkLayersAsync(scene.handle, p.data_ptr(), 4, layers, ids.data_ptr(), None, None, None) == -1
+        assert f"layers must be 1 to 8, got {layers}" in _native.last_error()
+        assert L.rtkFrameAsync(scene.handle, off.data_ptr(), 0, h, layers, fids.data_ptr(), None, None, None) == -1
+        assert f"layers must be 1 to 8, got {layers}" in _native.last_error()
+        assert L.rtkCompositeAsync(scene.handle, off.data_ptr(), fids.data_ptr(), layers, opa.data_ptr(), 0, h,
+                                   rgba.data_ptr(), None) == -1
+        assert f"layers must be 1 to 8, got {layers}" in _native.last_error()
+    # null arguments
+    assert L.rtkLayersAsync(None, p.data_ptr(), 4, 2, ids.data_ptr(), None, None, None) == -1
+    assert _native.last_error() == "Bad scene handle"
+    assert L.rtkLayersAsync(scene.handle, None, 4, 2, ids.data_ptr(), None, None, None) == -1
+    assert "d_positions" in _native.last_error()
+    assert L.rtkLayersAsync(scene.handle, p.data_ptr(), 4, 2, None, None, None, None) == -1
+    assert "d_ids" in _native.last_error()
+    assert L.rtkFrameAsync(scene.handle, None, 0, h, 2, fids.data_ptr(), None, None, None) == -1
+    assert "d_offsets" in _native.last_error()
+    for k, name in enumerate(("d_offsets", "d_ids", "d_opacity", "d_rgba")):
+        args = [off.data_ptr(), fids.data_ptr(), opa.data_ptr(), rgba.data_ptr()]
+        args[k] = None
+        assert L.rtkCompositeAsync(scene.handle, args[0], args[1], 2, args[2], 0, h, args[3], None) == -1
+        assert name in _native.last_error()
+    # a band outside the frame
+    assert L.rtkFrameAsync(scene.handle, off.data_ptr(), h - 1, 2, 2, fids.data_ptr(), None, None, None) == -1
+    assert "row band outside the frame" in _native.last_error()
+    assert L.rtkCompositeAsync(scene.handle, off.data_ptr(), fids.data_ptr(), 2, opa.data_ptr(), h - 1, 2,
+                               rgba.data_ptr(), None) == -1
+    assert "row band outside the frame" in _native.last_error()
+    # the wrapper's buffer checks
+    with pytest.raises(ValueError):
+        scene.layers(torch.zeros((4, 3), dtype=torch.float32, device="cuda"), ids)
+    with pytest.raises(ValueError):
+        scene.layers(p, torch.zeros((9, 4), dtype=torch.int32, device="cuda"))
+    with pytest.raises(ValueError):
+        scene.layers(p, torch.zeros((2, 5), dtype=torch.int32, device="cuda"))
+    with pytest.raises(ValueError):
+        scene.layers(p, ids, t[:1])
+    with pytest.raises(ValueError):
+        scene.layers(p, ids.to(torch.int64))
+    with pytest.raises(ValueError):
+        scene.layer_frame(off, fids[:, :-1])
+    with pytest.raises(ValueError):
+        scene.composite(off, fids, opa[:-1], rgba)
+    with pytest.raises(SrtError):
+        scene.layer_frame(off[:2], fids[:, :2].contiguous(), row_begin=h - 1, row_count=2)
+    # the valid calls still work after the refused ones
+    scene.layers(p, ids, t)
+    torch.cuda.synchronize()
+    want_ids, want_t = lc.oracle_layers(paths["stack"], w, h, np.zeros((4, 2), np.float32), layers=2)
+    lc.assert_same(ids.cpu().numpy(), t.cpu().numpy(), want_ids, want_t)
+    scene.close()
