@@ -315,6 +315,10 @@ struct CullSetup {
     unsigned* large_list;  // positions binned to every tile
     void* work;            // the plan: descs descriptors, heaviest first, facts baked in
     unsigned* work_count;
+    unsigned long long* stream_count;  // [0]: records of the record stream (LaunchStreamPlan), pad records included
+    // The record stream (below): an allocation of its own, sized from stream_count after the plan;
+    // null: the traces read the records through the lists (the indexed path).
+    const void* stream;
     std::size_t zero_bytes;
     std::size_t tiles;
     unsigned capacity;
@@ -322,6 +326,19 @@ struct CullSetup {
     unsigned min_chunk;    // smallest candidate chunk of a split part (env SRT_CULL_CHUNK at the carve-up)
     bool recompute;        // CullBins::recompute of the traces it serves
 };
+// The record stream of a built setup: the 64-B cull records of every (tile, chunk) of the plan, in
+// the order its trace blocks walk them (chunk [begin, end) of the tile's bin list, then the large
+// list), each range starting at a multiple of 128 B (an even record index). The parts of a tile walk
+// the same lists, so they share the tile's ranges. A statically FULL or empty descriptor has no
+// range. LaunchStreamPlan (after LaunchCullSetup, same stream) writes every descriptor's first record
+// index and record count into its w1.x and w1.y -- unused on the shared path otherwise --, zeroes
+// the second half of the end marks, and writes the stream's length into setup.stream_count; the
+// caller reads that once, allocates, and LaunchStreamPack fills `stream`.
+// A trace launched with setup.stream != null reads its candidates from there (stored records only).
+constexpr std::size_t kCullRecordBytes = 64;
+constexpr std::size_t kStreamCapRecords = std::size_t{1} << 22;  // 256 MiB (the sizes measured)
+hipError_t LaunchStreamPlan(const CullSetup& setup, hipStream_t stream);
+hipError_t LaunchStreamPack(const CullSetup& setup, void* records, hipStream_t stream);
 std::size_t CullSetupBytes(std::uint64_t n, std::size_t width, std::size_t height, unsigned descs);
 CullSetup CullSetupLayout(void* base, std::uint64_t n, std::size_t width, std::size_t height, unsigned descs,
                           bool recompute);

@@ -66,6 +66,7 @@ constexpr int kRowsPerLane = 8;  // rays per lane (LDS / scalar variants): one c
 struct CullRecord {
     float4 a, b, x, sb;
 };
+static_assert(sizeof(CullRecord) == kCullRecordBytes, "render.h kCullRecordBytes");
 
 // Per-tile facts the cull trace and the bin kernel share (TileInfoKernel), 32 B.
 struct TileInfo {
@@ -129,6 +130,7 @@ struct TraceParams {
     unsigned* __restrict__ bin_counts_next;   // the slot's other count buffer: reset by the trace for its next frame
     const unsigned* __restrict__ large_list;  // ids of records binned to every tile
     const unsigned* __restrict__ range_tag;   // = gen: some sample offset of this frame lies outside [0, 1]
+    const CullRecord* __restrict__ stream;    // shared setup's record stream (render.h; TraceCullKernel<.., STREAM>)
     unsigned gen;                              // frame number of the scene (never 0)
     unsigned fused;                            // bins from the analytic tile bounds (BinParams::fused)
     unsigned plan_only;  // the work list is the slot's plan (no order launch for this frame): read the bins
@@ -2941,8 +2943,14 @@ struct TraceRecords<true> {
 // plan, whose descriptors hold the tile's candidate count, list length, chunking, and the FULL
 // (unusable analytic box, overflowed list) and empty flags; p.bin_lists, p.large_list and the
 // records are the setup's and read-only (no count is reset); p.tile_facts holds this frame's facts.
-template <class Frames, bool RC = false, bool SHARED = false>
+// STREAM (shared setup, stored records): the block's candidates are the records p.stream[w1.x ..]
+// of the setup's record stream (render.h), in the order the lists give them. The range is a
+// function of the plan alone, so the first batch is requested as soon as the descriptor is there,
+// beside the frame's tile facts; a tile whose facts then say FULL drops what was loaded and streams
+// every record as on the indexed path. No list entry is read.
+template <class Frames, bool RC = false, bool SHARED = false, bool STREAM = false>
 __global__ __launch_bounds__(kCullThreads, SRT_TRACE_OCC) void TraceCullKernel(const Frames batch) {
+    static_assert(!STREAM || (SHARED && !RC), "the record stream: stored records of the shared setup");
     const TraceParams& p = batch[blockIdx.z];
     using Recs = TraceRecords<RC>;
     constexpr int R = kCullR;
@@ -2976,13 +2984,21 @@ __global__ __launch_bounds__(kCullThreads, SRT_TRACE_OCC) void TraceCullKernel(c
     unsigned item, chunk = 0u, nchunks = 1u, slot = 0u, flags = kItemFull;
     float ox = 0.f, oy = 0.f;
     CullSource src{nullptr, nullptr, 0u, 0u, 0u, true};
-    if (p.work != nullptr) {
+    typename Recs::Raw nxt[kSlices];  // the next batch's records, requested one batch ahead
+    [[maybe_unused]] const CullRecord* sbase = nullptr;  // STREAM: the block's range of the record stream
+    [[maybe_unused]] unsigned stream_n = 0u;             // STREAM: its records (the plan's: the tile in range)
+    if (STREAM || p.work != nullptr) {  // (STREAM: always a plan; its pointer is not waited for on its own)
         // The work list (WorkOrderKernel) gives this block its tile part and chunk; with an order
         // launch for this frame it also holds the frame's facts, else it is the slot's plan
         // (scheduling only) and the block reads them from the frame's bins and tile info.
         const unsigned d = blockIdx.x;  // < descs: the plan, then end marks
         const uint4 w0 = p.work[2 * d], w1 = p.work[2 * d + 1];
-        if (w0.x == kWorkEnd) {
+        // (STREAM: an end mark is the tag and seven zero words -- StreamPlanKernel clears its second
+        // half --, tested as a whole so that the descriptor arrives in one load, not its first word
+        // and, a round trip later, the rest)
+        const bool end_mark = STREAM ? (w0.x == kWorkEnd) & ((w0.y | w0.z | w0.w | w1.x | w1.y | w1.z | w1.w) == 0u)
+                                     : w0.x == kWorkEnd;
+        if (end_mark) {
             return;
         }
         item = w0.x;
@@ -3008,6 +3024,23 @@ __global__ __launch_bounds__(kCullThreads, SRT_TRACE_OCC) void TraceCullKernel(c
             // for an unusable box, the tile streams every record, as a plan-only frame's would, and
             // the setup's empty flag (made for rays inside the analytic box) does not hold.
             const TileFacts tf = p.tile_facts[t];
+            if constexpr (STREAM) {
+                // The first batch, requested beside the facts (a scalar load; the records are vector
+                // loads, so neither waits for the other): its range is the plan's -- w1.y records
+                // from w1.x, the cut below made by StreamPlanKernel -- and lies in the stream
+                // whatever the facts say.
+                stream_n = w1.y;
+                sbase = p.stream + w1.x;
+                if (stream_n != 0u) {
+#pragma unroll
+                    for (int e = 0; e < kSlices; ++e) {
+                        if (InBatch(e, threadIdx.x)) {
+                            const unsigned v = e * kCullThreads + threadIdx.x;
+                            nxt[e] = sbase[v < stream_n ? v : 0u];
+                        }
+                    }
+                }
+            }
             constexpr unsigned kValid = kFactUsable | kFactInRange;
             full = (w0.w & kItemFull) != 0u || (tf.flags & kValid) != kValid;
             flags = (full ? kItemFull : (w0.w & kItemEmpty)) | ((tf.flags & kFactRegular) != 0u ? kItemRegular : 0u);
@@ -3062,7 +3095,9 @@ __global__ __launch_bounds__(kCullThreads, SRT_TRACE_OCC) void TraceCullKernel(c
         // A FULL tile streams every record in its part's first chunk; the plan's other chunks of
         // the part (the plan is made as if the bins were valid) have no candidates and publish misses.
         src.full = full && chunk == 0u;
-        if (!src.full) {
+        if constexpr (STREAM) {
+            src.end = full ? 0u : stream_n;  // positions of the block's own stream range
+        } else if (!src.full) {
             // candidates cut into n chunks: chunk c = [c q + c r / n, (c + 1) q + (c + 1) r / n), q r = c_t / n, % n
             const unsigned q = c_t / nchunks, r = c_t % nchunks;
             src.list = p.bin_lists + static_cast<size_t>(t) * p.bin_capacity;
@@ -3116,12 +3151,11 @@ __global__ __launch_bounds__(kCullThreads, SRT_TRACE_OCC) void TraceCullKernel(c
     // LIST: the first batch's records are requested before the rays are set up (its loads
     // are the block's longest dependency chain: list entry, then the 64-B record).
     const unsigned total = src.end - src.begin;
-    typename Recs::Raw nxt[kSlices];
     // The list entries run one batch ahead of the records: batch b's prefetch loads batch b + 1's
     // records from entries that arrived during batch b - 1's walk, then requests batch b + 2's
     // entries (one load chain per batch no longer waits in front of the walk).
-    unsigned nid[kSlices];
-    auto load_ids = [&](unsigned b0) {
+    [[maybe_unused]] unsigned nid[kSlices];
+    [[maybe_unused]] auto load_ids = [&](unsigned b0) {
 #pragma unroll
         for (int e = 0; e < kSlices; ++e) {
             const unsigned v = b0 + e * kCullThreads + tid;
@@ -3131,7 +3165,7 @@ __global__ __launch_bounds__(kCullThreads, SRT_TRACE_OCC) void TraceCullKernel(c
             }
         }
     };
-    auto load_recs = [&] {
+    [[maybe_unused]] auto load_recs = [&] {
 #pragma unroll
         for (int e = 0; e < kSlices; ++e) {
             if (InBatch(e, tid)) {
@@ -3140,14 +3174,26 @@ __global__ __launch_bounds__(kCullThreads, SRT_TRACE_OCC) void TraceCullKernel(c
         }
     };
     auto load_list = [&](unsigned b0) {  // b0: the batch whose records are loaded now
-        load_recs();
-        if (b0 + kPacketBatch < total) {
-            load_ids(b0 + kPacketBatch);
+        if constexpr (STREAM) {  // straight from the block's stream range: no entries
+#pragma unroll
+            for (int e = 0; e < kSlices; ++e) {
+                const unsigned v = b0 + e * kCullThreads + tid;
+                if (InBatch(e, tid)) {
+                    nxt[e] = sbase[v < total ? v : 0u];
+                }
+            }
+        } else {
+            load_recs();
+            if (b0 + kPacketBatch < total) {
+                load_ids(b0 + kPacketBatch);
+            }
         }
     };
-    if (!src.full && total != 0u) {
-        load_ids(0u);
-        load_list(0u);
+    if constexpr (!STREAM) {  // (STREAM: the first batch was requested with the facts)
+        if (!src.full && total != 0u) {
+            load_ids(0u);
+            load_list(0u);
+        }
     }
     // Rays: lane = column x; rows y0 .. y0 + R - 1. A regular tile (every ray with the sample
     // offset (ox, oy)) computes them without reading the offsets: fx per lane, and row r's fy
@@ -4782,7 +4828,7 @@ hipError_t LaunchCullFrames(const CullFrame* frames, std::size_t count, std::uin
 
 namespace {
 struct SetupSizes {
-    std::size_t counts, range_tag, work_count, info, screen_boxes, qboxes, cull, lists, large, work;
+    std::size_t counts, range_tag, work_count, stream_count, info, screen_boxes, qboxes, cull, lists, large, work;
 };
 SetupSizes CullSetupSizes(std::uint64_t n, std::size_t width, std::size_t height, unsigned descs) {
     const std::size_t tiles = CullTiles(width, height), n_pad = PaddedTriangleCount(n);
@@ -4791,6 +4837,7 @@ SetupSizes CullSetupSizes(std::uint64_t n, std::size_t width, std::size_t height
     z.counts = al((tiles + 1) * 4);
     z.range_tag = al(4);
     z.work_count = al(kOrderWords * 4);
+    z.stream_count = al(8);
     z.info = al(tiles * sizeof(TileInfo));
     z.screen_boxes = al(n_pad * sizeof(float4));
     z.qboxes = al(n_pad * sizeof(uint2));
@@ -4804,8 +4851,8 @@ SetupSizes CullSetupSizes(std::uint64_t n, std::size_t width, std::size_t height
 
 std::size_t CullSetupBytes(std::uint64_t n, std::size_t width, std::size_t height, unsigned descs) {
     const SetupSizes z = CullSetupSizes(n, width, height, descs);
-    return z.counts + z.range_tag + z.work_count + z.info + z.screen_boxes + z.qboxes + z.cull + z.lists + z.large +
-           z.work;
+    return z.counts + z.range_tag + z.work_count + z.stream_count + z.info + z.screen_boxes + z.qboxes + z.cull +
+           z.lists + z.large + z.work;
 }
 
 CullSetup CullSetupLayout(void* base, std::uint64_t n, std::size_t width, std::size_t height, unsigned descs,
@@ -4823,6 +4870,8 @@ CullSetup CullSetupLayout(void* base, std::uint64_t n, std::size_t width, std::s
     s.range_tag = reinterpret_cast<unsigned*>(take(z.range_tag));
     s.zero_bytes = z.counts + z.range_tag;
     s.work_count = reinterpret_cast<unsigned*>(take(z.work_count));
+    s.stream_count = reinterpret_cast<unsigned long long*>(take(z.stream_count));
+    s.stream = nullptr;  // (the caller's, once the plan has sized it)
     s.tile_info = take(z.info);
     s.screen_boxes = take(z.screen_boxes);
     s.qboxes = take(z.qboxes);
@@ -4907,15 +4956,137 @@ hipError_t LaunchCullSetup(const CullSetup& s, std::uint64_t n, const Frame& fra
     return hipGetLastError();
 }
 
+// The record stream of a built setup (render.h). Both kernels derive a descriptor's range from the
+// descriptor alone, with the cut TraceCullKernel makes: chunk c of n = [c q + c r / n, (c + 1) q +
+// (c + 1) r / n) of the w0.y candidates. A part other than the tile's first owns no records: it
+// takes the offsets of the first part's descriptors, which lie `part` x n before its own.
+namespace {
+constexpr int kPlanBlock = 1024;
+constexpr int kPackBlock = 256;
+__device__ __forceinline__ unsigned StreamRange(const uint4 w0, const uint4 w1, unsigned& begin) {
+    begin = 0u;
+    if (w0.x == kWorkEnd || (w0.w & (kItemFull | kItemEmpty)) != 0u) {
+        return 0u;
+    }
+    const unsigned chunk = w1.z & 0xFFFFu, nch = max(w1.z >> 16, 1u);
+    const unsigned q = w0.y / nch, r = w0.y % nch;
+    begin = chunk * q + chunk * r / nch;
+    return (chunk + 1u) * q + (chunk + 1u) * r / nch - begin;
+}
+
+// One block: an exclusive prefix over the descriptors' record counts (each rounded up to an even
+// count: 128-B range starts), the offsets into the descriptors' w1.x and their counts into w1.y (a
+// trace block then needs no division before its first loads), the total into *stream_count.
+__global__ __launch_bounds__(kPlanBlock) void StreamPlanKernel(uint4* work, unsigned descs,
+                                                               unsigned long long* stream_count) {
+    __shared__ unsigned long long sums[kPlanBlock];
+    const unsigned tid = threadIdx.x;
+    const unsigned per = (descs + kPlanBlock - 1u) / kPlanBlock;
+    const unsigned d_lo = min(tid * per, descs), d_hi = min(d_lo + per, descs);
+    auto owned = [&](unsigned d) -> unsigned {  // records descriptor d adds to the stream
+        const uint4 w0 = work[2 * d];
+        if (w0.x == kWorkEnd || w0.x % kParts != 0u) {
+            return 0u;
+        }
+        unsigned begin;
+        const unsigned n = StreamRange(w0, work[2 * d + 1], begin);
+        return (n + 1u) & ~1u;
+    };
+    unsigned long long mine = 0ull;
+    for (unsigned d = d_lo; d < d_hi; ++d) {
+        mine += owned(d);
+    }
+    sums[tid] = mine;
+    __syncthreads();
+    for (unsigned o = 1u; o < kPlanBlock; o <<= 1) {
+        const unsigned long long v = tid >= o ? sums[tid - o] : 0ull;
+        __syncthreads();
+        sums[tid] += v;
+        __syncthreads();
+    }
+    if (tid == kPlanBlock - 1) {
+        *stream_count = sums[tid];
+    }
+    // (offsets past 2^32 records: far over the cap, the stream is not built and no trace reads them)
+    unsigned long long at = sums[tid] - mine;
+    for (unsigned d = d_lo; d < d_hi; ++d) {
+        const uint4 w0 = work[2 * d];
+        if (w0.x == kWorkEnd) {
+            work[2 * d + 1] = make_uint4(0u, 0u, 0u, 0u);  // (an end mark is read as a whole: TraceCullKernel)
+            continue;
+        }
+        unsigned begin;
+        work[2 * d + 1].y = StreamRange(w0, work[2 * d + 1], begin);  // every part its own count
+        if (w0.x % kParts == 0u) {
+            const unsigned n = owned(d);
+            work[2 * d + 1].x = n != 0u ? static_cast<unsigned>(at) : 0u;
+            at += n;
+        }
+    }
+    __syncthreads();  // the first parts' offsets are written (one block: visible after the barrier)
+    for (unsigned d = d_lo; d < d_hi; ++d) {
+        const uint4 w0 = work[2 * d];
+        const unsigned part = w0.x % kParts;
+        if (w0.x != kWorkEnd && part != 0u) {
+            const unsigned nch = max(work[2 * d + 1].z >> 16, 1u);
+            work[2 * d + 1].x = work[2 * (d - part * nch) + 1].x;
+        }
+    }
+}
+
+// Block d copies descriptor d's records (a tile's first part only) into its stream range; the pad
+// record of an odd range is a copy of the range's first (no trace reads it).
+__global__ __launch_bounds__(kPackBlock) void PackStreamKernel(const uint4* __restrict__ work,
+                                                               const unsigned* __restrict__ lists,
+                                                               const unsigned* __restrict__ large_list,
+                                                               const CullRecord* __restrict__ cull,
+                                                               CullRecord* __restrict__ records, unsigned capacity) {
+    const unsigned d = blockIdx.x;
+    const uint4 w0 = work[2 * d];
+    if (w0.x == kWorkEnd || w0.x % kParts != 0u) {
+        return;
+    }
+    const uint4 w1 = work[2 * d + 1];
+    unsigned begin;
+    const unsigned n = StreamRange(w0, w1, begin);
+    const unsigned* list = lists + static_cast<size_t>(w0.x / kParts) * capacity;
+    const unsigned count1 = w0.z;
+    CullRecord* out = records + w1.x;
+    for (unsigned v = threadIdx.x; v < n + (n & 1u); v += kPackBlock) {
+        const unsigned vv = begin + (v < n ? v : 0u);
+        out[v] = cull[vv < count1 ? list[vv] : large_list[vv - count1]];
+    }
+}
+}  // namespace
+
+hipError_t LaunchStreamPlan(const CullSetup& s, hipStream_t stream) {
+    hipLaunchKernelGGL(StreamPlanKernel, dim3(1), dim3(kPlanBlock), 0, stream, static_cast<uint4*>(s.work), s.descs,
+                       s.stream_count);
+    return hipGetLastError();
+}
+
+hipError_t LaunchStreamPack(const CullSetup& s, void* records, hipStream_t stream) {
+    if (records == nullptr || s.descs == 0u) {
+        return hipErrorInvalidValue;
+    }
+    hipLaunchKernelGGL(PackStreamKernel, dim3(s.descs), dim3(kPackBlock), 0, stream, static_cast<const uint4*>(s.work),
+                       s.lists, s.large_list, static_cast<const CullRecord*>(s.cull), static_cast<CullRecord*>(records),
+                       s.capacity);
+    return hipGetLastError();
+}
+
 namespace {
 // The two launches of a frame set on the shared setup: tile facts, trace.
 template <class TB, class BB>
 void LaunchSharedStages(const TB& tb, const BB& bb, unsigned z, unsigned gx, unsigned gy, bool recompute,
-                        unsigned descs, hipStream_t stream, const StageEvents& ev) {
+                        bool streamed, unsigned descs, hipStream_t stream, const StageEvents& ev) {
     Launch(TileInfoKernel<BB, true>, dim3(gx, (gy + kInfoTiles - 1) / kInfoTiles, z), dim3(kBinThreads), stream,
            ev.bin_begin, ev.bin_end, bb);
     if (recompute) {
         Launch(TraceCullKernel<TB, true, true>, dim3(descs, 1, z), dim3(kWave * kCullWaves), stream, ev.begin, ev.end, tb);
+    } else if (streamed) {
+        Launch(TraceCullKernel<TB, false, true, true>, dim3(descs, 1, z), dim3(kWave * kCullWaves), stream, ev.begin,
+               ev.end, tb);
     } else {
         Launch(TraceCullKernel<TB, false, true>, dim3(descs, 1, z), dim3(kWave * kCullWaves), stream, ev.begin, ev.end, tb);
     }
@@ -4971,6 +5142,7 @@ hipError_t LaunchSharedCullFrames(const CullFrame* frames, std::size_t count, co
         p.bin_lists = setup.lists;
         p.large_list = setup.large_list;
         p.bin_capacity = setup.capacity;
+        p.stream = static_cast<const CullRecord*>(setup.stream);
         BinParams& b = bp[i];
         b = BinParams{};
         b.offsets = p.offsets;
@@ -4987,8 +5159,9 @@ hipError_t LaunchSharedCullFrames(const CullFrame* frames, std::size_t count, co
     }
     const unsigned z = static_cast<unsigned>(count);
     const unsigned gx = static_cast<unsigned>(tp[0].tiles_x), gy = tp[0].tiles / gx;
+    const bool streamed = setup.stream != nullptr && !setup.recompute;
     if (!use_table) {
-        LaunchSharedStages(tb, bb, z, gx, gy, setup.recompute, setup.descs, stream, ev);
+        LaunchSharedStages(tb, bb, z, gx, gy, setup.recompute, streamed, setup.descs, stream, ev);
         return hipGetLastError();
     }
     if (table->host_device != nullptr) {
@@ -5010,7 +5183,7 @@ hipError_t LaunchSharedCullFrames(const CullFrame* frames, std::size_t count, co
     unsigned char* dev = static_cast<unsigned char*>(table->device);
     const BinTable bt{(ConstantPtr<BinParams>)(dev + lay.bin)};
     const TraceTable tt{(ConstantPtr<TraceParams>)(dev + lay.trace)};
-    LaunchSharedStages(tt, bt, z, gx, gy, setup.recompute, setup.descs, stream, ev);
+    LaunchSharedStages(tt, bt, z, gx, gy, setup.recompute, streamed, setup.descs, stream, ev);
     return hipGetLastError();
 }
 

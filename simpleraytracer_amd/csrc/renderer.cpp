@@ -170,6 +170,7 @@ DeviceScene::~DeviceScene() {
     (void)hipFree(m_svertices);
     (void)hipFree(m_block_ext);
     (void)hipFree(m_setup);
+    (void)hipFree(m_stream);
     for (CullArena& a : m_arenas) {
         (void)hipFree(a.work);
     }
@@ -706,6 +707,33 @@ int RecordModeFromEnv() {
     }
     throw std::runtime_error("SRT_TRACE_RECORDS must be stored, recompute or auto, got '" + v + "'");
 }
+
+// SRT_TRACE_STREAM = 1 (default) | 0, read per call (like SRT_SETUP): whether the shared setup builds
+// its record stream and the traces read it; 0 keeps the indexed path (records through the lists).
+bool TraceStreamFromEnv() {
+    const char* e = std::getenv("SRT_TRACE_STREAM");
+    const std::string v = e == nullptr || *e == '\0' ? "1" : e;
+    if (v != "1" && v != "0") {
+        throw std::runtime_error("SRT_TRACE_STREAM must be 1 or 0, got '" + v + "'");
+    }
+    return v == "1";
+}
+
+// SRT_TRACE_STREAM_CAP (tests only): the longest record stream, in records, instead of
+// kStreamCapRecords -- forces the indexed fallback at small sizes, as SRT_CULL_BIN_CAP forces list overflow.
+std::size_t StreamCapFromEnv() {
+    const char* e = std::getenv("SRT_TRACE_STREAM_CAP");
+    if (e == nullptr || *e == '\0') {
+        return kStreamCapRecords;
+    }
+    char* end = nullptr;
+    const unsigned long long v = std::strtoull(e, &end, 10);
+    if (end == e || *end != '\0' || *e == '-' || v > kStreamCapRecords) {
+        throw std::runtime_error("SRT_TRACE_STREAM_CAP must be a record count up to " +
+                                 std::to_string(kStreamCapRecords) + ", got '" + std::string(e) + "'");
+    }
+    return static_cast<std::size_t>(v);
+}
 }  // namespace
 
 void DeviceScene::SetRecordMode(int mode) {
@@ -747,9 +775,11 @@ void DeviceScene::LogSetupStats() const {
     if (e == nullptr || *e == '\0' || std::strcmp(e, "0") == 0) {
         return;
     }
-    std::fprintf(stderr, "srt setup: scene %p builds %llu shared_frames %llu per_frame_frames %llu\n",
+    std::fprintf(stderr,
+                 "srt setup: scene %p builds %llu shared_frames %llu per_frame_frames %llu stream_frames %llu "
+                 "stream_records %llu\n",
                  static_cast<const void*>(this), m_setup_stats.builds, m_setup_stats.shared_frames,
-                 m_setup_stats.per_frame_frames);
+                 m_setup_stats.per_frame_frames, m_setup_stats.stream_frames, m_setup_stats.stream_records);
     std::fflush(stderr);
 }
 
@@ -788,6 +818,7 @@ void DeviceScene::TraceShared(const float* const* d_offsets, float* const* d_rgb
         table->pending = true;  // (LaunchSharedCullFrames recorded `uploaded` after the upload)
     }
     m_setup_stats.shared_frames += frames;
+    m_setup_stats.stream_frames += setup.stream != nullptr ? frames : 0;
     LogSetupStats();
     RecordOrder(stream);
 }
@@ -810,18 +841,49 @@ CullSetup DeviceScene::EnsureSetup(unsigned descs, hipStream_t stream) const {
         m_setup_bytes = bytes;
         m_setup_pending = true;
     }
-    const CullSetup setup = CullSetupLayout(m_setup, m_n, m_width, m_height, descs, recompute);
-    const SetupKey key{m_width, m_height, setup.capacity, setup.descs, setup.min_chunk, setup.recompute};
+    CullSetup setup = CullSetupLayout(m_setup, m_n, m_width, m_height, descs, recompute);
+    // The record stream is for stored records; its cap is part of the key (a test lowers it).
+    const bool want_stream = TraceStreamFromEnv() && !recompute;
+    const SetupKey key{m_width,         m_height,    setup.capacity, setup.descs,
+                       setup.min_chunk, setup.recompute, want_stream,    want_stream ? StreamCapFromEnv() : 0};
     const SetupKey& k = m_setup_key;
     if (m_setup_pending || key.width != k.width || key.height != k.height || key.capacity != k.capacity ||
-        key.descs != k.descs || key.min_chunk != k.min_chunk || key.recompute != k.recompute) {
+        key.descs != k.descs || key.min_chunk != k.min_chunk || key.recompute != k.recompute ||
+        key.stream != k.stream || key.stream_cap != k.stream_cap) {
         m_setup_pending = true;  // (a failed build leaves none)
+        m_stream_on = false;
+        m_stream_records = 0;
         HipCheck(LaunchCullSetup(setup, m_n, m_frame, m_width, m_height, m_order, m_svertices, stream),
                  "cull setup launch");
+        if (want_stream) {
+            // The stream's length is known only from the built plan: one host read per build (never
+            // per frame). Over the cap, this setup's frames keep the indexed path.
+            unsigned long long records = 0;
+            HipCheck(LaunchStreamPlan(setup, stream), "record stream plan launch");
+            HipCheck(hipMemcpyAsync(&records, setup.stream_count, sizeof(records), hipMemcpyDeviceToHost, stream),
+                     "hipMemcpyAsync(record stream length)");
+            HipCheck(hipStreamSynchronize(stream), "hipStreamSynchronize(record stream length)");
+            if (records <= key.stream_cap) {
+                const std::size_t need = std::max<std::size_t>(static_cast<std::size_t>(records), 2);
+                if (need > m_stream_capacity) {
+                    // (earlier readers of the old stream ran before this stream's end, as for m_setup)
+                    (void)hipFree(m_stream);
+                    m_stream = nullptr;
+                    m_stream_capacity = 0;
+                    m_stream = DeviceAlloc<unsigned char>(need * kCullRecordBytes, "hipMalloc(record stream)");
+                    m_stream_capacity = need;
+                }
+                HipCheck(LaunchStreamPack(setup, m_stream, stream), "record stream pack launch");
+                m_stream_on = true;
+                m_stream_records = static_cast<std::size_t>(records);
+            }
+        }
         m_setup_key = key;
         m_setup_pending = false;
         ++m_setup_stats.builds;
+        m_setup_stats.stream_records = m_stream_records;
     }
+    setup.stream = m_stream_on ? m_stream : nullptr;
     return setup;
 }
 

@@ -185,6 +185,10 @@ public:
         unsigned long long builds = 0;
         unsigned long long shared_frames = 0;
         unsigned long long per_frame_frames = 0;
+        // Of shared_frames, those whose trace read the setup's record stream (env SRT_TRACE_STREAM,
+        // read per call; default 1), and the records of the stream now standing (0: none).
+        unsigned long long stream_frames = 0;
+        unsigned long long stream_records = 0;
     };
     SetupStats setup_stats() const { return m_setup_stats; }
 
@@ -217,9 +221,17 @@ private:
         std::size_t width = 0, height = 0;
         unsigned capacity = 0, descs = 0, min_chunk = 0;
         bool recompute = false;
+        bool stream = false;         // the record stream was asked for (SRT_TRACE_STREAM, stored records)
+        std::size_t stream_cap = 0;  // ... up to this many records (a longer one: the indexed path)
     };
     mutable unsigned char* m_setup = nullptr;
     mutable std::size_t m_setup_bytes = 0;
+    // The setup's record stream (render.h): sized from the built plan, so an allocation of its own;
+    // m_stream_on: the standing setup has one (m_stream_records records of it are in use).
+    mutable unsigned char* m_stream = nullptr;
+    mutable std::size_t m_stream_capacity = 0;  // records allocated
+    mutable std::size_t m_stream_records = 0;
+    mutable bool m_stream_on = false;
     mutable bool m_setup_pending = true;
     mutable SetupKey m_setup_key{};
     mutable SetupStats m_setup_stats{};
