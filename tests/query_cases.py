@@ -16,10 +16,9 @@ OUT_OF_RANGE = np.array([-3.25, np.nextafter(np.float32(1), np.float32(2)), 4.5,
                         np.float32)
 
 
-def write_scene_q(path):
-    """Scene Q: a soup in view, triangles behind the eye, a point and a collinear triangle, and two
-    frame-covering triangles (the large list)."""
-    rng = np.random.default_rng(11)
+def scene_q_vertices(rng):
+    """Scene Q's geometry, (N_SOUP + 24, 3, 3) float32, drawn from rng (default_rng(11) for Q itself;
+    scale_cases' scene S goes on drawing its albedo from the same generator)."""
     c = rng.uniform([-1.2, -0.9, 2.0], [1.2, 0.9, 4.0], (N_SOUP, 3))
     soup = c[:, None, :] + rng.uniform(-0.15, 0.15, (N_SOUP, 3, 3))
     behind = rng.uniform([-1, -1, -6], [1, 1, -0.5], (20, 3, 3))
@@ -28,7 +27,13 @@ def write_scene_q(path):
     cover = np.array([[[-40, -40, 9 + i], [-0.05 * i, -40, 9 + i], [-0.05 * i, 40, 9 + i]] for i in range(2)], np.float64)
     v = np.concatenate([soup, behind, point, line, cover]).astype(np.float32)
     assert v.shape == (N_SOUP + 24, 3, 3)
-    return write_custom_scene(path, v.reshape(-1, 9))
+    return v
+
+
+def write_scene_q(path):
+    """Scene Q: a soup in view, triangles behind the eye, a point and a collinear triangle, and two
+    frame-covering triangles (the large list)."""
+    return write_custom_scene(path, scene_q_vertices(np.random.default_rng(11)).reshape(-1, 9))
 
 
 def boundary_values(extent: int, step: int) -> np.ndarray:
