@@ -203,6 +203,19 @@ _SIGNATURES = {
                                      ctypes.c_void_p, ctypes.c_void_p, _SZ, _SZ, ctypes.c_float, ctypes.c_void_p,
                                      ctypes.c_void_p, ctypes.c_float]),
     "rtlProjectionHost": (ctypes.c_int, [ctypes.POINTER(ctypes.c_float), _SZ, _SZ, ctypes.POINTER(ctypes.c_float)]),
+    # include/srt_omni.h: omni-light shadow masks (origin, camera10, q: ctypes float arrays)
+    "rtoLightCreate": (ctypes.c_void_p, [ctypes.c_char_p, ctypes.c_int, ctypes.POINTER(ctypes.c_float)]),
+    "rtoLightRelease": (None, [ctypes.c_void_p]),
+    "rtoLightPrepareAsync": (ctypes.c_int, [ctypes.c_void_p, _SZ, ctypes.c_void_p]),
+    "rtoLightFace": (ctypes.c_void_p, [ctypes.c_void_p, ctypes.c_int]),
+    "rtoShadowAsync": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, _SZ, _SZ,
+                                      ctypes.c_float, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_float,
+                                      ctypes.c_void_p]),
+    "rtoShadowHost": (ctypes.c_int, [ctypes.c_char_p, _SZ, _SZ, ctypes.POINTER(ctypes.c_float), _SZ, ctypes.c_void_p,
+                                     ctypes.c_void_p, _SZ, _SZ, ctypes.c_float, ctypes.c_void_p, ctypes.c_void_p,
+                                     ctypes.c_void_p, ctypes.c_float]),
+    "rtoFaceCameraHost": (ctypes.c_int, [ctypes.POINTER(ctypes.c_float), ctypes.c_int, ctypes.POINTER(ctypes.c_float)]),
+    "rtoFaceOfHost": (ctypes.c_int, [ctypes.POINTER(ctypes.c_float)]),
     # include/srt_layers.h: depth layers and their over-composite
     "rtkLayersAsync": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, _SZ, _SZ, ctypes.c_void_p, ctypes.c_void_p,
                                       ctypes.c_void_p, ctypes.c_void_p]),

@@ -2,6 +2,7 @@
 
 #include "gbuffer_math.h"
 #include "layers_math.h"
+#include "omni_math.h"
 #include "samples_math.h"
 #include "screen_box.h"
 #include "shadow_math.h"
@@ -458,6 +459,98 @@ void HostShadow(const Scene& scene, std::size_t width, std::size_t height, const
             }
         }
         mask[i] = cls;
+        if (rgba != nullptr) {
+            std::copy(out, out + 4, rgba + 4 * i);
+        }
+    });
+}
+
+Camera OmniFaceCameraOf(const float origin[3], int face) {
+    float c10[10];
+    OmniFaceCamera(origin, face, c10);
+    Camera c{};
+    std::copy(c10, c10 + 3, c.eye);
+    std::copy(c10 + 3, c10 + 6, c.lookat);
+    std::copy(c10 + 6, c10 + 9, c.up);
+    c.vfov_deg = c10[9];
+    return c;
+}
+
+void HostOmniShadow(const Scene& scene, std::size_t width, std::size_t height, const float origin[3],
+                    std::size_t face_size, const float* offsets, const int* ids, std::size_t row_begin,
+                    std::size_t row_count, float bias, unsigned char* mask, unsigned char* face, float* rgba, float dim) {
+    if (width == 0 || height == 0 || face_size == 0) {
+        throw std::runtime_error("Host omni shadow: frame dimensions must be non-zero");
+    }
+    if (row_begin > height || row_count > height - row_begin) {
+        throw std::runtime_error("Host omni shadow: row band outside the frame");
+    }
+    const Frame f = MakeFrame(scene.camera, width, height);
+    const std::size_t n = scene.triangle_count();
+    Frame lf[kOmniFaces];
+    float rows[kOmniFaces][9];
+    std::vector<Rec> lrecs(kOmniFaces * n);  // every triangle's record under every face frame
+    for (int k = 0; k < kOmniFaces; ++k) {
+        lf[k] = MakeFrame(OmniFaceCameraOf(origin, k), face_size, face_size);
+        ShadowProjectionRows(lf[k].base, lf[k].du, lf[k].dv, rows[k]);
+        Rec* out = lrecs.data() + static_cast<std::size_t>(k) * n;
+        ParallelFor(n, 1024, [&](std::size_t i) { out[i] = MakeRecord(scene.vertices.data() + 9 * i, lf[k]); });
+    }
+    const float wf = static_cast<float>(width), hf = static_cast<float>(height);
+    const float inf = std::numeric_limits<float>::infinity();
+    ParallelFor(row_count * width, 64, [&](std::size_t i) {
+        const std::size_t x = i % width, y = row_begin + i / width;
+        const int id = ids[i];
+        const float fx = (static_cast<float>(x) + offsets[2 * i]) / wf;
+        const float fy = (static_cast<float>(y) + offsets[2 * i + 1]) / hf;
+        const bool surface = id >= 0 && static_cast<std::size_t>(id) < n;
+        unsigned char cls = kShadowNoSurface;
+        unsigned char fc = kOmniNoFace;
+        float out[4] = {scene.background[0], scene.background[1], scene.background[2], -1.f};
+        if (surface) {
+            const Rec r = MakeRecord(scene.vertices.data() + 9 * static_cast<std::size_t>(id), f);
+            const float t = ShadowDepth(r.c, r.vol, fx, fy);
+            float q[3];
+            ShadowOffset(f.origin, f.base, f.du, f.dv, fx, fy, t, lf[0].origin, q);
+            fc = static_cast<unsigned char>(OmniFace(q));
+            const ShadowPoint sp = ShadowProjectOffset(q, rows[fc], bias);
+            cls = kShadowOutside;
+            if (sp.inside) {
+                const Rec* recs = lrecs.data() + static_cast<std::size_t>(fc) * n;
+                float best = inf;
+                int lid = -1;
+                for (std::size_t k = 0; k < n; ++k) {  // ascending ids: strict < keeps the lowest on ties
+                    const float* c = recs[k].c;
+                    const float eA = std::fma(sp.gy, c[2], std::fma(sp.gx, c[1], c[0]));
+                    const float eB = std::fma(sp.gy, c[5], std::fma(sp.gx, c[4], c[3]));
+                    const float eC = std::fma(sp.gy, c[8], std::fma(sp.gx, c[7], c[6]));
+                    if (eA >= 0.f && eB >= 0.f && eC >= 0.f) {
+                        const float det = (eA + eB) + eC;
+                        if (det > 0.f) {
+                            const float tt = recs[k].vol / det;
+                            if (tt < best) {
+                                best = tt;
+                                lid = static_cast<int>(k);
+                            }
+                        }
+                    }
+                }
+                cls = ShadowClass(id, lid, best, sp.thr);
+            }
+            if (rgba != nullptr) {
+                const float* a = scene.albedo.data() + 3 * static_cast<std::size_t>(id);
+                const ResolveRgb c = ResolveShadeHit(f.base, f.du, f.dv, fx, fy, r.n[0], r.n[1], r.n[2], r.n[3], a[0], a[1], a[2]);
+                const float k = ShadowScale(cls, dim);
+                out[0] = c.r * k;
+                out[1] = c.g * k;
+                out[2] = c.b * k;
+                out[3] = static_cast<float>(id);
+            }
+        }
+        mask[i] = cls;
+        if (face != nullptr) {
+            face[i] = fc;
+        }
         if (rgba != nullptr) {
             std::copy(out, out + 4, rgba + 4 * i);
         }

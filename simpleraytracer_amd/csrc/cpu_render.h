@@ -69,6 +69,15 @@ void HostComposite(const Scene& scene, std::size_t width, std::size_t height, co
 void HostShadow(const Scene& scene, std::size_t width, std::size_t height, const Camera& light_camera,
                 std::size_t light_width, std::size_t light_height, const float* offsets, const int* ids,
                 std::size_t row_begin, std::size_t row_count, float bias, unsigned char* mask, float* rgba, float dim);
+// The omni-light shadow mask (omni_math.h; the host answer of render.h LaunchOmniShadow): HostShadow
+// under the point light at `origin`, six cube faces of face_size x face_size; `face` (may be null)
+// receives the face each pixel selected, 255 for a class-3 pixel.
+void HostOmniShadow(const Scene& scene, std::size_t width, std::size_t height, const float origin[3],
+                    std::size_t face_size, const float* offsets, const int* ids, std::size_t row_begin,
+                    std::size_t row_count, float bias, unsigned char* mask, unsigned char* face, float* rgba, float dim);
+// Face `face` (0 .. 5) of the light at `origin` as a camera (omni_math.h OmniFaceCamera).
+Camera OmniFaceCameraOf(const float origin[3], int face);
+
 // The light frame's projection rows (px, py, pz) as HostShadow and LaunchShadow compute them.
 void HostShadowRows(const Camera& light_camera, std::size_t light_width, std::size_t light_height, float rows[9]);
 

@@ -452,6 +452,17 @@ hipError_t LaunchShadow(const float* d_vertices, const float* d_shade, std::uint
                         const float background[3], const ShadowLight& light, const ShadowArgs& args,
                         hipStream_t stream);
 
+// Omni-light shadow mask (render.hip OmniShadowKernel; omni_math.h; DESIGN.md section 2 "Omni
+// shadow"): LaunchShadow's class byte under a point light given as six cube-face frames of one
+// size, each a ShadowLight. Every pixel selects its face from q = surface point - light (OmniFace)
+// and runs LaunchShadow's test in that face's frame only: bit for bit LaunchShadow's class for the
+// selected face. args: LaunchShadow's; d_face (device, row_count x width bytes, or null): the
+// selected face, kOmniNoFace for a class-3 pixel. The six faces share one origin, one frame size and
+// one record source (all with a setup of the same kind, or all without). One launch; no rows: none.
+hipError_t LaunchOmniShadow(const float* d_vertices, const float* d_shade, std::uint64_t n, const Frame& frame,
+                            const float background[3], const ShadowLight faces[6], const ShadowArgs& args,
+                            unsigned char* d_face, hipStream_t stream);
+
 // G-buffer (render.hip GBufferKernel): the surface attributes of (image position, triangle id)
 // pairs of the frame -- depth, barycentrics, normal + shading cosine, albedo + id (gbuffer_math.h;
 // DESIGN.md section 2 "Surface attributes") -- from hit ids, a deferred pass like LaunchShade with

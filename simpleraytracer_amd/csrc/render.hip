@@ -8,6 +8,7 @@
 #include "layers_math.h"
 #include "samples_math.h"
 #include "screen_box.h"
+#include "omni_math.h"
 #include "shadow_math.h"
 #include "tile_lookup.h"
 
@@ -4016,6 +4017,245 @@ __global__ __launch_bounds__(kShadowThreads) void ShadowKernel(const ShadowParam
 }
 
 // ---------------------------------------------------------------------------------------
+// Omni-light shadow mask (render.h LaunchOmniShadow; DESIGN.md section 5 "Omni shadow"): ShadowKernel
+// under a point light given as six cube-face frames. The pixel's facts as ShadowKernel computes them
+// (ComputeEdges on the view scene's vertices, the traces' bits), q = surface point - light, the face
+// OmniFace(q) picks, and then ShadowKernel's scan against that face's setup alone: the own
+// triangle's (t_id, id) first, the bound min((thr, below every id), (t_id, id)), the lanes striding
+// the tile's list then the large list (every record of the face where it has no usable list), the
+// group leaving at the end of the first round in which a lane took a candidate.
+// The face is a per-pixel value, so what the scan reads of a face -- OmniFaceParams, 168 B, not a
+// TraceParams -- is read through a per-lane index into the six entries of the argument segment
+// (6 x 168 B + the view's part, 1168 B: under 4 KB, no table, no upload): vector loads from constant
+// memory, no scratch. A wave whose pixels agree on the face (most do: faces are large on screen)
+// reads one address. No LDS, no atomics, plain vector stores. Lanes x candidates per round,
+// measured at C3 under a light inside and a light outside the soup with faces of 512, 1024 and 2048
+// (2 ... 32 lanes, 1 / 2 / 4 candidates: DESIGN.md; profiles/omni/): started from ShadowKernel's
+// 2 x 2, on which 16 x 2 saves 5 to 27 % of the time on all six -- a cube face of a few hundred pixels holds the
+// whole scene, so lists are long and the wider rounds find the first occluder in fewer of them, the
+// spot shadow's own finding at a 512 x 512 light frame. 16 x 2, QueryKernel's shape, is the fastest
+// or within 6 % of it on every one. SRT_OMNI_LANES, SRT_OMNI_AHEAD: measurement builds.
+// ---------------------------------------------------------------------------------------
+#ifndef SRT_OMNI_LANES
+#define SRT_OMNI_LANES 16
+#endif
+constexpr int kOmniLanes = SRT_OMNI_LANES;  // lanes per pixel (a divisor of the wave)
+#ifndef SRT_OMNI_AHEAD
+#define SRT_OMNI_AHEAD 2
+#endif
+constexpr int kOmniAhead = SRT_OMNI_AHEAD;  // candidates per lane and round
+constexpr int kOmniThreads = 256;
+constexpr int kOmniBlock = kOmniThreads / kOmniLanes;  // pixels per block
+static_assert(kOmniLanes >= 2 && kWave % kOmniLanes == 0, "a pixel's lanes share a wave");
+struct OmniFaceParams {
+    const CullRecord* cull;        // stored records by position (RC = false)
+    const float* svertices;        // vertices by position (RC = true)
+    const unsigned* rank;          // the face scene's record id -> position
+    const TileInfo* tile_info;     // null: no setup, every pixel of the face streams
+    const unsigned* bin_lists;
+    const unsigned* bin_counts;
+    const unsigned* large_list;
+    unsigned bin_capacity;
+    unsigned tiles;
+    int tiles_x, tiles_y;
+    unsigned stream_end;           // records of a streamed pixel: positions [0, stream_end)
+    float wf, hf;                  // the face frame's
+    float base[3], du[3], dv[3];
+    float rows[9];                 // the face's projection rows (px, py, pz)
+    float origin[3];
+};
+struct OmniParams {
+    OmniFaceParams face[kOmniFaces];
+    const float* __restrict__ vertices;  // the view scene's, by id
+    const float4* __restrict__ shade;    // the view scene's shading table
+    const float2* __restrict__ offsets;  // band-local
+    const int* __restrict__ ids;         // band-local
+    unsigned char* __restrict__ mask;
+    unsigned char* __restrict__ face_out;  // null: not stored
+    F4* __restrict__ rgba;                 // null: not stored
+    unsigned n;  // triangles of every scene
+    unsigned width;
+    unsigned row_begin;
+    unsigned pixels;  // of the band
+    float wf, hf;     // the view frame's
+    float eye[3], base[3], du[3], dv[3], bg[3];
+    float light[3];
+    float bias, dim;
+};
+static_assert(sizeof(OmniFaceParams) == 168 && sizeof(OmniParams) == 1168, "the faces travel in the kernel-argument segment (< 4 KB)");
+
+__device__ __forceinline__ bool OmniGroupAny(bool mine) {
+    const unsigned long long b = __ballot(mine);
+    if constexpr (kOmniLanes == kWave) {
+        return b != 0ull;
+    } else {
+        const unsigned first = (threadIdx.x & (kWave - 1)) & ~static_cast<unsigned>(kOmniLanes - 1);
+        return ((b >> first) & ((1ull << kOmniLanes) - 1ull)) != 0ull;
+    }
+}
+
+// A face's candidate record by position, as TraceRecords<RC> gives a trace its own (the screen box,
+// which the exact test does not read, left out).
+template <bool RC>
+struct OmniRecords {
+    struct Raw {
+        float4 a, b, x;
+    };
+    static __device__ __forceinline__ Raw Load(const OmniFaceParams& f, unsigned, unsigned pos) {
+        const float4* at = reinterpret_cast<const float4*>(f.cull + pos);
+        return Raw{at[0], at[1], at[2]};
+    }
+    static __device__ __forceinline__ Raw Make(const OmniFaceParams&, unsigned, const Raw& r) { return r; }
+};
+template <>
+struct OmniRecords<true> {
+    struct Raw {
+        float v[9];
+        unsigned id;
+    };
+    using Made = OmniRecords<false>::Raw;
+    static __device__ __forceinline__ Raw Load(const OmniFaceParams& f, unsigned n, unsigned pos) {
+        Raw r;
+        const bool real = pos < n;
+        const float4* v = reinterpret_cast<const float4*>(f.svertices + static_cast<size_t>(kSpatialStride) * (real ? pos : 0u));
+        const float4 v0 = v[0], v1 = v[1], v2 = v[2];
+        r.v[0] = v0.x, r.v[1] = v0.y, r.v[2] = v0.z, r.v[3] = v0.w;
+        r.v[4] = v1.x, r.v[5] = v1.y, r.v[6] = v1.z, r.v[7] = v1.w;
+        r.v[8] = v2.x;
+        r.id = real ? __float_as_uint(v2.y) : pos;
+        return r;
+    }
+    static __device__ __forceinline__ Made Make(const OmniFaceParams& f, unsigned n, const Raw& r) {
+        float c[9], vol;
+        ComputeEdges(f.origin, f.base, f.du, f.dv, r.v, r.id < n, c, vol);
+        return Made{make_float4(c[0], c[1], c[2], c[3]), make_float4(c[4], c[5], c[6], c[7]),
+                    make_float4(c[8], vol, __uint_as_float(r.id), 0.f)};
+    }
+};
+
+template <bool RC>
+__global__ __launch_bounds__(kOmniThreads) void OmniShadowKernel(const OmniParams q) {
+    using Recs = OmniRecords<RC>;
+    const unsigned lane = threadIdx.x & (kOmniLanes - 1);
+    const unsigned pixel = blockIdx.x * kOmniBlock + threadIdx.x / kOmniLanes;
+    if (pixel >= q.pixels) {
+        return;
+    }
+    const int code = q.ids[pixel];
+    const float2 o = q.offsets[pixel];
+    const unsigned y = pixel / q.width, x = pixel - y * q.width;
+    const float fx = (static_cast<float>(x) + o.x) / q.wf;
+    const float fy = (static_cast<float>(q.row_begin + y) + o.y) / q.hf;
+    const bool surface = static_cast<unsigned>(code) < q.n;
+    unsigned char cls = kShadowNoSurface;
+    unsigned char face = kOmniNoFace;
+    ShadowPoint sp{false, 0.f, 0.f, 0.f};
+    if (surface) {
+        const float* at = q.vertices + 9ull * static_cast<unsigned>(code);
+        float v[9], c[9], vol;
+#pragma unroll
+        for (int j = 0; j < 9; ++j) {
+            v[j] = at[j];
+        }
+        ComputeEdges(q.eye, q.base, q.du, q.dv, v, true, c, vol);
+        const float t = ShadowDepth(c, vol, fx, fy);
+        float off[3];
+        ShadowOffset(q.eye, q.base, q.du, q.dv, fx, fy, t, q.light, off);
+        face = static_cast<unsigned char>(OmniFace(off));
+        sp = ShadowProjectOffset(off, q.face[face].rows, q.bias);
+        cls = kShadowOutside;
+    }
+    // The shaded pixel, before the scan: the view frame's vectors need not stay live across it.
+    F4 out{q.bg[0], q.bg[1], q.bg[2], -1.f};
+    if (q.rgba != nullptr && surface) {
+        const float4* sr = q.shade + 2ull * static_cast<unsigned>(code);
+        const float4 nr = sr[0], al = sr[1];
+        const ResolveRgb c = ResolveShadeHit(q.base, q.du, q.dv, fx, fy, nr.x, nr.y, nr.z, nr.w, al.x, al.y, al.z);
+        out = F4{c.r, c.g, c.b, static_cast<float>(code)};
+    }
+    if (sp.inside) {
+        const OmniFaceParams& f = q.face[face];
+        Rays<1> s;
+        s.fx[0] = sp.gx;
+        s.fy[0] = sp.gy;
+        s.bt[0] = __builtin_inff();
+        s.bi[0] = -1;
+        int col = 0, row = 0;
+        const TileInfo* tile_info = f.tile_info;
+        bool listed = tile_info != nullptr &&
+                      TileOfPosition(sp.gx, sp.gy, f.wf, f.hf, kCullTileCols, kTileRows, f.tiles_x, f.tiles_y, col, row);
+        unsigned cnt = 0u, large = 0u, capacity = 0u;
+        const unsigned* list = nullptr;
+        const unsigned* large_list = nullptr;
+        if (listed) {
+            const unsigned tile = static_cast<unsigned>(row) * static_cast<unsigned>(f.tiles_x) + static_cast<unsigned>(col);
+            const unsigned* counts = f.bin_counts;
+            capacity = f.bin_capacity;
+            cnt = counts[tile];
+            large = counts[f.tiles];
+            list = f.bin_lists + static_cast<size_t>(tile) * capacity;
+            large_list = f.large_list;
+            listed = cnt <= capacity && tile_info[tile].usable != 0u;
+        }
+        const unsigned total = listed ? cnt + large : f.stream_end;
+        auto entry = [&](unsigned k) {
+            if (!listed) {
+                return k;
+            }
+            const unsigned* at = k < cnt ? list + k : large_list + (k - cnt);
+            return *at;
+        };
+        auto test = [&](const typename Recs::Raw& raw) {
+            const auto r = Recs::Make(f, q.n, raw);
+            const Record rec{r.a.x, r.a.y, r.a.z, r.a.w, r.b.x, r.b.y, r.b.z, r.b.w, r.x.x};
+            ExactTestAnyOrder<1, false>(s, rec, r.x.y, static_cast<int>(__float_as_uint(r.x.z)));
+        };
+        // The own triangle under the face's records: (t_id, id), or (+inf, -1) if it does not pass.
+        test(Recs::Load(f, q.n, f.rank[static_cast<unsigned>(code)]));
+        if (sp.thr <= s.bt[0]) {  // the bound: (thr, below every id) or (t_id, id), whichever is lower
+            s.bt[0] = sp.thr;
+            s.bi[0] = static_cast<int>(0x80000000u);
+        }
+        const int bound_id = s.bi[0];
+        bool occluded = false;
+        for (unsigned base = 0u; base < total; base += kOmniAhead * kOmniLanes) {
+            unsigned pos[kOmniAhead];
+            typename Recs::Raw raw[kOmniAhead];
+#pragma unroll
+            for (int a = 0; a < kOmniAhead; ++a) {
+                pos[a] = entry(min(base + a * kOmniLanes + lane, total - 1u));
+            }
+#pragma unroll
+            for (int a = 0; a < kOmniAhead; ++a) {
+                raw[a] = Recs::Load(f, q.n, pos[a]);
+            }
+#pragma unroll
+            for (int a = 0; a < kOmniAhead; ++a) {
+                test(raw[a]);
+            }
+            if (OmniGroupAny(s.bi[0] != bound_id)) {  // a candidate below the bound: an occluder
+                occluded = true;
+                break;
+            }
+        }
+        cls = occluded ? kShadowShadowed : kShadowLit;
+    }
+    if (lane == 0u) {
+        q.mask[pixel] = cls;
+        if (q.face_out != nullptr) {
+            q.face_out[pixel] = face;
+        }
+        if (q.rgba != nullptr) {
+            if (surface) {
+                const float k = ShadowScale(cls, q.dim);
+                out = F4{out.x * k, out.y * k, out.z * k, out.w};
+            }
+            StoreNontemporal(q.rgba + pixel, out);
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------------------
 // BVH variant: primary rays share the eye, so the closest-hit search
 // is a 2-D query over the records' screen boxes. The tree is implicit and 8 wide over the
 // cull records in the scene's spatial (Morton) order -- no sort, no topology arrays; only the
@@ -5405,6 +5645,93 @@ hipError_t LaunchShadow(const float* d_vertices, const float* d_shade, std::uint
         hipLaunchKernelGGL(ShadowKernel<true>, grid, dim3(kShadowThreads), 0, stream, q);
     } else {
         hipLaunchKernelGGL(ShadowKernel<false>, grid, dim3(kShadowThreads), 0, stream, q);
+    }
+    return hipGetLastError();
+}
+
+hipError_t LaunchOmniShadow(const float* d_vertices, const float* d_shade, std::uint64_t n, const Frame& frame,
+                            const float background[3], const ShadowLight faces[6], const ShadowArgs& args,
+                            unsigned char* d_face, hipStream_t stream) {
+    if (args.width == 0 || args.row_count == 0) {
+        return hipSuccess;
+    }
+    const std::size_t pixels = args.width * args.row_count;
+    if (args.offsets == nullptr || args.ids == nullptr || args.mask == nullptr || d_shade == nullptr ||
+        (n != 0 && d_vertices == nullptr) || n > 0x7FFFFFFFull || args.height == 0 || args.height > 0x7FFFFFFFull ||
+        args.row_begin > args.height || args.row_count > args.height - args.row_begin ||
+        args.width > 0xFFFFFFFFull || args.row_count > (0xFFFFFFFFull - kOmniBlock) / args.width ||
+        !(args.bias >= 0.f) || !std::isfinite(args.bias) || !std::isfinite(args.dim)) {
+        return hipErrorInvalidValue;
+    }
+    OmniParams q{};
+    bool recompute = false;
+    for (int k = 0; k < kOmniFaces; ++k) {
+        const ShadowLight& l = faces[k];
+        if ((n != 0 && l.rank == nullptr) || l.svertices == nullptr || l.edges == nullptr ||
+            l.width != faces[0].width || l.height != faces[0].height || (l.setup == nullptr) != (faces[0].setup == nullptr) ||
+            std::memcmp(l.frame.origin, faces[0].frame.origin, sizeof l.frame.origin) != 0 ||
+            (l.setup != nullptr && (l.width == 0 || l.height == 0 || !CullBinnable(l.width, l.height) ||
+                                    l.setup->tiles != CullTiles(l.width, l.height)))) {
+            return hipErrorInvalidValue;
+        }
+        TraceParams p{};
+        int tiles_y = 0;
+        const bool rc = QueryRecords(p, tiles_y, l.setup, n, l.frame, l.width, l.height, l.svertices, l.edges);
+        if (k != 0 && rc != recompute) {
+            return hipErrorInvalidValue;
+        }
+        recompute = rc;
+        OmniFaceParams& f = q.face[k];
+        f.cull = p.cull;
+        f.svertices = p.svertices;
+        f.rank = l.rank;
+        f.tile_info = p.tile_info;
+        f.bin_lists = p.bin_lists;
+        f.bin_counts = p.bin_counts;
+        f.large_list = p.large_list;
+        f.bin_capacity = p.bin_capacity;
+        f.tiles = p.tiles;
+        f.tiles_x = p.tiles_x;
+        f.tiles_y = tiles_y;
+        f.stream_end = n == 0 ? 0u : p.n_pad;
+        f.wf = p.wf;
+        f.hf = p.hf;
+        for (int c = 0; c < 3; ++c) {
+            f.base[c] = l.frame.base[c];
+            f.du[c] = l.frame.du[c];
+            f.dv[c] = l.frame.dv[c];
+            f.origin[c] = l.frame.origin[c];
+        }
+        ShadowProjectionRows(l.frame.base, l.frame.du, l.frame.dv, f.rows);
+    }
+    q.vertices = d_vertices;
+    q.shade = reinterpret_cast<const float4*>(d_shade);
+    q.offsets = reinterpret_cast<const float2*>(args.offsets);
+    q.ids = args.ids;
+    q.mask = args.mask;
+    q.face_out = d_face;
+    q.rgba = reinterpret_cast<F4*>(args.rgba);
+    q.n = static_cast<unsigned>(n);
+    q.width = static_cast<unsigned>(args.width);
+    q.row_begin = static_cast<unsigned>(args.row_begin);
+    q.pixels = static_cast<unsigned>(pixels);
+    q.wf = static_cast<float>(args.width);
+    q.hf = static_cast<float>(args.height);
+    for (int k = 0; k < 3; ++k) {
+        q.eye[k] = frame.origin[k];
+        q.base[k] = frame.base[k];
+        q.du[k] = frame.du[k];
+        q.dv[k] = frame.dv[k];
+        q.bg[k] = background[k];
+        q.light[k] = faces[0].frame.origin[k];
+    }
+    q.bias = args.bias;
+    q.dim = args.dim;
+    const dim3 grid(static_cast<unsigned>((pixels + kOmniBlock - 1) / kOmniBlock));
+    if (recompute) {
+        hipLaunchKernelGGL(OmniShadowKernel<true>, grid, dim3(kOmniThreads), 0, stream, q);
+    } else {
+        hipLaunchKernelGGL(OmniShadowKernel<false>, grid, dim3(kOmniThreads), 0, stream, q);
     }
     return hipGetLastError();
 }

@@ -1016,6 +1016,63 @@ void DeviceScene::Shadow(const DeviceScene& light, const float* d_offsets, const
     }
 }
 
+// Shadow under a point light's six face scenes (render.h LaunchOmniShadow): the launch reads this
+// scene's buffers and all six faces', so it is ordered after the previous call of each and every
+// one records it.
+void DeviceScene::OmniShadow(const DeviceScene* const faces[6], const float* d_offsets, const int* d_ids,
+                             std::size_t row_begin, std::size_t row_count, float bias, unsigned char* d_mask,
+                             unsigned char* d_face, float* d_rgba, float dim, hipStream_t stream) const {
+    if (m_width == 0) {
+        throw std::runtime_error("Omni shadow: Prepare() has not been called on the view scene");
+    }
+    for (int k = 0; k < 6; ++k) {
+        const DeviceScene& f = *faces[k];
+        if (f.m_width == 0) {
+            throw std::runtime_error("Omni shadow: the light has not been prepared");
+        }
+        if (f.m_width != faces[0]->m_width || f.m_height != faces[0]->m_height) {
+            throw std::runtime_error("Omni shadow: the light's faces are prepared at different sizes");
+        }
+        if (f.m_device != m_device) {
+            throw std::runtime_error("Omni shadow: the view scene lives on device " + std::to_string(m_device) +
+                                     ", the light on device " + std::to_string(f.m_device));
+        }
+        if (f.m_n != m_n) {
+            throw std::runtime_error("Omni shadow: the view scene has " + std::to_string(m_n) +
+                                     " triangles, the light's scene " + std::to_string(f.m_n));
+        }
+    }
+    if (!(bias >= 0.f) || !std::isfinite(bias)) {
+        throw std::runtime_error("Omni shadow: bias must be finite and >= 0");
+    }
+    if (!std::isfinite(dim)) {
+        throw std::runtime_error("Omni shadow: dim must be finite");
+    }
+    if (row_begin > m_height || row_count > m_height - row_begin) {
+        throw std::runtime_error("Omni shadow: row band outside the frame");
+    }
+    if (row_count == 0) {
+        return;
+    }
+    OrderAfterPrevious(stream);
+    CullSetup setups[6] = {};
+    ShadowLight lights[6];
+    for (int k = 0; k < 6; ++k) {
+        const DeviceScene& f = *faces[k];
+        f.OrderAfterPrevious(stream);
+        const bool shared = f.QuerySetup(setups[k], stream);
+        lights[k] = ShadowLight{shared ? &setups[k] : nullptr, f.m_frame, f.m_width, f.m_height,
+                                f.m_svertices,                 f.m_edges, f.m_rank};
+    }
+    const ShadowArgs args{d_offsets, d_ids, m_width, m_height, row_begin, row_count, bias, d_mask, d_rgba, dim};
+    HipCheck(LaunchOmniShadow(m_vertices, m_shade, m_n, m_frame, m_background, lights, args, d_face, stream),
+             "omni shadow launch");
+    RecordOrder(stream);
+    for (int k = 0; k < 6; ++k) {
+        faces[k]->RecordOrder(stream);
+    }
+}
+
 DeviceScene::StageTimes DeviceScene::TakeTimes() {
     auto elapsed = [](hipEvent_t a, hipEvent_t b) {
         HipCheck(hipEventSynchronize(b), "hipEventSynchronize(stage timing)");

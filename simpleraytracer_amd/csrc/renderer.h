@@ -136,6 +136,15 @@ public:
                 std::size_t row_count, float bias, unsigned char* d_mask, float* d_rgba, float dim,
                 hipStream_t stream) const;
 
+    // Omni-light shadow mask (render.h LaunchOmniShadow): Shadow under a point light given as its six
+    // cube-face scenes (omni_math.h), all prepared at one size, on this scene's device, with this
+    // scene's number of triangles. d_face (may be null): the selected face per pixel. Builds every
+    // face's shared setup that its prepared frame lacks; one launch; this scene's and the six faces'
+    // calls are ordered against this one.
+    void OmniShadow(const DeviceScene* const faces[6], const float* d_offsets, const int* d_ids, std::size_t row_begin,
+                    std::size_t row_count, float bias, unsigned char* d_mask, unsigned char* d_face, float* d_rgba,
+                    float dim, hipStream_t stream) const;
+
     // G-buffer: the surface attributes (render.h GBufferArgs: depth, bary, normal, albedo; a null
     // plane is not written) of hit ids on the prepared frame. points: `count` positions d_where
     // (count x 2) with d_ids (count), row_begin unused. Else the band rows [row_begin, row_begin +

@@ -96,6 +96,34 @@ __host__ __device__ inline ShadowPoint ShadowProject(const float eye[3], const f
     return o;
 }
 
+// ShadowProject in two steps, for a caller that chooses its light frame from q (omni_math.h): the
+// same expressions in the same order, so ShadowProjectOffset(ShadowOffset(...)) has ShadowProject's bits.
+__host__ __device__ inline void ShadowOffset(const float eye[3], const float base[3], const float du[3],
+                                             const float dv[3], float fx, float fy, float t,
+                                             const float light_origin[3], float q[3]) {
+    for (int k = 0; k < 3; ++k) {
+        const float d = (base[k] + fx * du[k]) + fy * dv[k];
+        const float p = eye[k] + t * d;
+        q[k] = p - light_origin[k];
+    }
+}
+
+__host__ __device__ inline ShadowPoint ShadowProjectOffset(const float q[3], const float rows[9], float bias) {
+    ShadowPoint o{false, 0.f, 0.f, 0.f};
+    const float z = ShadowDot(q, rows + 6);
+    if (!(z > 0.f && z < __builtin_inff())) {
+        return o;
+    }
+    o.gx = ShadowDot(q, rows) / z;
+    o.gy = ShadowDot(q, rows + 3) / z;
+    if (!(o.gx >= 0.f && o.gx <= 1.f && o.gy >= 0.f && o.gy <= 1.f)) {
+        return o;
+    }
+    o.inside = true;
+    o.thr = z - bias * z;
+    return o;
+}
+
 // The class of a pixel inside the light's frustum from the light frame's closest hit (id', t').
 __host__ __device__ inline unsigned char ShadowClass(int id, int light_id, float light_t, float thr) {
     return light_id == id || light_t >= thr ? kShadowLit : kShadowShadowed;

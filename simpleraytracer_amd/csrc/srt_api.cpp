@@ -5,17 +5,20 @@
 #include <cmath>
 #include <cstring>
 #include <exception>
+#include <memory>
 #include <string>
 #include <vector>
 
 #include "cpu_render.h"
 #include "engine.h"
+#include "omni_math.h"
 #include "render.h"
 #include "renderer.h"
 #include "scene.h"
 #include "srt_gbuffer.h"
 #include "srt_layers.h"
 #include "srt_light.h"
+#include "srt_omni.h"
 #include "srt_query.h"
 #include "srt_render.h"
 #include "srt_samples.h"
@@ -1217,6 +1220,184 @@ RTL_API int rtlProjectionHost(const float camera10[10], size_t light_width, size
         }
         srt::HostShadowRows(CheckedCamera(camera10), light_width, light_height, rows9);
     });
+}
+
+// Omni-light shadow masks (include/srt_omni.h): the rto family.
+struct rto_light_t {
+    std::unique_ptr<srt::DeviceScene> faces[srt::kOmniFaces];
+    int device = 0;
+};
+
+namespace {
+
+void CheckedOrigin(const float origin[3]) {
+    if (origin == nullptr) {
+        throw std::runtime_error("Bad argument: origin is NULL");
+    }
+    for (int k = 0; k < 3; ++k) {
+        if (!std::isfinite(origin[k]) || std::fabs(origin[k]) > srt::kOmniOriginMax) {
+            throw std::runtime_error("Bad light origin: value " + std::to_string(k) +
+                                     " must be finite and at most 2^16 in magnitude");
+        }
+    }
+}
+
+void CheckedFace(int face) {
+    if (face < 0 || face >= srt::kOmniFaces) {
+        throw std::runtime_error("Bad face index " + std::to_string(face) + ": faces are 0 to 5");
+    }
+}
+
+}  // namespace
+
+RTO_API rto_light rtoLightCreate(const char* path, int device, const float origin[3]) {
+    rto_light out = nullptr;
+    Guarded([&] {
+        if (path == nullptr) {
+            throw std::runtime_error("Bad path argument");
+        }
+        CheckedOrigin(origin);
+        srt::Scene scene = srt::LoadScene(path);
+        int count = 0;
+        if (hipGetDeviceCount(&count) != hipSuccess || device < 0 || device >= count) {
+            throw std::runtime_error("HIP error: device " + std::to_string(device) + " not available (" +
+                                     std::to_string(count) + " present); the device stages have no CPU path");
+        }
+        auto light = std::make_unique<rto_light_t>();
+        light->device = device;
+        for (int k = 0; k < srt::kOmniFaces; ++k) {
+            float c10[10];
+            srt::OmniFaceCamera(origin, k, c10);
+            scene.camera = CheckedCamera(c10);
+            light->faces[k] = std::make_unique<srt::DeviceScene>(scene, device);
+        }
+        out = light.release();
+    });
+    return out;
+}
+
+RTO_API void rtoLightRelease(rto_light light) { delete light; }
+
+RTO_API int rtoLightPrepareAsync(rto_light light, size_t face_size, void* stream) {
+    return Guarded([&] {
+        if (light == nullptr) {
+            throw std::runtime_error("Bad light handle");
+        }
+        if (face_size == 0) {
+            throw std::runtime_error("Bad argument: face_size must be non-zero");
+        }
+        Bind bind(light->device);
+        for (auto& f : light->faces) {
+            f->Prepare(face_size, face_size, static_cast<hipStream_t>(stream));
+        }
+    });
+}
+
+RTO_API srt_device_scene rtoLightFace(rto_light light, int face) {
+    srt_device_scene out = nullptr;
+    Guarded([&] {
+        if (light == nullptr) {
+            throw std::runtime_error("Bad light handle");
+        }
+        CheckedFace(face);
+        out = reinterpret_cast<srt_device_scene>(light->faces[face].get());
+    });
+    return out;
+}
+
+RTO_API int rtoShadowAsync(srt_device_scene view, rto_light light, const float* d_offsets, const int* d_ids,
+                           size_t row_begin, size_t row_count, float bias, unsigned char* d_mask,
+                           unsigned char* d_face, float* d_rgba, float dim, void* stream) {
+    return Guarded([&] {
+        if (view == nullptr) {
+            throw std::runtime_error("Bad scene handle: view is NULL");
+        }
+        if (light == nullptr) {
+            throw std::runtime_error("Bad light handle");
+        }
+        if (row_count != 0) {
+            if (d_offsets == nullptr) {
+                throw std::runtime_error("Bad buffer argument: d_offsets is NULL");
+            }
+            if (d_ids == nullptr) {
+                throw std::runtime_error("Bad buffer argument: d_ids is NULL");
+            }
+            if (d_mask == nullptr) {
+                throw std::runtime_error("Bad buffer argument: d_mask is NULL");
+            }
+        }
+        srt::DeviceScene* s = FromHandle(view);
+        Bind bind(s->device());
+        const srt::DeviceScene* faces[srt::kOmniFaces];
+        for (int k = 0; k < srt::kOmniFaces; ++k) {
+            faces[k] = light->faces[k].get();
+        }
+        s->OmniShadow(faces, d_offsets, d_ids, row_begin, row_count, bias, d_mask, d_face, d_rgba, dim,
+                      static_cast<hipStream_t>(stream));
+    });
+}
+
+RTO_API int rtoShadowHost(const char* scene_path, size_t width, size_t height, const float origin[3], size_t face_size,
+                          const float* offsets, const int* ids, size_t row_begin, size_t row_count, float bias,
+                          unsigned char* mask, unsigned char* face, float* rgba, float dim) {
+    return Guarded([&] {
+        if (scene_path == nullptr) {
+            throw std::runtime_error("Bad argument: scene_path is NULL");
+        }
+        CheckedOrigin(origin);
+        if (width == 0 || height == 0) {
+            throw std::runtime_error("Bad argument: frame dimensions must be non-zero");
+        }
+        if (face_size == 0) {
+            throw std::runtime_error("Bad argument: face_size must be non-zero");
+        }
+        if (!(bias >= 0.f) || !std::isfinite(bias)) {
+            throw std::runtime_error("Omni shadow: bias must be finite and >= 0");
+        }
+        if (!std::isfinite(dim)) {
+            throw std::runtime_error("Omni shadow: dim must be finite");
+        }
+        if (row_begin > height || row_count > height - row_begin) {
+            throw std::runtime_error("Bad argument: row band outside the frame");
+        }
+        if (row_count == 0) {
+            return;
+        }
+        if (offsets == nullptr) {
+            throw std::runtime_error("Bad buffer argument: offsets is NULL");
+        }
+        if (ids == nullptr) {
+            throw std::runtime_error("Bad buffer argument: ids is NULL");
+        }
+        if (mask == nullptr) {
+            throw std::runtime_error("Bad buffer argument: mask is NULL");
+        }
+        const srt::Scene scene = srt::LoadScene(scene_path);
+        srt::HostOmniShadow(scene, width, height, origin, face_size, offsets, ids, row_begin, row_count, bias, mask,
+                            face, rgba, dim);
+    });
+}
+
+RTO_API int rtoFaceCameraHost(const float origin[3], int face, float camera10[10]) {
+    return Guarded([&] {
+        CheckedOrigin(origin);
+        CheckedFace(face);
+        if (camera10 == nullptr) {
+            throw std::runtime_error("Bad argument: camera10 is NULL");
+        }
+        srt::OmniFaceCamera(origin, face, camera10);
+    });
+}
+
+RTO_API int rtoFaceOfHost(const float q[3]) {
+    int face = -1;
+    Guarded([&] {
+        if (q == nullptr) {
+            throw std::runtime_error("Bad argument: q is NULL");
+        }
+        face = srt::OmniFace(q);
+    });
+    return face;
 }
 
 #ifdef SRT_DIAG

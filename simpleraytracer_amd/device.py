@@ -1,6 +1,7 @@
 """Scene files, the device-level render stages (include/srt_render.h), point queries
 (include/srt_query.h), G-buffer outputs (include/srt_gbuffer.h), multi-sample frames
-(include/srt_samples.h) and spot-light shadow masks (include/srt_light.h).
+(include/srt_samples.h), spot-light shadow masks (include/srt_light.h) and omni-light shadow masks
+(include/srt_omni.h).
 
 ``DeviceScene`` keeps a scene resident on one GPU and launches the two stages on a caller's
 HIP stream with caller-owned device buffers (torch tensors or raw pointers):
@@ -13,6 +14,7 @@ HIP stream with caller-owned device buffers (torch tensors or raw pointers):
     scene.render_samples(offsets_s, ids_s, rgba, stream=s)       # S samples per pixel, resolved (also resolve())
     scene.shadow(light, offsets, ids, mask, rgba, stream=s)      # which pixels a spot light (a second scene) reaches
     scene.layer_frame(offsets, ids_k, t_k, stream=s)             # the K nearest hits per pixel (also layers(), composite())
+    scene.omni_shadow(omni, offsets, ids, mask, face, stream=s)  # which pixels a point light (an OmniLight) reaches
 
 This is the path bench.py times (inputs resident in HBM) and the one-process-per-GPU
 band renderer uses; ``runner.render`` is the host-image ml* path.
@@ -256,6 +258,53 @@ def shadow_host(path: str, width: int, height: int, light_camera, light_width: i
     return mask, rgba
 
 
+def _float3(name: str, values):
+    vals = [float(v) for v in values]
+    if len(vals) != 3:
+        raise ValueError(f"{name} must be 3 floats, got {len(vals)}")
+    return (ctypes.c_float * 3)(*vals)
+
+
+def omni_face_camera(origin, face: int):
+    """The camera (eye, lookat, up, vfov_deg: 10 floats) of cube face `face` (0 .. 5) of the point
+    light at `origin` (rtoFaceCameraHost; include/srt_omni.h has the table)."""
+    cam = (ctypes.c_float * 10)()
+    _check(_native.lib().rtoFaceCameraHost(_float3("origin", origin), face, cam))
+    return tuple(cam)
+
+
+def omni_face_of(q) -> int:
+    """The cube face (0 .. 5) the omni shadow kernel selects for q = surface point - light origin
+    (rtoFaceOfHost): the largest |q_k|, ties to the lower axis, 2 k + (q_k < 0)."""
+    return _native.lib().rtoFaceOfHost(_float3("q", q))
+
+
+def omni_shadow_host(path: str, width: int, height: int, origin, face_size: int, offsets, ids, bias: float = 0.0,
+                     dim: float = 0.0, row_begin: int = 0, row_count: int | None = None):
+    """The omni-light shadow mask on the host (rtoShadowHost: brute force, the library's canonical
+    math, no device): the band rows of path's width x height frame under the point light at
+    `origin` with face_size x face_size cube faces, offsets (rows, W, 2) float32 and ids (rows, W)
+    int32 -> (mask (rows, W) uint8 of shadow_host()'s classes, face (rows, W) uint8: the selected
+    face, 255 for a class-3 pixel, rgba (rows, W, 4) float32 as shadow_host()'s)."""
+    import numpy as np
+
+    if row_count is None:
+        row_count = height - row_begin
+    off = np.ascontiguousarray(offsets, np.float32)
+    idv = np.ascontiguousarray(ids, np.int32)
+    if off.shape != (row_count, width, 2):
+        raise ValueError(f"offsets must be {(row_count, width, 2)}, got {off.shape}")
+    if idv.shape != (row_count, width):
+        raise ValueError(f"ids must be {(row_count, width)}, got {idv.shape}")
+    mask = np.empty((row_count, width), np.uint8)
+    face = np.empty((row_count, width), np.uint8)
+    rgba = np.empty((row_count, width, 4), np.float32)
+    _check(_native.lib().rtoShadowHost(os.fsencode(path), width, height, _float3("origin", origin), face_size,
+                                       off.ctypes.data, idv.ctypes.data, row_begin, row_count, bias, mask.ctypes.data,
+                                       face.ctypes.data, rgba.ctypes.data, dim))
+    return mask, face, rgba
+
+
 def tile_of(width: int, height: int, fx: float, fy: float):
     """The cull tile (col, row) the query kernel looks a position up in (rtqTileHost), or None
     when the position is not in [0, 1]^2."""
@@ -291,6 +340,7 @@ class DeviceScene:
         a spot light's for instance; None keeps the file's."""
         self._lib = _native.lib()
         self.handle = None
+        self._owned = True
         if camera is None:
             self.handle = self._lib.srtDeviceSceneCreate(os.fsencode(path), device)
         else:
@@ -302,6 +352,19 @@ class DeviceScene:
         self.triangles = self._lib.srtDeviceSceneTriangles(self.handle)
         self.width = 0
         self.height = 0
+
+    @classmethod
+    def _borrowed(cls, handle, device: int, path: str, size: int):
+        """A view of a device scene another object owns (OmniLight.face): close() releases nothing."""
+        self = cls.__new__(cls)
+        self._lib = _native.lib()
+        self.handle = handle
+        self._owned = False
+        self.device = device
+        self.path = path
+        self.triangles = self._lib.srtDeviceSceneTriangles(handle)
+        self.width = self.height = size
+        return self
 
     def prepare(self, width: int, height: int, stream=None):
         _check(self._lib.srtPrepareAsync(self.handle, width, height, _stream(stream)))
@@ -642,9 +705,73 @@ class DeviceScene:
                                            ctypes.byref(t)))
         return n.value, p.value, b.value, t.value
 
+    def omni_shadow(self, light, offsets, ids, mask, face=None, rgba=None, bias: float = 0.0, dim: float = 0.0,
+                    row_begin: int = 0, row_count: int | None = None, stream=None):
+        """Omni-light shadow mask of the prepared frame's rows (include/srt_omni.h): `light` is a
+        prepared OmniLight of the same triangles. offsets, ids, mask, rgba, bias, dim as shadow()'s;
+        face (rows, W) uint8, optional: the cube face each pixel selected, 255 for a class-3 pixel.
+        One launch: every pixel runs shadow()'s test in its own face's frame only."""
+        if row_count is None:
+            row_count = self.height - row_begin
+        self._check_buffer("offsets", offsets, row_count, 2, "f32")
+        self._check_buffer("ids", ids, row_count, 0, "i32")
+        self._check_buffer("mask", mask, row_count, 0, "u8")
+        if face is not None:
+            self._check_buffer("face", face, row_count, 0, "u8")
+        if rgba is not None:
+            self._check_buffer("rgba", rgba, row_count, 4, "f32")
+        _check(self._lib.rtoShadowAsync(self.handle, light.handle, _ptr(offsets), _ptr(ids), row_begin, row_count, bias,
+                                        _ptr(mask), _ptr(face), _ptr(rgba), dim, _stream(stream)))
+
     def close(self):
         if self.handle:
-            self._lib.srtDeviceSceneRelease(self.handle)
+            if self._owned:
+                self._lib.srtDeviceSceneRelease(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        self.close()
+
+
+class OmniLight:
+    """A point light resident on one HIP device (include/srt_omni.h): six cube-face scenes of the
+    file's triangles under the cameras omni_face_camera(origin, k), prepared at one face size."""
+
+    def __init__(self, path: str, device: int = 0, origin=(0.0, 0.0, 0.0)):
+        self._lib = _native.lib()
+        self.handle = None
+        self.handle = self._lib.rtoLightCreate(os.fsencode(path), device, _float3("origin", origin))
+        if not self.handle:
+            raise SrtError(_native.last_error())
+        self.device = device
+        self.path = path
+        self.origin = tuple(float(v) for v in origin)
+        self.face_size = 0
+        self._faces = {}
+
+    def prepare(self, face_size: int, stream=None):
+        _check(self._lib.rtoLightPrepareAsync(self.handle, face_size, _stream(stream)))
+        self.face_size = face_size
+        for f in self._faces.values():
+            f.width = f.height = face_size
+
+    def face(self, k: int):
+        """Face k (0 .. 5) as a DeviceScene that does not own its handle: every DeviceScene call
+        works on it (trace_ids() of the six gives a cube map); close() on it releases nothing, and
+        it must not be used after the light's close()."""
+        if k not in self._faces:
+            handle = self._lib.rtoLightFace(self.handle, k)
+            if not handle:
+                raise SrtError(_native.last_error())
+            self._faces[k] = DeviceScene._borrowed(handle, self.device, self.path, self.face_size)
+        return self._faces[k]
+
+    def close(self):
+        if self.handle:
+            for f in self._faces.values():
+                f.handle = None
+            self._faces = {}
+            self._lib.rtoLightRelease(self.handle)
             self.handle = None
 
     def __del__(self):
