@@ -314,8 +314,11 @@ struct CullSetup {
     unsigned* lists;       // tiles x capacity candidate positions
     unsigned* large_list;  // positions binned to every tile
     void* work;            // the plan: descs descriptors, heaviest first, facts baked in
+    void* work_tmp;        // descs descriptors of scratch (LaunchStreamPlan's partition)
     unsigned* work_count;
-    unsigned long long* stream_count;  // [0]: records of the record stream (LaunchStreamPlan), pad records included
+    // [0]: records of the record stream (LaunchStreamPlan), pad records included; [1]: the plan's
+    // descriptors that are not statically empty (low word) and those that are (high word)
+    unsigned long long* stream_count;
     // The record stream (below): an allocation of its own, sized from stream_count after the plan;
     // null: the traces read the records through the lists (the indexed path).
     const void* stream;
@@ -325,12 +328,26 @@ struct CullSetup {
     unsigned descs;        // the trace grid the plan was made for
     unsigned min_chunk;    // smallest candidate chunk of a split part (env SRT_CULL_CHUNK at the carve-up)
     bool recompute;        // CullBins::recompute of the traces it serves
+    // The empty sweep (below). sweep: LaunchStreamPlan lists the statically empty descriptors last and
+    // the traces sweep them in groups; list_descs, empty_descs: the built plan's counts (the caller
+    // reads stream_count[1] once per build); empty_group: descriptors per sweep block, 1 to
+    // kMaxEmptyGroup (read per launch: not part of what is built).
+    bool sweep;
+    unsigned list_descs, empty_descs, empty_group;
 };
+// The empty sweep: with setup.sweep the trace grid is the list descriptors, one block each, and one
+// sweep block per empty_group statically empty descriptors (render.hip TraceCullKernel), instead of
+// one block per descriptor of the plan's room.
+constexpr unsigned kDefaultEmptyGroup = 16;
+constexpr unsigned kMaxEmptyGroup = 64;  // one lane of a wave per descriptor of the group
+unsigned SharedTraceBlocks(unsigned descs, unsigned list_descs, unsigned empty_descs, unsigned group);
 // The record stream of a built setup: the 64-B cull records of every (tile, chunk) of the plan, in
 // the order its trace blocks walk them (chunk [begin, end) of the tile's bin list, then the large
 // list), each range starting at a multiple of 128 B (an even record index). The parts of a tile walk
 // the same lists, so they share the tile's ranges. A statically FULL or empty descriptor has no
-// range. LaunchStreamPlan (after LaunchCullSetup, same stream) writes every descriptor's first record
+// range. LaunchStreamPlan (after LaunchCullSetup, same stream; run for every build, stream or not)
+// first puts the plan into the empty sweep's order (setup.sweep) and counts its list and empty
+// descriptors into setup.stream_count[1]; then it writes every descriptor's first record
 // index and record count into its w1.x and w1.y -- unused on the shared path otherwise --, zeroes
 // the second half of the end marks, and writes the stream's length into setup.stream_count; the
 // caller reads that once, allocates, and LaunchStreamPack fills `stream`.

@@ -136,6 +136,9 @@ struct TraceParams {
     unsigned fused;                            // bins from the analytic tile bounds (BinParams::fused)
     unsigned plan_only;  // the work list is the slot's plan (no order launch for this frame): read the bins
     unsigned bin_capacity;
+    unsigned list_descs;   // shared setup: the plan's descriptors that are not statically empty (they come first)
+    unsigned empty_descs;  // shared setup: its statically empty descriptors (they follow)
+    unsigned empty_group;  // shared setup: empty descriptors per sweep block (TraceCullKernel); 0: one block each
     unsigned exp;                                // diagnostic build: experiment bits (env SRT_EXP), 0 in the product
     float wf;
     float hf;
@@ -1436,7 +1439,8 @@ struct CullShared {
     float rlo[kBlockRows], rhi[kBlockRows];  // monotone row bounds of fy
     unsigned counts[2][kCullWaves];            // FULL stream: survivors per wave and step
     Box wave_box[kCullWaves];
-    unsigned last;  // split work item: this block arrived last
+    unsigned last;  // split work item: this block arrived last; a sweep block: its `todo` bits, low word
+    unsigned todo_hi;  // a sweep block: high word (the 4 B in front of the 8-B aligned keys: no LDS added)
     unsigned long long keys[kBlockRows][kWave];  // per-pixel lexicographic (t, id) keys
 };
 static_assert(sizeof(float2) * kWave * kCullWaves <= sizeof(float4) * 2 * kPacketBatch, "PacketTables scratch");
@@ -2168,13 +2172,19 @@ __device__ __forceinline__ int LastLoAtMost(const float2* b, int n, float v, con
 // invalid; a plan-only trace (a later frame) reads those facts from its own bins (TraceParams::
 // plan_only). The chunking is made as if every offset were in [0, 1], so it may serve later frames.
 // (Gathering whole empty tiles four to a descriptor, one block storing all their misses, cut the
-// trace grid by ~950 blocks at C3 and measured no faster: an empty part's block is cheap.)
+// trace grid by ~950 blocks at C3 and measured no faster: an empty part's block is cheap. That was
+// a per-frame plan with the trace about half of a frame's three launches. On the shared setup the
+// plan is static, the trace is the frame, and its resident block slots are what is scarce: there
+// the empty descriptors are listed last and swept sixteen to a block -- TraceCullKernel's sweep
+// blocks --, which measured +3.8 % on the headline; not launching them at all, +11.4 %:
+// profiles/empty_sweep/README.md.)
 // (BinParams::work_count: kOrderWords words, unused by the product kernels.)
 constexpr int kOrderBuckets = 64;
 constexpr int kOrderWords = 72;
 constexpr unsigned kItemRegular = 1u;
 constexpr unsigned kItemFull = 2u;
 constexpr unsigned kItemEmpty = 4u;  // no candidate can hit a ray of the tile: every pixel misses
+[[maybe_unused]] constexpr unsigned kItemSweep = 8u;  // diagnostic rows only: a sweep block's (TraceCullKernel)
 constexpr unsigned kWorkEnd = 0xFFFFFFFFu;  // w0.x of a descriptor past the end of the list
 constexpr int kEmptyTest = 4;  // a tile with an empty bin list is tested against up to this many large-list records
 struct OrderItem {
@@ -2949,6 +2959,30 @@ struct TraceRecords<true> {
 // function of the plan alone, so the first batch is requested as soon as the descriptor is there,
 // beside the frame's tile facts; a tile whose facts then say FULL drops what was loaded and streams
 // every record as on the indexed path. No list entry is read.
+// The miss value of every pixel of one tile part (kBlockRows rows from band row row0 of tile column
+// tx), stored by the block's 256 threads: wave w rows row0 + w R .. + R - 1, lane = column.
+__device__ __forceinline__ void StoreMissPart(const TraceParams& p, int tx, int row0, int lane, int wave) {
+    constexpr int R = kCullR;
+    const int xe = tx * kWave + lane;
+    if (p.out_packed != nullptr) {
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+            const int y = row0 + wave * R + r;
+            if (y < p.row_count) {
+                StorePackedIds(p, tx, xe, y, -1);
+            }
+        }
+    } else if (xe < p.width) {
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+            const int y = row0 + wave * R + r;
+            if (y < p.row_count) {
+                StorePixel(p, xe, y, 0.f, 0.f, -1);
+            }
+        }
+    }
+}
+
 template <class Frames, bool RC = false, bool SHARED = false, bool STREAM = false>
 __global__ __launch_bounds__(kCullThreads, SRT_TRACE_OCC) void TraceCullKernel(const Frames batch) {
     static_assert(!STREAM || (SHARED && !RC), "the record stream: stored records of the shared setup");
@@ -2958,11 +2992,38 @@ __global__ __launch_bounds__(kCullThreads, SRT_TRACE_OCC) void TraceCullKernel(c
     __shared__ CullShared sh;
 #ifdef SRT_DIAG
     const unsigned long long d_rt0 = __builtin_amdgcn_s_memrealtime();
+#endif
+    // SHARED with p.empty_group = G != 0 (the empty sweep): the plan lists its statically empty
+    // descriptors last (StreamPlanKernel) and the grid is p.list_descs + ceil(p.empty_descs / G)
+    // blocks. Block b < list_descs is descriptor b's, as ever (a list block). Block list_descs + g is
+    // a sweep block: it owns the empty descriptors [list_descs + g G, + G) (the last group: the
+    // rest). It knows itself by its own descriptor b, which is one of the empty ones (g < empty_descs),
+    // so a list block's chain of loads is what it was. One lane per descriptor -- in every wave, so
+    // that each wave holds the answers -- loads it and then its tile's facts: two vector loads for
+    // the group, where G blocks each waited for two dependent scalar loads. Which tiles are empty is
+    // the setup's; a frame decides only whether the tile's offsets are valid (kFactUsable |
+    // kFactInRange). The valid tiles' misses are stored by the block's 256 threads, one part after
+    // another (StoreMissPart: the stores an empty part's own block made). A tile whose facts are
+    // not valid must be traced, FULL stream, with the empty flag ignored: the sweep block runs the
+    // block body for each such descriptor, one after another (`todo`: their bits). That case is rare
+    // (offsets outside [0, 1], NaN) and G-fold serialised against one block per descriptor: correct,
+    // not fast.
+    // The body is a lambda inlined twice: the list blocks' copy, which every block enters and a
+    // sweep block leaves at once (it returns true), and the sweep blocks' copy in the loop at the
+    // kernel's end, compiled for the FULL stream only (kOnlyFull). A loop around one shared copy,
+    // and even the sweep's loads in front of it, cost the kernel its allocation (80 VGPRs are the
+    // walk's, with none to spare: scratch and VGPR spills in every shared instantiation); so did the
+    // loop's state in registers, which is why the sweep block keeps `todo` in the two LDS words in
+    // front of the keys (CullShared::last, todo_hi: no LDS added). profiles/empty_sweep/README.md.
+    unsigned long long todo = 0ull;  // a sweep block: the descriptors of its group it has to trace
+    [[maybe_unused]] bool sweeping = false;
+    [[maybe_unused]] unsigned swept = 0u, d_traced = 0u;  // (diagnostic row: tiles filled, tiles traced)
+#ifdef SRT_DIAG
     const unsigned d_blk = (blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;
     unsigned long long d_gather = 0, d_walk = 0, d_batches = 0, d_cand = 0;
     unsigned long long d_mark = __builtin_amdgcn_s_memtime();
     auto diag_end = [&](unsigned it, unsigned ch, unsigned nch, unsigned last, unsigned full, unsigned fl) {
-        if (threadIdx.x == 0 && d_blk < kDiagBlocks) {
+        if (threadIdx.x == 0 && d_blk < kDiagBlocks && !sweeping) {
             unsigned long long* d = g_srt_diag[d_blk];
             d[1] = d_gather;
             d[2] = d_walk;
@@ -2979,6 +3040,59 @@ __global__ __launch_bounds__(kCullThreads, SRT_TRACE_OCC) void TraceCullKernel(c
 #else
 #define SRT_DIAG_END(it, ch, nch, last, full)
 #endif
+    // A sweep block's group: loads, the fill of the valid tiles, `todo` = the others.
+    [[maybe_unused]] auto sweep_fill = [&]() __attribute__((always_inline)) {
+            sweeping = true;
+            const int s_lane = threadIdx.x & (kWave - 1);
+            const int s_wave = __builtin_amdgcn_readfirstlane(threadIdx.x / kWave);
+            const unsigned d_first = p.list_descs + (blockIdx.x - p.list_descs) * p.empty_group;
+            const unsigned cnt = min(p.empty_group, p.list_descs + p.empty_descs - d_first);  // >= 1: the grid
+            unsigned my_item = 0u, my_facts = 0u;
+            float my_ox = 0.f, my_oy = 0.f;
+            bool fill = false;
+            if (static_cast<unsigned>(s_lane) < cnt) {
+                const uint4 w0 = p.work[2 * (d_first + s_lane)];
+                my_item = w0.x;
+                if (w0.x != kWorkEnd) {  // (never: the counts are the plan's)
+                    const TileFacts tf = p.tile_facts[w0.x / kParts];
+                    constexpr unsigned kValid = kFactUsable | kFactInRange;
+                    fill = (w0.w & (kItemFull | kItemEmpty)) == kItemEmpty && (tf.flags & kValid) == kValid;
+                    my_facts = tf.flags;
+                    my_ox = tf.ox;
+                    my_oy = tf.oy;
+                }
+            }
+            const unsigned long long filled = __ballot(fill);
+            todo = __ballot(static_cast<unsigned>(s_lane) < cnt && !fill);
+            swept = static_cast<unsigned>(__popcll(filled));
+            d_traced = static_cast<unsigned>(__popcll(todo));
+            for (unsigned long long m = filled; m != 0ull; m &= m - 1ull) {
+                const int k = __builtin_ctzll(m);  // wave-uniform
+                const unsigned it = static_cast<unsigned>(__builtin_amdgcn_readlane(static_cast<int>(my_item), k));
+                const unsigned tile = it / kParts;
+                const int tx = static_cast<int>(tile % static_cast<unsigned>(p.tiles_x));
+                const int ty = static_cast<int>(tile / static_cast<unsigned>(p.tiles_x));
+                const int row0 = ty * kTileRows + static_cast<int>(it % kParts) * kBlockRows;
+                if (row0 >= p.row_count) {
+                    continue;  // the last tile row's empty part
+                }
+                if (p.out_packed != nullptr && it % kParts == 0u) {  // the tile's offset entry (below)
+                    const unsigned ff = static_cast<unsigned>(__builtin_amdgcn_readlane(static_cast<int>(my_facts), k));
+                    const float fox = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(my_ox), k));
+                    const float foy = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(my_oy), k));
+                    if (threadIdx.x == 0) {
+                        const float qn = __builtin_nanf("");
+                        *reinterpret_cast<float2*>(PackedTileOffset(p.out_packed, p, ty * kTileRows, tx)) =
+                            (ff & kFactRegular) != 0u ? make_float2(fox, foy) : make_float2(qn, qn);
+                    }
+                }
+                StoreMissPart(p, tx, row0, s_lane, s_wave);
+            }
+    };
+    // (the body keeps the kernel's indentation: it was the kernel's own text, and `return` still ends
+    // the block's work on descriptor d; true: a sweep block, which goes on below)
+    auto body = [&](const unsigned d, auto only_full) __attribute__((always_inline)) -> bool {
+    constexpr bool kOnlyFull = decltype(only_full)::value;  // a sweep block's copy: FULL stream, whatever the plan says
     // Block = one part (kBlockRows rows) of a cull tile. Binned: work item blockIdx.x of the
     // tile order's list (a part, or one candidate chunk of a split part; the grid is sized for
     // the longest list and the blocks past its end exit). Unbinned: part (x, y), FULL stream.
@@ -2992,7 +3106,6 @@ __global__ __launch_bounds__(kCullThreads, SRT_TRACE_OCC) void TraceCullKernel(c
         // The work list (WorkOrderKernel) gives this block its tile part and chunk; with an order
         // launch for this frame it also holds the frame's facts, else it is the slot's plan
         // (scheduling only) and the block reads them from the frame's bins and tile info.
-        const unsigned d = blockIdx.x;  // < descs: the plan, then end marks
         const uint4 w0 = p.work[2 * d], w1 = p.work[2 * d + 1];
         // (STREAM: an end mark is the tag and seven zero words -- StreamPlanKernel clears its second
         // half --, tested as a whole so that the descriptor arrives in one load, not its first word
@@ -3000,7 +3113,15 @@ __global__ __launch_bounds__(kCullThreads, SRT_TRACE_OCC) void TraceCullKernel(c
         const bool end_mark = STREAM ? (w0.x == kWorkEnd) & ((w0.y | w0.z | w0.w | w1.x | w1.y | w1.z | w1.w) == 0u)
                                      : w0.x == kWorkEnd;
         if (end_mark) {
-            return;
+            return false;
+        }
+        if constexpr (SHARED && !kOnlyFull) {
+            // A statically empty descriptor with the sweep on: this is a sweep block (they follow the
+            // list descriptors, so each one's own descriptor is an empty one). Decided from the
+            // descriptor, which every block waits for anyway: nothing joins a list block's load chain.
+            if ((w0.w & kItemEmpty) != 0u && p.empty_group != 0u) {
+                return true;
+            }
         }
         item = w0.x;
         chunk = w1.z & 0xFFFFu;
@@ -3032,7 +3153,7 @@ __global__ __launch_bounds__(kCullThreads, SRT_TRACE_OCC) void TraceCullKernel(c
                 // whatever the facts say.
                 stream_n = w1.y;
                 sbase = p.stream + w1.x;
-                if (stream_n != 0u) {
+                if (!kOnlyFull && stream_n != 0u) {
 #pragma unroll
                     for (int e = 0; e < kSlices; ++e) {
                         if (InBatch(e, threadIdx.x)) {
@@ -3043,7 +3164,7 @@ __global__ __launch_bounds__(kCullThreads, SRT_TRACE_OCC) void TraceCullKernel(c
                 }
             }
             constexpr unsigned kValid = kFactUsable | kFactInRange;
-            full = (w0.w & kItemFull) != 0u || (tf.flags & kValid) != kValid;
+            full = kOnlyFull || (w0.w & kItemFull) != 0u || (tf.flags & kValid) != kValid;
             flags = (full ? kItemFull : (w0.w & kItemEmpty)) | ((tf.flags & kFactRegular) != 0u ? kItemRegular : 0u);
             ox = tf.ox;
             oy = tf.oy;
@@ -3095,10 +3216,10 @@ __global__ __launch_bounds__(kCullThreads, SRT_TRACE_OCC) void TraceCullKernel(c
         }
         // A FULL tile streams every record in its part's first chunk; the plan's other chunks of
         // the part (the plan is made as if the bins were valid) have no candidates and publish misses.
-        src.full = full && chunk == 0u;
+        src.full = kOnlyFull || (full && chunk == 0u);
         if constexpr (STREAM) {
             src.end = full ? 0u : stream_n;  // positions of the block's own stream range
-        } else if (!src.full) {
+        } else if (!kOnlyFull && !src.full) {
             // candidates cut into n chunks: chunk c = [c q + c r / n, (c + 1) q + (c + 1) r / n), q r = c_t / n, % n
             const unsigned q = c_t / nchunks, r = c_t % nchunks;
             src.list = p.bin_lists + static_cast<size_t>(t) * p.bin_capacity;
@@ -3115,7 +3236,7 @@ __global__ __launch_bounds__(kCullThreads, SRT_TRACE_OCC) void TraceCullKernel(c
     const int ty = static_cast<int>(tile / static_cast<unsigned>(p.tiles_x));
     const int row0 = ty * kTileRows + static_cast<int>(item % kParts) * kBlockRows;  // band row of the block
     if (row0 >= p.row_count) {
-        return;  // the last tile row's empty part
+        return false;  // the last tile row's empty part
     }
     if (p.out_packed != nullptr && threadIdx.x == 0 && chunk == 0u && item % kParts == 0u) {
         // The tile's sample offset in the packed ids when every ray of the tile has it (the deferred
@@ -3127,27 +3248,10 @@ __global__ __launch_bounds__(kCullThreads, SRT_TRACE_OCC) void TraceCullKernel(c
     const int tid = threadIdx.x;
     const int lane = tid & (kWave - 1);
     const int wave = __builtin_amdgcn_readfirstlane(tid / kWave);
-    if (flags & kItemEmpty) {  // every pixel misses (BuildWorkOrder): the miss value, no rays
-        const int xe = tx * kWave + lane;
-        if (p.out_packed != nullptr) {
-#pragma unroll
-            for (int r = 0; r < R; ++r) {
-                const int y = row0 + wave * R + r;
-                if (y < p.row_count) {
-                    StorePackedIds(p, tx, xe, y, -1);
-                }
-            }
-        } else if (xe < p.width) {
-#pragma unroll
-            for (int r = 0; r < R; ++r) {
-                const int y = row0 + wave * R + r;
-                if (y < p.row_count) {
-                    StorePixel(p, xe, y, 0.f, 0.f, -1);
-                }
-            }
-        }
+    if (!kOnlyFull && (flags & kItemEmpty) != 0u) {  // every pixel misses (BuildWorkOrder): the miss value, no rays
+        StoreMissPart(p, tx, row0, lane, wave);
         SRT_DIAG_END(item, chunk, nchunks, 1u, src.full);
-        return;
+        return false;
     }
     // LIST: the first batch's records are requested before the rays are set up (its loads
     // are the block's longest dependency chain: list entry, then the 64-B record).
@@ -3191,7 +3295,7 @@ __global__ __launch_bounds__(kCullThreads, SRT_TRACE_OCC) void TraceCullKernel(c
         }
     };
     if constexpr (!STREAM) {  // (STREAM: the first batch was requested with the facts)
-        if (!src.full && total != 0u) {
+        if (!kOnlyFull && !src.full && total != 0u) {
             load_ids(0u);
             load_list(0u);
         }
@@ -3254,7 +3358,7 @@ __global__ __launch_bounds__(kCullThreads, SRT_TRACE_OCC) void TraceCullKernel(c
         d_mark = now;
     }
 #endif
-    if (!src.full) {
+    if (!kOnlyFull && !src.full) {
         // LIST: candidates [begin, end) of the tile's virtual list, one batch ahead.
 #pragma unroll 1
         for (unsigned b0 = 0; b0 < total; b0 += kPacketBatch) {
@@ -3361,7 +3465,7 @@ __global__ __launch_bounds__(kCullThreads, SRT_TRACE_OCC) void TraceCullKernel(c
     for (int r = 0; r < R; ++r) {
         key[r] = sh.keys[wave * R + r][lane];
     }
-    if (nchunks > 1u) {
+    if (!kOnlyFull && nchunks > 1u) {
         constexpr int kPix = kBlockRows * kWave;
         unsigned long long* slices = p.split_keys + static_cast<size_t>(slot) * kPix;
         const int pix = wave * R * kWave + lane;
@@ -3390,7 +3494,7 @@ __global__ __launch_bounds__(kCullThreads, SRT_TRACE_OCC) void TraceCullKernel(c
         __syncthreads();
         if (sh.last == 0u) {
             SRT_DIAG_END(item, chunk, nchunks, 0u, src.full);
-            return;
+            return false;
         }
         for (unsigned c = 0; c < nchunks; ++c) {
             if (c == chunk) {
@@ -3443,6 +3547,47 @@ __global__ __launch_bounds__(kCullThreads, SRT_TRACE_OCC) void TraceCullKernel(c
         }
     }
     SRT_DIAG_END(item, chunk, nchunks, 1u, src.full);
+    return false;
+    };
+    if (!body(blockIdx.x, std::false_type{})) {
+        return;
+    }
+    if constexpr (SHARED) {
+        sweep_fill();
+    }
+    if (todo != 0ull) {  // (block-uniform: every wave made the same ballot)
+        if (threadIdx.x == 0) {
+            sh.last = static_cast<unsigned>(todo);
+            sh.todo_hi = static_cast<unsigned>(todo >> 32);
+        }
+        for (;;) {
+            __syncthreads();  // the bits are written; the previous descriptor's last reads of sh.keys / sh.fxy
+            const unsigned lo = __builtin_amdgcn_readfirstlane(sh.last), hi = __builtin_amdgcn_readfirstlane(sh.todo_hi);
+            const unsigned long long t = static_cast<unsigned long long>(hi) << 32 | lo;
+            if (t == 0ull) {
+                break;
+            }
+            __syncthreads();  // every wave has read them
+            if (threadIdx.x == 0) {
+                const unsigned long long rest = t & (t - 1ull);
+                sh.last = static_cast<unsigned>(rest);
+                sh.todo_hi = static_cast<unsigned>(rest >> 32);
+            }
+            body(p.list_descs + (blockIdx.x - p.list_descs) * p.empty_group + static_cast<unsigned>(__builtin_ctzll(t)),
+                 std::true_type{});
+        }
+    }
+#ifdef SRT_DIAG
+    // A sweep block's row: [8] start / [9] end, [10] tiles filled, [11] tiles traced, [12] flag 8.
+    if (sweeping && threadIdx.x == 0 && d_blk < kDiagBlocks) {
+        unsigned long long* dg = g_srt_diag[d_blk];
+        dg[8] = d_rt0;
+        dg[9] = __builtin_amdgcn_s_memrealtime();
+        dg[10] = swept;
+        dg[11] = d_traced;
+        dg[12] = kItemSweep | static_cast<unsigned long long>(blockIdx.z) << 32;
+    }
+#endif
 #undef SRT_DIAG_END
 }
 
@@ -5068,7 +5213,7 @@ hipError_t LaunchCullFrames(const CullFrame* frames, std::size_t count, std::uin
 
 namespace {
 struct SetupSizes {
-    std::size_t counts, range_tag, work_count, stream_count, info, screen_boxes, qboxes, cull, lists, large, work;
+    std::size_t counts, range_tag, work_count, stream_count, info, screen_boxes, qboxes, cull, lists, large, work, work_tmp;
 };
 SetupSizes CullSetupSizes(std::uint64_t n, std::size_t width, std::size_t height, unsigned descs) {
     const std::size_t tiles = CullTiles(width, height), n_pad = PaddedTriangleCount(n);
@@ -5085,6 +5230,7 @@ SetupSizes CullSetupSizes(std::uint64_t n, std::size_t width, std::size_t height
     z.lists = al(tiles * static_cast<std::size_t>(CullBinCapacity(n, tiles)) * 4);
     z.large = al(n_pad * 4);
     z.work = al(static_cast<std::size_t>(descs) * 2 * sizeof(uint4));
+    z.work_tmp = z.work;  // StreamPlanKernel's partition
     return z;
 }
 }  // namespace
@@ -5092,7 +5238,7 @@ SetupSizes CullSetupSizes(std::uint64_t n, std::size_t width, std::size_t height
 std::size_t CullSetupBytes(std::uint64_t n, std::size_t width, std::size_t height, unsigned descs) {
     const SetupSizes z = CullSetupSizes(n, width, height, descs);
     return z.counts + z.range_tag + z.work_count + z.stream_count + z.info + z.screen_boxes + z.qboxes + z.cull +
-           z.lists + z.large + z.work;
+           z.lists + z.large + z.work + z.work_tmp;
 }
 
 CullSetup CullSetupLayout(void* base, std::uint64_t n, std::size_t width, std::size_t height, unsigned descs,
@@ -5119,6 +5265,7 @@ CullSetup CullSetupLayout(void* base, std::uint64_t n, std::size_t width, std::s
     s.lists = reinterpret_cast<unsigned*>(take(z.lists));
     s.large_list = reinterpret_cast<unsigned*>(take(z.large));
     s.work = take(z.work);
+    s.work_tmp = take(z.work_tmp);
     s.tiles = CullTiles(width, height);
     s.capacity = CullBinCapacity(n, s.tiles);
     s.descs = descs;
@@ -5217,12 +5364,57 @@ __device__ __forceinline__ unsigned StreamRange(const uint4 w0, const uint4 w1, 
 // One block: an exclusive prefix over the descriptors' record counts (each rounded up to an even
 // count: 128-B range starts), the offsets into the descriptors' w1.x and their counts into w1.y (a
 // trace block then needs no division before its first loads), the total into *stream_count.
-__global__ __launch_bounds__(kPlanBlock) void StreamPlanKernel(uint4* work, unsigned descs,
+// Before that, the empty sweep's order (TraceCullKernel): a stable partition of the used descriptors
+// into those without kItemEmpty, in their longest-first order, then the kItemEmpty ones; the end
+// marks already come last. The counts of the two classes go into stream_count[1] (low word: list
+// descriptors, high word: empty ones), with `partition` or without. Stable, so a split part's chunks
+// stay consecutive and so do the parts of a tile (a tile's descriptors share their flags, and an
+// empty part is never split): the `d - part * nch` relation below and PackStreamKernel hold as before.
+// Through `tmp` (descs descriptors) and back: one block, the copies ordered by barriers.
+__global__ __launch_bounds__(kPlanBlock) void StreamPlanKernel(uint4* work, uint4* tmp, unsigned descs, bool partition,
                                                                unsigned long long* stream_count) {
     __shared__ unsigned long long sums[kPlanBlock];
     const unsigned tid = threadIdx.x;
     const unsigned per = (descs + kPlanBlock - 1u) / kPlanBlock;
     const unsigned d_lo = min(tid * per, descs), d_hi = min(d_lo + per, descs);
+    {
+        unsigned long long mine = 0ull;  // low word: list descriptors of [d_lo, d_hi), high word: empty ones
+        for (unsigned d = d_lo; d < d_hi; ++d) {
+            const uint4 w0 = work[2 * d];
+            mine += w0.x == kWorkEnd ? 0ull : (w0.w & kItemEmpty) != 0u ? 1ull << 32 : 1ull;
+        }
+        sums[tid] = mine;
+        __syncthreads();
+        for (unsigned o = 1u; o < kPlanBlock; o <<= 1) {
+            const unsigned long long v = tid >= o ? sums[tid - o] : 0ull;
+            __syncthreads();
+            sums[tid] += v;
+            __syncthreads();
+        }
+        const unsigned long long total = sums[kPlanBlock - 1];
+        const unsigned long long before = sums[tid] - mine;
+        __syncthreads();  // (sums is reused below)
+        if (tid == 0) {
+            stream_count[1] = total;
+        }
+        const unsigned lists = static_cast<unsigned>(total), used = lists + static_cast<unsigned>(total >> 32);
+        if (partition && lists != used) {  // (block-uniform)
+            unsigned at_list = static_cast<unsigned>(before), at_empty = lists + static_cast<unsigned>(before >> 32);
+            for (unsigned d = d_lo; d < d_hi; ++d) {
+                const uint4 w0 = work[2 * d];
+                if (w0.x != kWorkEnd) {
+                    const unsigned to = (w0.w & kItemEmpty) != 0u ? at_empty++ : at_list++;
+                    tmp[2 * to] = w0;
+                    tmp[2 * to + 1] = work[2 * d + 1];
+                }
+            }
+            __syncthreads();
+            for (unsigned i = tid; i < 2u * used; i += kPlanBlock) {
+                work[i] = tmp[i];
+            }
+            __syncthreads();
+        }
+    }
     auto owned = [&](unsigned d) -> unsigned {  // records descriptor d adds to the stream
         const uint4 w0 = work[2 * d];
         if (w0.x == kWorkEnd || w0.x % kParts != 0u) {
@@ -5299,9 +5491,13 @@ __global__ __launch_bounds__(kPackBlock) void PackStreamKernel(const uint4* __re
 }
 }  // namespace
 
+unsigned SharedTraceBlocks(unsigned descs, unsigned list_descs, unsigned empty_descs, unsigned group) {
+    return group == 0u ? descs : list_descs + (empty_descs + group - 1u) / group;
+}
+
 hipError_t LaunchStreamPlan(const CullSetup& s, hipStream_t stream) {
-    hipLaunchKernelGGL(StreamPlanKernel, dim3(1), dim3(kPlanBlock), 0, stream, static_cast<uint4*>(s.work), s.descs,
-                       s.stream_count);
+    hipLaunchKernelGGL(StreamPlanKernel, dim3(1), dim3(kPlanBlock), 0, stream, static_cast<uint4*>(s.work),
+                       static_cast<uint4*>(s.work_tmp), s.descs, s.sweep, s.stream_count);
     return hipGetLastError();
 }
 
@@ -5320,6 +5516,7 @@ namespace {
 template <class TB, class BB>
 void LaunchSharedStages(const TB& tb, const BB& bb, unsigned z, unsigned gx, unsigned gy, bool recompute,
                         bool streamed, unsigned descs, hipStream_t stream, const StageEvents& ev) {
+    // (descs: the trace grid -- the plan's room, or SharedTraceBlocks with the empty sweep)
     Launch(TileInfoKernel<BB, true>, dim3(gx, (gy + kInfoTiles - 1) / kInfoTiles, z), dim3(kBinThreads), stream,
            ev.bin_begin, ev.bin_end, bb);
     if (recompute) {
@@ -5349,6 +5546,11 @@ hipError_t LaunchSharedCullFrames(const CullFrame* frames, std::size_t count, co
         setup.tiles != CullTiles(band0.width, band0.row_count)) {
         return hipErrorInvalidValue;  // whole frames of the setup's shape only
     }
+    if (setup.sweep && (setup.empty_group == 0u || setup.empty_group > kMaxEmptyGroup ||
+                        setup.list_descs + setup.empty_descs > setup.descs)) {
+        return hipErrorInvalidValue;  // (a sweep block has one lane per descriptor of its group)
+    }
+    const unsigned group = setup.sweep ? setup.empty_group : 0u;
     const StageEvents ev = events != nullptr ? *events : StageEvents{};
     TraceBatch tb{};
     BinBatch bb{};
@@ -5383,6 +5585,9 @@ hipError_t LaunchSharedCullFrames(const CullFrame* frames, std::size_t count, co
         p.large_list = setup.large_list;
         p.bin_capacity = setup.capacity;
         p.stream = static_cast<const CullRecord*>(setup.stream);
+        p.list_descs = setup.list_descs;
+        p.empty_descs = setup.empty_descs;
+        p.empty_group = group;
         BinParams& b = bp[i];
         b = BinParams{};
         b.offsets = p.offsets;
@@ -5400,8 +5605,14 @@ hipError_t LaunchSharedCullFrames(const CullFrame* frames, std::size_t count, co
     const unsigned z = static_cast<unsigned>(count);
     const unsigned gx = static_cast<unsigned>(tp[0].tiles_x), gy = tp[0].tiles / gx;
     const bool streamed = setup.stream != nullptr && !setup.recompute;
+    unsigned blocks = std::max(SharedTraceBlocks(setup.descs, setup.list_descs, setup.empty_descs, group), 1u);
+#ifdef SRT_EXP_SKIP_EMPTY
+    // Measurement build only (make exp): no sweep blocks, the empty tiles stay unwritten -- wrong
+    // frames, the upper bound of what the empty sweep can gain (profiles/empty_sweep/README.md).
+    blocks = group != 0u ? std::max(setup.list_descs, 1u) : blocks;
+#endif
     if (!use_table) {
-        LaunchSharedStages(tb, bb, z, gx, gy, setup.recompute, streamed, setup.descs, stream, ev);
+        LaunchSharedStages(tb, bb, z, gx, gy, setup.recompute, streamed, blocks, stream, ev);
         return hipGetLastError();
     }
     if (table->host_device != nullptr) {
@@ -5423,7 +5634,7 @@ hipError_t LaunchSharedCullFrames(const CullFrame* frames, std::size_t count, co
     unsigned char* dev = static_cast<unsigned char*>(table->device);
     const BinTable bt{(ConstantPtr<BinParams>)(dev + lay.bin)};
     const TraceTable tt{(ConstantPtr<TraceParams>)(dev + lay.trace)};
-    LaunchSharedStages(tt, bt, z, gx, gy, setup.recompute, streamed, setup.descs, stream, ev);
+    LaunchSharedStages(tt, bt, z, gx, gy, setup.recompute, streamed, blocks, stream, ev);
     return hipGetLastError();
 }
 

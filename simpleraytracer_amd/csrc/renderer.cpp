@@ -719,6 +719,34 @@ bool TraceStreamFromEnv() {
     return v == "1";
 }
 
+// SRT_EMPTY_SWEEP = 1 (default) | 0, read per call (like SRT_TRACE_STREAM) and part of the setup's
+// key: whether the shared setup's plan lists its statically empty descriptors last and the traces
+// sweep them in groups (render.h CullSetup::sweep); 0 keeps one trace block per descriptor.
+bool EmptySweepFromEnv() {
+    const char* e = std::getenv("SRT_EMPTY_SWEEP");
+    const std::string v = e == nullptr || *e == '\0' ? "1" : e;
+    if (v != "1" && v != "0") {
+        throw std::runtime_error("SRT_EMPTY_SWEEP must be 1 or 0, got '" + v + "'");
+    }
+    return v == "1";
+}
+
+// SRT_EMPTY_GROUP (measurements and tests), read per call: empty descriptors per sweep block instead
+// of kDefaultEmptyGroup. A launch parameter, not part of what is built.
+unsigned EmptyGroupFromEnv() {
+    const char* e = std::getenv("SRT_EMPTY_GROUP");
+    if (e == nullptr || *e == '\0') {
+        return kDefaultEmptyGroup;
+    }
+    char* end = nullptr;
+    const unsigned long long v = std::strtoull(e, &end, 10);
+    if (end == e || *end != '\0' || *e == '-' || v == 0 || v > kMaxEmptyGroup) {
+        throw std::runtime_error("SRT_EMPTY_GROUP must be 1 to " + std::to_string(kMaxEmptyGroup) + ", got '" +
+                                 std::string(e) + "'");
+    }
+    return static_cast<unsigned>(v);
+}
+
 // SRT_TRACE_STREAM_CAP (tests only): the longest record stream, in records, instead of
 // kStreamCapRecords -- forces the indexed fallback at small sizes, as SRT_CULL_BIN_CAP forces list overflow.
 std::size_t StreamCapFromEnv() {
@@ -777,9 +805,10 @@ void DeviceScene::LogSetupStats() const {
     }
     std::fprintf(stderr,
                  "srt setup: scene %p builds %llu shared_frames %llu per_frame_frames %llu stream_frames %llu "
-                 "stream_records %llu\n",
+                 "stream_records %llu empty_descs %llu sweep_blocks %llu\n",
                  static_cast<const void*>(this), m_setup_stats.builds, m_setup_stats.shared_frames,
-                 m_setup_stats.per_frame_frames, m_setup_stats.stream_frames, m_setup_stats.stream_records);
+                 m_setup_stats.per_frame_frames, m_setup_stats.stream_frames, m_setup_stats.stream_records,
+                 m_setup_stats.empty_descs, m_setup_stats.sweep_blocks);
     std::fflush(stderr);
 }
 
@@ -806,6 +835,10 @@ void DeviceScene::TraceShared(const float* const* d_offsets, float* const* d_rgb
                               d_ids != nullptr ? d_ids[f] : nullptr, 1, id_planes, rgba_frame_rows};
     }
     const CullSetup setup = EnsureSetup(bins[0].descs, stream);
+    // (the last trace's grid: sweep blocks per frame, 0 with the sweep off)
+    m_setup_stats.sweep_blocks =
+        setup.sweep ? SharedTraceBlocks(setup.descs, setup.list_descs, setup.empty_descs, setup.empty_group) - setup.list_descs
+                    : 0;
     const StageEvents ev = BindStageEvents(false, true);
     ParamTable* table = frames > static_cast<std::size_t>(kMaxBatch) ? &AcquireTable(frames, stream) : nullptr;
     const CullTable ct{table != nullptr ? table->device : nullptr, table != nullptr ? table->host : nullptr,
@@ -844,25 +877,32 @@ CullSetup DeviceScene::EnsureSetup(unsigned descs, hipStream_t stream) const {
     CullSetup setup = CullSetupLayout(m_setup, m_n, m_width, m_height, descs, recompute);
     // The record stream is for stored records; its cap is part of the key (a test lowers it).
     const bool want_stream = TraceStreamFromEnv() && !recompute;
+    setup.sweep = EmptySweepFromEnv();
+    setup.empty_group = EmptyGroupFromEnv();
     const SetupKey key{m_width,         m_height,    setup.capacity, setup.descs,
-                       setup.min_chunk, setup.recompute, want_stream,    want_stream ? StreamCapFromEnv() : 0};
+                       setup.min_chunk, setup.recompute, want_stream,    want_stream ? StreamCapFromEnv() : 0,
+                       setup.sweep};
     const SetupKey& k = m_setup_key;
     if (m_setup_pending || key.width != k.width || key.height != k.height || key.capacity != k.capacity ||
         key.descs != k.descs || key.min_chunk != k.min_chunk || key.recompute != k.recompute ||
-        key.stream != k.stream || key.stream_cap != k.stream_cap) {
+        key.stream != k.stream || key.stream_cap != k.stream_cap || key.sweep != k.sweep) {
         m_setup_pending = true;  // (a failed build leaves none)
         m_stream_on = false;
         m_stream_records = 0;
         HipCheck(LaunchCullSetup(setup, m_n, m_frame, m_width, m_height, m_order, m_svertices, stream),
                  "cull setup launch");
+        // The stream's length and the plan's list and empty descriptor counts are known only from
+        // the built plan: one host read per build (never per frame), with a stream or without.
+        unsigned long long plan[2] = {0, 0};
+        HipCheck(LaunchStreamPlan(setup, stream), "record stream plan launch");
+        HipCheck(hipMemcpyAsync(plan, setup.stream_count, sizeof(plan), hipMemcpyDeviceToHost, stream),
+                 "hipMemcpyAsync(plan counts)");
+        HipCheck(hipStreamSynchronize(stream), "hipStreamSynchronize(plan counts)");
+        m_list_descs = static_cast<unsigned>(plan[1]);
+        m_empty_descs = static_cast<unsigned>(plan[1] >> 32);
         if (want_stream) {
-            // The stream's length is known only from the built plan: one host read per build (never
-            // per frame). Over the cap, this setup's frames keep the indexed path.
-            unsigned long long records = 0;
-            HipCheck(LaunchStreamPlan(setup, stream), "record stream plan launch");
-            HipCheck(hipMemcpyAsync(&records, setup.stream_count, sizeof(records), hipMemcpyDeviceToHost, stream),
-                     "hipMemcpyAsync(record stream length)");
-            HipCheck(hipStreamSynchronize(stream), "hipStreamSynchronize(record stream length)");
+            // Over the cap, this setup's frames keep the indexed path.
+            const unsigned long long records = plan[0];
             if (records <= key.stream_cap) {
                 const std::size_t need = std::max<std::size_t>(static_cast<std::size_t>(records), 2);
                 if (need > m_stream_capacity) {
@@ -882,8 +922,11 @@ CullSetup DeviceScene::EnsureSetup(unsigned descs, hipStream_t stream) const {
         m_setup_pending = false;
         ++m_setup_stats.builds;
         m_setup_stats.stream_records = m_stream_records;
+        m_setup_stats.empty_descs = m_empty_descs;
     }
     setup.stream = m_stream_on ? m_stream : nullptr;
+    setup.list_descs = m_list_descs;
+    setup.empty_descs = m_empty_descs;
     return setup;
 }
 

@@ -198,6 +198,8 @@ public:
         // read per call; default 1), and the records of the stream now standing (0: none).
         unsigned long long stream_frames = 0;
         unsigned long long stream_records = 0;
+        unsigned long long empty_descs = 0;   // statically empty descriptors of the standing setup's plan
+        unsigned long long sweep_blocks = 0;  // sweep blocks per frame of the last shared trace (0: sweep off)
     };
     SetupStats setup_stats() const { return m_setup_stats; }
 
@@ -232,6 +234,7 @@ private:
         bool recompute = false;
         bool stream = false;         // the record stream was asked for (SRT_TRACE_STREAM, stored records)
         std::size_t stream_cap = 0;  // ... up to this many records (a longer one: the indexed path)
+        bool sweep = false;          // the plan is in the empty sweep's order (SRT_EMPTY_SWEEP)
     };
     mutable unsigned char* m_setup = nullptr;
     mutable std::size_t m_setup_bytes = 0;
@@ -241,6 +244,7 @@ private:
     mutable std::size_t m_stream_capacity = 0;  // records allocated
     mutable std::size_t m_stream_records = 0;
     mutable bool m_stream_on = false;
+    mutable unsigned m_list_descs = 0, m_empty_descs = 0;  // the standing setup's plan (render.h CullSetup)
     mutable bool m_setup_pending = true;
     mutable SetupKey m_setup_key{};
     mutable SetupStats m_setup_stats{};

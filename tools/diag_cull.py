@@ -75,7 +75,7 @@ def main():
     start = (b[:, 8] - t0) / 100.0  # us
     end = (b[:, 9] - t0) / 100.0
     dur = end - start
-    info = buf[ran, 11]
+    info = np.where(buf[ran, 12] & 8 != 0, np.uint64(0), buf[ran, 11])  # (a sweep block's row: no work item)
     chunk, nch, last = info & 0xFFFF, (info >> 16) & 0xFFFF, (info >> 32) & 1
     item = buf[ran, 10]
     summary = {"frame": f"{w}x{h}, {tri} triangles, offsets {os.environ.get('OFFSETS', 'uniform')}",
@@ -114,13 +114,19 @@ def main():
             wk = b[sel, 2] / 2400.0
             summary["phases_us"][name] = {"blocks": int(sel.sum()), "dur": stats(dur[sel]), "gather": stats(g),
                                           "walk": stats(wk), "rest": stats(dur[sel] - g - wk)}
-    # block classes by work-item flags (render.hip kItemRegular 1, kItemFull 2, kItemEmpty 4)
+    # block classes by work-item flags (render.hip kItemRegular 1, kItemFull 2, kItemEmpty 4; kItemSweep 8:
+    # a block of the sweep launch, whose row holds its lifetime, the tiles it filled and those it traced)
     fl = buf[ran, 12] & 0xFFFFFFFF
-    classes = {"empty": (fl & 4) != 0, "full": ((fl & 2) != 0) & ((fl & 4) == 0),
-               "list_whole": ((fl & 6) == 0) & (nch <= 1), "list_split": ((fl & 6) == 0) & (nch > 1)}
+    sweep = (fl & 8) != 0
+    classes = {"empty": (fl & 12) == 4, "full": (fl & 14) == 2,
+               "list_whole": ((fl & 14) == 0) & (nch <= 1), "list_split": ((fl & 14) == 0) & (nch > 1), "sweep": sweep}
     summary["classes"] = {k: {"blocks": int(v.sum()), "dur_us": stats(dur[v]),
                               "gather_us": stats(b[v, 1] / 2400.0), "walk_us": stats(b[v, 2] / 2400.0)}
                           for k, v in classes.items() if v.any()}
+    if sweep.any():
+        summary["classes"]["sweep"].update({"tiles_filled": stats(b[sweep, 10]), "tiles_traced": stats(b[sweep, 11]),
+                                            "first_start_us": round(float(start[sweep].min()), 2)})
+        summary["span_without_sweep_us"] = round(float(end[~sweep].max()), 2)
     slots = int(os.environ.get("SLOTS", "1536"))
     summary["occupancy"] = {"block_us": round(float(dur.sum()), 1), "slots": slots,
                             "busy_frac": round(float(dur.sum() / (end.max() * slots)), 3),
