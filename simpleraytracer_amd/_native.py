@@ -100,6 +100,41 @@ class RtgOutputs(ctypes.Structure):
     ]
 
 
+RTD_MAX_LIGHTS = 8   # include/srt_lighting.h: lights per rtdLightAsync / rtdLightHost call
+RTD_MAX_FRAMES = 16  # light frames per call: 1 per spot light, 6 per point light
+
+
+class RtdLight(ctypes.Structure):
+    """``rtd_light`` (include/srt_lighting.h): exactly one of spot / point is non-NULL."""
+
+    _fields_ = [
+        ("struct_size", ctypes.c_size_t),
+        ("spot", ctypes.c_void_p),
+        ("point", ctypes.c_void_p),
+        ("color", ctypes.c_float * 3),
+        ("falloff", ctypes.c_float),
+        ("bias", ctypes.c_float),
+    ]
+
+
+class RtdLightHost(ctypes.Structure):
+    """``rtd_light_host`` (include/srt_lighting.h): kind 0 spot (camera10, width, height), 1 point
+    (origin, face_size)."""
+
+    _fields_ = [
+        ("struct_size", ctypes.c_size_t),
+        ("kind", ctypes.c_int),
+        ("camera10", ctypes.c_float * 10),
+        ("width", ctypes.c_size_t),
+        ("height", ctypes.c_size_t),
+        ("origin", ctypes.c_float * 3),
+        ("face_size", ctypes.c_size_t),
+        ("color", ctypes.c_float * 3),
+        ("falloff", ctypes.c_float),
+        ("bias", ctypes.c_float),
+    ]
+
+
 _SZ = ctypes.c_size_t
 _PSZ = ctypes.POINTER(ctypes.c_size_t)
 _PD = ctypes.POINTER(ctypes.c_double)
@@ -216,6 +251,12 @@ _SIGNATURES = {
                                      ctypes.c_void_p, ctypes.c_float]),
     "rtoFaceCameraHost": (ctypes.c_int, [ctypes.POINTER(ctypes.c_float), ctypes.c_int, ctypes.POINTER(ctypes.c_float)]),
     "rtoFaceOfHost": (ctypes.c_int, [ctypes.POINTER(ctypes.c_float)]),
+    # include/srt_lighting.h: direct lighting (lights: an array of RtdLight / RtdLightHost, or None; ambient: 3 floats)
+    "rtdLightAsync": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, _SZ, ctypes.POINTER(ctypes.c_float),
+                                     ctypes.c_void_p, ctypes.c_void_p, _SZ, _SZ, ctypes.c_void_p, ctypes.c_void_p,
+                                     ctypes.c_void_p]),
+    "rtdLightHost": (ctypes.c_int, [ctypes.c_char_p, _SZ, _SZ, ctypes.c_void_p, _SZ, ctypes.POINTER(ctypes.c_float),
+                                    ctypes.c_void_p, ctypes.c_void_p, _SZ, _SZ, ctypes.c_void_p, ctypes.c_void_p]),
     # include/srt_layers.h: depth layers and their over-composite
     "rtkLayersAsync": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, _SZ, _SZ, ctypes.c_void_p, ctypes.c_void_p,
                                       ctypes.c_void_p, ctypes.c_void_p]),

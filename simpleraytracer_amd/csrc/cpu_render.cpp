@@ -2,6 +2,7 @@
 
 #include "gbuffer_math.h"
 #include "layers_math.h"
+#include "lighting_math.h"
 #include "omni_math.h"
 #include "samples_math.h"
 #include "screen_box.h"
@@ -554,6 +555,115 @@ void HostOmniShadow(const Scene& scene, std::size_t width, std::size_t height, c
         if (rgba != nullptr) {
             std::copy(out, out + 4, rgba + 4 * i);
         }
+    });
+}
+
+void HostLighting(const Scene& scene, std::size_t width, std::size_t height, const HostLight* lights, std::size_t count,
+                  const float ambient[3], const float* offsets, const int* ids, std::size_t row_begin,
+                  std::size_t row_count, float* rgba, unsigned char* classes) {
+    if (width == 0 || height == 0) {
+        throw std::runtime_error("Host lighting: frame dimensions must be non-zero");
+    }
+    if (row_begin > height || row_count > height - row_begin) {
+        throw std::runtime_error("Host lighting: row band outside the frame");
+    }
+    const Frame f = MakeFrame(scene.camera, width, height);
+    const std::size_t n = scene.triangle_count();
+    // Every light's frames (1 or 6), their projection rows and every triangle's record under each.
+    struct LightFrame {
+        Frame frame;
+        float rows[9];
+        std::vector<Rec> recs;
+    };
+    std::vector<LightFrame> frames;
+    std::vector<std::size_t> first(count);
+    for (std::size_t l = 0; l < count; ++l) {
+        const HostLight& in = lights[l];
+        first[l] = frames.size();
+        const int faces = in.point ? kOmniFaces : 1;
+        for (int k = 0; k < faces; ++k) {
+            LightFrame lf;
+            lf.frame = in.point ? MakeFrame(OmniFaceCameraOf(in.origin, k), in.face_size, in.face_size)
+                                : MakeFrame(in.camera, in.width, in.height);
+            ShadowProjectionRows(lf.frame.base, lf.frame.du, lf.frame.dv, lf.rows);
+            lf.recs.resize(n);
+            Rec* out = lf.recs.data();
+            const Frame& fr = lf.frame;
+            ParallelFor(n, 1024, [&](std::size_t i) { out[i] = MakeRecord(scene.vertices.data() + 9 * i, fr); });
+            frames.push_back(std::move(lf));
+        }
+    }
+    const float wf = static_cast<float>(width), hf = static_cast<float>(height);
+    const float inf = std::numeric_limits<float>::infinity();
+    const std::size_t plane = row_count * width;
+    ParallelFor(plane, 64, [&](std::size_t i) {
+        const std::size_t x = i % width, y = row_begin + i / width;
+        const int id = ids[i];
+        const float fx = (static_cast<float>(x) + offsets[2 * i]) / wf;
+        const float fy = (static_cast<float>(y) + offsets[2 * i + 1]) / hf;
+        const bool surface = id >= 0 && static_cast<std::size_t>(id) < n;
+        float out[4] = {scene.background[0], scene.background[1], scene.background[2], -1.f};
+        if (!surface) {
+            for (std::size_t l = 0; l < count && classes != nullptr; ++l) {
+                classes[l * plane + i] = kShadowNoSurface;
+            }
+            std::copy(out, out + 4, rgba + 4 * i);
+            return;
+        }
+        const Rec r = MakeRecord(scene.vertices.data() + 9 * static_cast<std::size_t>(id), f);
+        const float t = ShadowDepth(r.c, r.vol, fx, fy);
+        float d[3], p[3];
+        LightingPoint(f.origin, f.base, f.du, f.dv, fx, fy, t, d, p);
+        const float nn = ShadowDot(r.n, r.n), nd = ShadowDot(r.n, d);
+        float e[3] = {ambient[0], ambient[1], ambient[2]};
+        for (std::size_t l = 0; l < count; ++l) {
+            const HostLight& in = lights[l];
+            const float* origin = frames[first[l]].frame.origin;
+            float q[3];
+            for (int k = 0; k < 3; ++k) {
+                q[k] = p[k] - origin[k];
+            }
+            const LightFrame& lf = frames[first[l] + (in.point ? static_cast<std::size_t>(OmniFace(q)) : 0)];
+            const ShadowPoint sp = ShadowProjectOffset(q, lf.rows, in.bias);
+            unsigned char cls = kShadowOutside;
+            if (sp.inside) {
+                float best = inf;
+                int lid = -1;
+                for (std::size_t k = 0; k < n; ++k) {  // ascending ids: strict < keeps the lowest on ties
+                    const float* c = lf.recs[k].c;
+                    const float eA = std::fma(sp.gy, c[2], std::fma(sp.gx, c[1], c[0]));
+                    const float eB = std::fma(sp.gy, c[5], std::fma(sp.gx, c[4], c[3]));
+                    const float eC = std::fma(sp.gy, c[8], std::fma(sp.gx, c[7], c[6]));
+                    if (eA >= 0.f && eB >= 0.f && eC >= 0.f) {
+                        const float det = (eA + eB) + eC;
+                        if (det > 0.f) {
+                            const float tt = lf.recs[k].vol / det;
+                            if (tt < best) {
+                                best = tt;
+                                lid = static_cast<int>(k);
+                            }
+                        }
+                    }
+                }
+                cls = ShadowClass(id, lid, best, sp.thr);
+            }
+            if (classes != nullptr) {
+                classes[l * plane + i] = cls;
+            }
+            const float nl = ShadowDot(r.n, q);
+            if (cls == kShadowLit && LightingFacing(nl, nd)) {
+                const float w = LightingWeight(nl, nn, ShadowDot(q, q), in.falloff);
+                for (int k = 0; k < 3; ++k) {
+                    e[k] = e[k] + in.color[k] * w;
+                }
+            }
+        }
+        const float* a = scene.albedo.data() + 3 * static_cast<std::size_t>(id);
+        out[0] = a[0] * e[0];
+        out[1] = a[1] * e[1];
+        out[2] = a[2] * e[2];
+        out[3] = static_cast<float>(id);
+        std::copy(out, out + 4, rgba + 4 * i);
     });
 }
 

@@ -78,6 +78,24 @@ void HostOmniShadow(const Scene& scene, std::size_t width, std::size_t height, c
 // Face `face` (0 .. 5) of the light at `origin` as a camera (omni_math.h OmniFaceCamera).
 Camera OmniFaceCameraOf(const float origin[3], int face);
 
+// Direct lighting (lighting_math.h; the host answer of render.h LaunchLighting): the lit RGBA of the
+// band under `count` lights of the same triangles, a spot light being `camera` at width x height, a
+// point light `origin` with six face_size x face_size cube faces. offsets, ids: HostShadow's; rgba
+// (row_count x width x 4); classes (count x row_count x width, light-major) may be null. Every light
+// frame's closest hit by brute force over every record.
+struct HostLight {
+    bool point;
+    Camera camera;              // spot
+    std::size_t width, height;  // spot
+    float origin[3];            // point
+    std::size_t face_size;      // point
+    float color[3];
+    float falloff, bias;
+};
+void HostLighting(const Scene& scene, std::size_t width, std::size_t height, const HostLight* lights, std::size_t count,
+                  const float ambient[3], const float* offsets, const int* ids, std::size_t row_begin,
+                  std::size_t row_count, float* rgba, unsigned char* classes);
+
 // The light frame's projection rows (px, py, pz) as HostShadow and LaunchShadow compute them.
 void HostShadowRows(const Camera& light_camera, std::size_t light_width, std::size_t light_height, float rows[9]);
 

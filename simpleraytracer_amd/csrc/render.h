@@ -480,6 +480,39 @@ hipError_t LaunchOmniShadow(const float* d_vertices, const float* d_shade, std::
                             const float background[3], const ShadowLight faces[6], const ShadowArgs& args,
                             unsigned char* d_face, hipStream_t stream);
 
+// Direct lighting (render.hip LightingKernel; lighting_math.h; DESIGN.md section 2 "Lighting"): the
+// lit RGBA of every pixel of a band of the view frame from its hit id under `count` (0 to
+// kLightingMaxLights) lights -- albedo . (ambient + the sum over the lights that reach the pixel from
+// the eye's side of its triangle of color . cosine . falloff / distance^2), alpha = float(id); an id
+// outside [0, n): the background, alpha -1. A spot light is one ShadowLight frame, a point light six
+// (LaunchOmniShadow's faces); at most kLightingMaxFrames in a call, all of one record source. The
+// class a light gives a pixel is LaunchShadow's / LaunchOmniShadow's byte at that light's bias.
+struct LightingLight {
+    const ShadowLight* frames;  // 1 (spot) or 6 (point: one origin, one size)
+    bool point;
+    float color[3];
+    float falloff;  // finite, >= 0; 0: no distance term
+    float bias;     // finite, >= 0
+};
+struct LightingArgs {
+    // Band-local, as LaunchShade's: pixel (x, row_begin + y) of the width x height view frame.
+    const float* offsets;  // device, row_count x width x 2
+    const int* ids;        // device, row_count x width
+    std::size_t width;
+    std::size_t height;
+    std::size_t row_begin;
+    std::size_t row_count;
+    float ambient[3];
+    float* rgba;             // device, row_count x width x 4
+    unsigned char* classes;  // device, count x row_count x width (light-major), or null
+};
+// d_vertices, d_shade, n, frame, background: the view scene's (n: of every scene). One launch
+// whatever `count`; no rows: none. Without class planes a light on the far side of a pixel's
+// triangle is not scanned for it (it adds nothing): the RGBA is the same either way.
+hipError_t LaunchLighting(const float* d_vertices, const float* d_shade, std::uint64_t n, const Frame& frame,
+                          const float background[3], const LightingLight* lights, std::size_t count,
+                          const LightingArgs& args, hipStream_t stream);
+
 // G-buffer (render.hip GBufferKernel): the surface attributes of (image position, triangle id)
 // pairs of the frame -- depth, barycentrics, normal + shading cosine, albedo + id (gbuffer_math.h;
 // DESIGN.md section 2 "Surface attributes") -- from hit ids, a deferred pass like LaunchShade with

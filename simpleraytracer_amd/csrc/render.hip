@@ -6,6 +6,7 @@
 #include "render.h"
 #include "gbuffer_math.h"
 #include "layers_math.h"
+#include "lighting_math.h"
 #include "samples_math.h"
 #include "screen_box.h"
 #include "omni_math.h"
@@ -4401,6 +4402,214 @@ __global__ __launch_bounds__(kOmniThreads) void OmniShadowKernel(const OmniParam
 }
 
 // ---------------------------------------------------------------------------------------
+// Direct lighting (render.h LaunchLighting; lighting_math.h; DESIGN.md section 5 "Lighting"): the lit
+// pixel of a band under up to kLightingMaxLights spot and point lights, one launch. The pixel's
+// facts are computed once, as OmniShadowKernel computes them (ComputeEdges on the view scene's
+// vertices, the traces' bits: t, d, the surface point P) together with the shading-table row (N,
+// albedo: one 32-B line); every light then adds q = P - its origin, its frame -- frame `first` of a
+// spot light, first + OmniFace(q) of a point light -- ShadowProjectOffset in that frame (the frustum
+// test decides for a spot light and never fires for a selected cube face) and OmniShadowKernel's scan
+// there: the own triangle's (t_id, id) first, the bound min((thr, below every id), (t_id, id)), the
+// lanes striding the tile's list then the large list (every record where the frame has no usable
+// list), the group leaving at the end of the first round in which a lane took a candidate. A light
+// that reaches the pixel from the eye's side of the triangle adds color . w to E (lighting_math.h);
+// E stays in three registers across the lights.
+// The light frames (up to 16 OmniFaceParams, 168 B each) and the per-light table travel by value in
+// the kernel-argument segment: the light index is uniform (scalar loads), the frame index per lane
+// (vector loads from constant memory, OmniShadowKernel's pattern). No device table, no upload, no
+// LDS, no atomics, no scratch. Without class planes a light that is not facing is not scanned: it
+// cannot contribute. Lane 0 stores the float4 and, asked for, one class byte per light.
+// SRT_LIGHTING_LANES, SRT_LIGHTING_AHEAD: measurement builds (profiles/lighting/).
+// ---------------------------------------------------------------------------------------
+#ifndef SRT_LIGHTING_LANES
+#define SRT_LIGHTING_LANES 16
+#endif
+constexpr int kLightingLanes = SRT_LIGHTING_LANES;  // lanes per pixel (a divisor of the wave)
+#ifndef SRT_LIGHTING_AHEAD
+#define SRT_LIGHTING_AHEAD 2
+#endif
+constexpr int kLightingAhead = SRT_LIGHTING_AHEAD;  // candidates per lane and round
+constexpr int kLightingThreads = 256;
+constexpr int kLightingBlock = kLightingThreads / kLightingLanes;  // pixels per block
+static_assert(kLightingLanes >= 2 && kWave % kLightingLanes == 0, "a pixel's lanes share a wave");
+struct LightingLightParams {
+    float origin[3];
+    float color[3];
+    float falloff, bias;
+    unsigned first;  // its first light frame
+    unsigned point;  // 1: six frames, selected by OmniFace(q); 0: one
+};
+struct LightingParams {
+    OmniFaceParams frame[kLightingMaxFrames];
+    LightingLightParams light[kLightingMaxLights];
+    const float* __restrict__ vertices;  // the view scene's, by id
+    const float4* __restrict__ shade;    // the view scene's shading table
+    const float2* __restrict__ offsets;  // band-local
+    const int* __restrict__ ids;         // band-local
+    F4* __restrict__ rgba;
+    unsigned char* __restrict__ classes;  // null: not stored; else count planes of `pixels` bytes
+    unsigned n;  // triangles of every scene
+    unsigned width;
+    unsigned row_begin;
+    unsigned pixels;  // of the band
+    unsigned count;   // lights
+    float wf, hf;     // the view frame's
+    float eye[3], base[3], du[3], dv[3], bg[3], ambient[3];
+};
+static_assert(sizeof(LightingLightParams) == 40 && sizeof(LightingParams) == 3160 && sizeof(LightingParams) < 4096,
+              "the light frames and the light table travel in the kernel-argument segment (< 4 KB)");
+
+__device__ __forceinline__ bool LightingGroupAny(bool mine) {
+    const unsigned long long b = __ballot(mine);
+    if constexpr (kLightingLanes == kWave) {
+        return b != 0ull;
+    } else {
+        const unsigned first = (threadIdx.x & (kWave - 1)) & ~static_cast<unsigned>(kLightingLanes - 1);
+        return ((b >> first) & ((1ull << kLightingLanes) - 1ull)) != 0ull;
+    }
+}
+
+template <bool RC>
+__global__ __launch_bounds__(kLightingThreads) void LightingKernel(const LightingParams q) {
+    using Recs = OmniRecords<RC>;
+    const unsigned lane = threadIdx.x & (kLightingLanes - 1);
+    const unsigned pixel = blockIdx.x * kLightingBlock + threadIdx.x / kLightingLanes;
+    if (pixel >= q.pixels) {
+        return;
+    }
+    const int code = q.ids[pixel];
+    const float2 o = q.offsets[pixel];
+    const unsigned y = pixel / q.width, x = pixel - y * q.width;
+    const float fx = (static_cast<float>(x) + o.x) / q.wf;
+    const float fy = (static_cast<float>(q.row_begin + y) + o.y) / q.hf;
+    const bool surface = static_cast<unsigned>(code) < q.n;
+    // The pixel's facts, once for all lights.
+    float P[3] = {0.f, 0.f, 0.f}, N[3] = {0.f, 0.f, 0.f}, al[3] = {0.f, 0.f, 0.f};
+    float nn = 0.f, nd = 0.f;
+    if (surface) {
+        const float* at = q.vertices + 9ull * static_cast<unsigned>(code);
+        float v[9], c[9], vol;
+#pragma unroll
+        for (int j = 0; j < 9; ++j) {
+            v[j] = at[j];
+        }
+        ComputeEdges(q.eye, q.base, q.du, q.dv, v, true, c, vol);
+        const float t = ShadowDepth(c, vol, fx, fy);
+        float d[3];
+        LightingPoint(q.eye, q.base, q.du, q.dv, fx, fy, t, d, P);
+        const float4* sr = q.shade + 2ull * static_cast<unsigned>(code);
+        const float4 nr = sr[0], ar = sr[1];
+        N[0] = nr.x, N[1] = nr.y, N[2] = nr.z;
+        al[0] = ar.x, al[1] = ar.y, al[2] = ar.z;
+        nn = ShadowDot(N, N);
+        nd = ShadowDot(N, d);
+    }
+    float e0 = q.ambient[0], e1 = q.ambient[1], e2 = q.ambient[2];
+    for (unsigned l = 0u; l < q.count; ++l) {
+        const LightingLightParams& lt = q.light[l];
+        unsigned char cls = kShadowNoSurface;
+        if (surface) {
+            float off[3];
+#pragma unroll
+            for (int k = 0; k < 3; ++k) {
+                off[k] = P[k] - lt.origin[k];
+            }
+            const float nl = ShadowDot(N, off);
+            const bool facing = LightingFacing(nl, nd);
+            cls = kShadowOutside;
+            if (facing || q.classes != nullptr) {  // (a light that is not facing adds nothing)
+                const unsigned fi = lt.first + (lt.point != 0u ? static_cast<unsigned>(OmniFace(off)) : 0u);
+                const OmniFaceParams& f = q.frame[fi];
+                const ShadowPoint sp = ShadowProjectOffset(off, f.rows, lt.bias);
+                if (sp.inside) {
+                    Rays<1> s;
+                    s.fx[0] = sp.gx;
+                    s.fy[0] = sp.gy;
+                    s.bt[0] = __builtin_inff();
+                    s.bi[0] = -1;
+                    int col = 0, row = 0;
+                    const TileInfo* tile_info = f.tile_info;
+                    bool listed = tile_info != nullptr && TileOfPosition(sp.gx, sp.gy, f.wf, f.hf, kCullTileCols, kTileRows,
+                                                                         f.tiles_x, f.tiles_y, col, row);
+                    unsigned cnt = 0u, large = 0u, capacity = 0u;
+                    const unsigned* list = nullptr;
+                    const unsigned* large_list = nullptr;
+                    if (listed) {
+                        const unsigned tile =
+                            static_cast<unsigned>(row) * static_cast<unsigned>(f.tiles_x) + static_cast<unsigned>(col);
+                        const unsigned* counts = f.bin_counts;
+                        capacity = f.bin_capacity;
+                        cnt = counts[tile];
+                        large = counts[f.tiles];
+                        list = f.bin_lists + static_cast<size_t>(tile) * capacity;
+                        large_list = f.large_list;
+                        listed = cnt <= capacity && tile_info[tile].usable != 0u;
+                    }
+                    const unsigned total = listed ? cnt + large : f.stream_end;
+                    auto entry = [&](unsigned k) {
+                        if (!listed) {
+                            return k;
+                        }
+                        const unsigned* at = k < cnt ? list + k : large_list + (k - cnt);
+                        return *at;
+                    };
+                    auto test = [&](const typename Recs::Raw& raw) {
+                        const auto r = Recs::Make(f, q.n, raw);
+                        const Record rec{r.a.x, r.a.y, r.a.z, r.a.w, r.b.x, r.b.y, r.b.z, r.b.w, r.x.x};
+                        ExactTestAnyOrder<1, false>(s, rec, r.x.y, static_cast<int>(__float_as_uint(r.x.z)));
+                    };
+                    // The own triangle under the frame's records: (t_id, id), or (+inf, -1) if it does not pass.
+                    test(Recs::Load(f, q.n, f.rank[static_cast<unsigned>(code)]));
+                    if (sp.thr <= s.bt[0]) {  // the bound: (thr, below every id) or (t_id, id), whichever is lower
+                        s.bt[0] = sp.thr;
+                        s.bi[0] = static_cast<int>(0x80000000u);
+                    }
+                    const int bound_id = s.bi[0];
+                    bool occluded = false;
+                    for (unsigned base = 0u; base < total; base += kLightingAhead * kLightingLanes) {
+                        unsigned pos[kLightingAhead];
+                        typename Recs::Raw raw[kLightingAhead];
+#pragma unroll
+                        for (int a = 0; a < kLightingAhead; ++a) {
+                            pos[a] = entry(min(base + a * kLightingLanes + lane, total - 1u));
+                        }
+#pragma unroll
+                        for (int a = 0; a < kLightingAhead; ++a) {
+                            raw[a] = Recs::Load(f, q.n, pos[a]);
+                        }
+#pragma unroll
+                        for (int a = 0; a < kLightingAhead; ++a) {
+                            test(raw[a]);
+                        }
+                        if (LightingGroupAny(s.bi[0] != bound_id)) {  // a candidate below the bound: an occluder
+                            occluded = true;
+                            break;
+                        }
+                    }
+                    cls = occluded ? kShadowShadowed : kShadowLit;
+                }
+            }
+            if (cls == kShadowLit && facing) {
+                const float w = LightingWeight(nl, nn, ShadowDot(off, off), lt.falloff);
+                e0 = e0 + lt.color[0] * w;
+                e1 = e1 + lt.color[1] * w;
+                e2 = e2 + lt.color[2] * w;
+            }
+        }
+        if (lane == 0u && q.classes != nullptr) {
+            q.classes[static_cast<size_t>(l) * q.pixels + pixel] = cls;
+        }
+    }
+    if (lane == 0u) {
+        F4 out{q.bg[0], q.bg[1], q.bg[2], -1.f};
+        if (surface) {
+            out = F4{al[0] * e0, al[1] * e1, al[2] * e2, static_cast<float>(code)};
+        }
+        StoreNontemporal(q.rgba + pixel, out);
+    }
+}
+
+// ---------------------------------------------------------------------------------------
 // BVH variant: primary rays share the eye, so the closest-hit search
 // is a 2-D query over the records' screen boxes. The tree is implicit and 8 wide over the
 // cull records in the scene's spatial (Morton) order -- no sort, no topology arrays; only the
@@ -5943,6 +6152,109 @@ hipError_t LaunchOmniShadow(const float* d_vertices, const float* d_shade, std::
         hipLaunchKernelGGL(OmniShadowKernel<true>, grid, dim3(kOmniThreads), 0, stream, q);
     } else {
         hipLaunchKernelGGL(OmniShadowKernel<false>, grid, dim3(kOmniThreads), 0, stream, q);
+    }
+    return hipGetLastError();
+}
+
+hipError_t LaunchLighting(const float* d_vertices, const float* d_shade, std::uint64_t n, const Frame& frame,
+                          const float background[3], const LightingLight* lights, std::size_t count,
+                          const LightingArgs& args, hipStream_t stream) {
+    if (args.width == 0 || args.row_count == 0) {
+        return hipSuccess;
+    }
+    const std::size_t pixels = args.width * args.row_count;
+    if (args.offsets == nullptr || args.ids == nullptr || args.rgba == nullptr || d_shade == nullptr ||
+        (n != 0 && d_vertices == nullptr) || n > 0x7FFFFFFFull || args.height == 0 || args.height > 0x7FFFFFFFull ||
+        args.row_begin > args.height || args.row_count > args.height - args.row_begin ||
+        args.width > 0xFFFFFFFFull || args.row_count > (0xFFFFFFFFull - kLightingBlock) / args.width ||
+        count > static_cast<std::size_t>(kLightingMaxLights) || (count != 0 && lights == nullptr)) {
+        return hipErrorInvalidValue;
+    }
+    LightingParams q{};
+    bool recompute = false;
+    unsigned frames = 0u;
+    for (std::size_t i = 0; i < count; ++i) {
+        const LightingLight& in = lights[i];
+        const unsigned faces = in.point ? static_cast<unsigned>(kOmniFaces) : 1u;
+        if (in.frames == nullptr || frames + faces > static_cast<unsigned>(kLightingMaxFrames) || !(in.bias >= 0.f) ||
+            !std::isfinite(in.bias) || !(in.falloff >= 0.f) || !std::isfinite(in.falloff)) {
+            return hipErrorInvalidValue;
+        }
+        LightingLightParams& lt = q.light[i];
+        lt.first = frames;
+        lt.point = in.point ? 1u : 0u;
+        lt.falloff = in.falloff;
+        lt.bias = in.bias;
+        for (int c = 0; c < 3; ++c) {
+            lt.origin[c] = in.frames[0].frame.origin[c];
+            lt.color[c] = in.color[c];
+        }
+        for (unsigned k = 0; k < faces; ++k) {
+            const ShadowLight& l = in.frames[k];
+            if ((n != 0 && l.rank == nullptr) || l.svertices == nullptr || l.edges == nullptr ||
+                l.width != in.frames[0].width || l.height != in.frames[0].height ||
+                std::memcmp(l.frame.origin, in.frames[0].frame.origin, sizeof l.frame.origin) != 0 ||
+                (l.setup != nullptr && (l.width == 0 || l.height == 0 || !CullBinnable(l.width, l.height) ||
+                                        l.setup->tiles != CullTiles(l.width, l.height)))) {
+                return hipErrorInvalidValue;
+            }
+            TraceParams p{};
+            int tiles_y = 0;
+            const bool rc = QueryRecords(p, tiles_y, l.setup, n, l.frame, l.width, l.height, l.svertices, l.edges);
+            if (frames != 0u && rc != recompute) {
+                return hipErrorInvalidValue;  // one record source per launch (the kernel's template argument)
+            }
+            recompute = rc;
+            OmniFaceParams& f = q.frame[frames++];
+            f.cull = p.cull;
+            f.svertices = p.svertices;
+            f.rank = l.rank;
+            f.tile_info = p.tile_info;
+            f.bin_lists = p.bin_lists;
+            f.bin_counts = p.bin_counts;
+            f.large_list = p.large_list;
+            f.bin_capacity = p.bin_capacity;
+            f.tiles = p.tiles;
+            f.tiles_x = p.tiles_x;
+            f.tiles_y = tiles_y;
+            f.stream_end = n == 0 ? 0u : p.n_pad;
+            f.wf = p.wf;
+            f.hf = p.hf;
+            for (int c = 0; c < 3; ++c) {
+                f.base[c] = l.frame.base[c];
+                f.du[c] = l.frame.du[c];
+                f.dv[c] = l.frame.dv[c];
+                f.origin[c] = l.frame.origin[c];
+            }
+            ShadowProjectionRows(l.frame.base, l.frame.du, l.frame.dv, f.rows);
+        }
+    }
+    q.vertices = d_vertices;
+    q.shade = reinterpret_cast<const float4*>(d_shade);
+    q.offsets = reinterpret_cast<const float2*>(args.offsets);
+    q.ids = args.ids;
+    q.rgba = reinterpret_cast<F4*>(args.rgba);
+    q.classes = args.classes;
+    q.n = static_cast<unsigned>(n);
+    q.width = static_cast<unsigned>(args.width);
+    q.row_begin = static_cast<unsigned>(args.row_begin);
+    q.pixels = static_cast<unsigned>(pixels);
+    q.count = static_cast<unsigned>(count);
+    q.wf = static_cast<float>(args.width);
+    q.hf = static_cast<float>(args.height);
+    for (int k = 0; k < 3; ++k) {
+        q.eye[k] = frame.origin[k];
+        q.base[k] = frame.base[k];
+        q.du[k] = frame.du[k];
+        q.dv[k] = frame.dv[k];
+        q.bg[k] = background[k];
+        q.ambient[k] = args.ambient[k];
+    }
+    const dim3 grid(static_cast<unsigned>((pixels + kLightingBlock - 1) / kLightingBlock));
+    if (recompute) {
+        hipLaunchKernelGGL(LightingKernel<true>, grid, dim3(kLightingThreads), 0, stream, q);
+    } else {
+        hipLaunchKernelGGL(LightingKernel<false>, grid, dim3(kLightingThreads), 0, stream, q);
     }
     return hipGetLastError();
 }

@@ -11,6 +11,7 @@
 
 #include "comm.h"
 #include "engine.h"
+#include "lighting_math.h"
 #include "render.h"
 
 namespace srt {
@@ -1000,7 +1001,7 @@ void DeviceScene::Composite(const float* d_offsets, const int* d_ids, std::size_
 }
 
 bool DeviceScene::QuerySetup(CullSetup& setup, hipStream_t stream) const {
-    const bool shared = OnSharedSetup(0, m_height, 1) && CullBinningEnabled() && CullBinnable(m_width, m_height);
+    const bool shared = QuerySetupUsable();
     if (shared) {
         // (a query reads no plan: a setup standing for another grid, a batch's, serves as it is)
         const bool standing = !m_setup_pending && m_setup_key.width == m_width && m_setup_key.height == m_height;
@@ -1113,6 +1114,141 @@ void DeviceScene::OmniShadow(const DeviceScene* const faces[6], const float* d_o
     RecordOrder(stream);
     for (int k = 0; k < 6; ++k) {
         faces[k]->RecordOrder(stream);
+    }
+}
+
+bool DeviceScene::QuerySetupUsable() const {
+    return OnSharedSetup(0, m_height, 1) && CullBinningEnabled() && CullBinnable(m_width, m_height);
+}
+
+// (no setup: the records are recomputed from the scene's vertices -- render.hip QueryRecords; EnsureSetup's rule else)
+bool DeviceScene::QueryRecomputes() const {
+    return !QuerySetupUsable() || RecordModeFromEnv() == static_cast<int>(kRecordsRecompute);
+}
+
+void DeviceScene::CheckLightCount(std::size_t count) {
+    if (count > static_cast<std::size_t>(kLightingMaxLights)) {
+        throw std::runtime_error("Lighting: at most " + std::to_string(kLightingMaxLights) + " lights per call, got " +
+                                 std::to_string(count));
+    }
+}
+
+void DeviceScene::CheckLights(const LightTerms* lights, std::size_t count, const float ambient[3]) {
+    CheckLightCount(count);
+    for (int k = 0; k < 3; ++k) {
+        if (!std::isfinite(ambient[k])) {
+            throw std::runtime_error("Lighting: ambient value " + std::to_string(k) + " is not finite");
+        }
+    }
+    std::size_t frames = 0;
+    for (std::size_t l = 0; l < count; ++l) {
+        const LightTerms& in = lights[l];
+        const std::string who = "Lighting: light " + std::to_string(l);
+        frames += in.point ? 6 : 1;
+        if (frames > static_cast<std::size_t>(kLightingMaxFrames)) {
+            throw std::runtime_error(who + " brings the call to " + std::to_string(frames) + " light frames, at most " +
+                                     std::to_string(kLightingMaxFrames) + " (1 per spot, 6 per point light)");
+        }
+        for (int k = 0; k < 3; ++k) {
+            if (!std::isfinite(in.color[k])) {
+                throw std::runtime_error(who + ": color value " + std::to_string(k) + " is not finite");
+            }
+        }
+        if (!(in.falloff >= 0.f) || !std::isfinite(in.falloff)) {
+            throw std::runtime_error(who + ": falloff must be finite and >= 0");
+        }
+        if (!(in.bias >= 0.f) || !std::isfinite(in.bias)) {
+            throw std::runtime_error(who + ": bias must be finite and >= 0");
+        }
+    }
+}
+
+// Direct lighting (render.h LaunchLighting): the launch reads this scene's buffers and every light
+// frame's, so it is ordered after the previous call of each and every one records it (a scene that
+// appears twice is ordered and recorded twice: harmless). Every refusal comes before the first
+// side effect: a refused call orders nothing, builds no setup and leaves every scene as it was.
+void DeviceScene::Lighting(const Light* lights, std::size_t count, const float ambient[3], const float* d_offsets,
+                           const int* d_ids, std::size_t row_begin, std::size_t row_count, float* d_rgba,
+                           unsigned char* d_classes, hipStream_t stream) const {
+    if (m_width == 0) {
+        throw std::runtime_error("Lighting: Prepare() has not been called on the view scene");
+    }
+    CheckLightCount(count);
+    LightTerms terms[kLightingMaxLights];
+    for (std::size_t l = 0; l < count; ++l) {
+        terms[l] = LightTerms{lights[l].point, lights[l].color, lights[l].falloff, lights[l].bias};
+    }
+    CheckLights(terms, count, ambient);
+    bool recompute = false;
+    for (std::size_t l = 0; l < count; ++l) {
+        const Light& in = lights[l];
+        const std::string who = "Lighting: light " + std::to_string(l);
+        for (std::size_t k = 0; k < (in.point ? 6u : 1u); ++k) {
+            const DeviceScene& f = *in.scenes[k];
+            if (f.m_width == 0) {
+                throw std::runtime_error(who + " has not been prepared");
+            }
+            if (f.m_width != in.scenes[0]->m_width || f.m_height != in.scenes[0]->m_height) {
+                throw std::runtime_error(who + ": the faces are prepared at different sizes");
+            }
+            if (f.m_device != m_device) {
+                throw std::runtime_error(who + ": the view scene lives on device " + std::to_string(m_device) +
+                                         ", the light on device " + std::to_string(f.m_device));
+            }
+            if (f.m_n != m_n) {
+                throw std::runtime_error(who + ": the view scene has " + std::to_string(m_n) +
+                                         " triangles, the light's scene " + std::to_string(f.m_n));
+            }
+            // One record source per launch (the kernel's template argument; LaunchOmniShadow's rule
+            // for its six faces). A frame that cannot be binned has no shared cull setup and
+            // recomputes its records; a frame with one reads stored records unless the env says otherwise.
+            const bool rc = f.QueryRecomputes();
+            if ((l != 0 || k != 0) && rc != recompute) {
+                throw std::runtime_error(
+                    who + ": its " + std::to_string(f.m_width) + " x " + std::to_string(f.m_height) + " frame reads " +
+                    (rc ? "recomputed" : "stored") + " records, the light frames before it " +
+                    (rc ? "stored" : "recomputed") +
+                    " ones: a light frame too large for a shared cull setup (more than " + std::to_string(kMaxBinTiles) +
+                    " tiles of 64 x 16 pixels, or more than " + std::to_string(kMaxBoundTiles) +
+                    " tile columns plus tile rows) cannot share a call with a smaller one");
+            }
+            recompute = rc;
+        }
+    }
+    if (row_begin > m_height || row_count > m_height - row_begin) {
+        throw std::runtime_error("Lighting: row band outside the frame");
+    }
+    if (row_count == 0) {
+        return;
+    }
+    OrderAfterPrevious(stream);
+    CullSetup setups[kLightingMaxFrames] = {};
+    ShadowLight sl[kLightingMaxFrames];
+    LightingLight ll[kLightingMaxLights];
+    std::size_t frames = 0;
+    for (std::size_t l = 0; l < count; ++l) {
+        const Light& in = lights[l];
+        ll[l] = LightingLight{sl + frames, in.point, {in.color[0], in.color[1], in.color[2]}, in.falloff, in.bias};
+        for (std::size_t k = 0; k < (in.point ? 6u : 1u); ++k, ++frames) {
+            const DeviceScene& f = *in.scenes[k];
+            if (&f != this) {
+                f.OrderAfterPrevious(stream);
+            }
+            const bool shared = f.QuerySetup(setups[frames], stream);
+            sl[frames] = ShadowLight{shared ? &setups[frames] : nullptr, f.m_frame, f.m_width, f.m_height,
+                                     f.m_svertices,                      f.m_edges, f.m_rank};
+        }
+    }
+    const LightingArgs args{d_offsets, d_ids,  m_width,  m_height, row_begin, row_count, {ambient[0], ambient[1], ambient[2]},
+                            d_rgba,    d_classes};
+    HipCheck(LaunchLighting(m_vertices, m_shade, m_n, m_frame, m_background, ll, count, args, stream), "lighting launch");
+    RecordOrder(stream);
+    for (std::size_t l = 0; l < count; ++l) {
+        for (std::size_t k = 0; k < (lights[l].point ? 6u : 1u); ++k) {
+            if (lights[l].scenes[k] != this) {
+                lights[l].scenes[k]->RecordOrder(stream);
+            }
+        }
     }
 }
 

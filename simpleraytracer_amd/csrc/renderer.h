@@ -145,6 +145,33 @@ public:
                     std::size_t row_count, float bias, unsigned char* d_mask, unsigned char* d_face, float* d_rgba,
                     float dim, hipStream_t stream) const;
 
+    // Direct lighting (render.h LaunchLighting) of the band rows [row_begin, row_begin + row_count) of
+    // this scene's prepared frame under `count` (0 .. kLightingMaxLights) lights, each one prepared
+    // scene (spot) or six cube-face scenes (point), at most kLightingMaxFrames scenes in all, on this
+    // scene's device, with this scene's number of triangles; a scene may appear more than once.
+    // d_rgba row_count x width x 4; d_classes (may be null) count x row_count x width class bytes.
+    // Builds every light frame's shared setup that its prepared frame lacks; one launch; this
+    // scene's and every light scene's calls are ordered against this one. Every rule about the
+    // lights is checked here, before anything is enqueued or built, and the message names the light
+    // and the field; CheckLights is that part for a caller without device scenes (the host call):
+    // the count, the ambient colour, the frame total and every light's colour, falloff and bias.
+    struct LightTerms {
+        bool point;
+        const float* color;
+        float falloff, bias;
+    };
+    static void CheckLights(const LightTerms* lights, std::size_t count, const float ambient[3]);
+    static void CheckLightCount(std::size_t count);  // (before a caller reads `count` structs)
+    struct Light {
+        const DeviceScene* const* scenes;  // 1 (spot) or 6 (point)
+        bool point;
+        float color[3];
+        float falloff, bias;
+    };
+    void Lighting(const Light* lights, std::size_t count, const float ambient[3], const float* d_offsets,
+                  const int* d_ids, std::size_t row_begin, std::size_t row_count, float* d_rgba,
+                  unsigned char* d_classes, hipStream_t stream) const;
+
     // G-buffer: the surface attributes (render.h GBufferArgs: depth, bary, normal, albedo; a null
     // plane is not written) of hit ids on the prepared frame. points: `count` positions d_where
     // (count x 2) with d_ids (count), row_begin unused. Else the band rows [row_begin, row_begin +
@@ -260,6 +287,10 @@ private:
     // The setup a point query of the prepared frame reads (Query, Shadow), (re)built on `stream` if
     // need be; false: no usable setup (SRT_SETUP=frame, SRT_CULL_BIN=0, a shape that cannot be binned).
     bool QuerySetup(CullSetup& setup, hipStream_t stream) const;
+    // Whether QuerySetup would give a setup, and whether a launch on it (or without one) recomputes
+    // its records: known without building anything.
+    bool QuerySetupUsable() const;
+    bool QueryRecomputes() const;
     Frame m_frame{};
     std::size_t m_width = 0;
     std::size_t m_height = 0;

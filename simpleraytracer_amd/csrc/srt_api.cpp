@@ -11,6 +11,7 @@
 
 #include "cpu_render.h"
 #include "engine.h"
+#include "lighting_math.h"
 #include "omni_math.h"
 #include "render.h"
 #include "renderer.h"
@@ -18,6 +19,7 @@
 #include "srt_gbuffer.h"
 #include "srt_layers.h"
 #include "srt_light.h"
+#include "srt_lighting.h"
 #include "srt_omni.h"
 #include "srt_query.h"
 #include "srt_render.h"
@@ -1398,6 +1400,146 @@ RTO_API int rtoFaceOfHost(const float q[3]) {
         face = srt::OmniFace(q);
     });
     return face;
+}
+
+// Direct lighting (include/srt_lighting.h): the rtd family. The entry points check what is theirs --
+// NULL arguments, the structs' sizes and handles, the host lights' geometry; every rule about the
+// lights themselves (count, frame total, ambient, colour, falloff, bias, and for device lights
+// preparation, device, triangle count and record source) is DeviceScene's (renderer.cpp).
+static_assert(RTD_MAX_LIGHTS == srt::kLightingMaxLights && RTD_MAX_FRAMES == srt::kLightingMaxFrames,
+              "include/srt_lighting.h and lighting_math.h agree");
+
+RTD_API int rtdLightAsync(srt_device_scene view, const rtd_light* lights, size_t count, const float ambient[3],
+                          const float* d_offsets, const int* d_ids, size_t row_begin, size_t row_count,
+                          float* d_rgba, unsigned char* d_classes, void* stream) {
+    return Guarded([&] {
+        if (view == nullptr) {
+            throw std::runtime_error("Bad scene handle: view is NULL");
+        }
+        srt::DeviceScene::CheckLightCount(count);
+        if (count != 0 && lights == nullptr) {
+            throw std::runtime_error("Bad argument: lights is NULL");
+        }
+        if (ambient == nullptr) {
+            throw std::runtime_error("Bad argument: ambient is NULL");
+        }
+        std::vector<srt::DeviceScene::Light> in(count);
+        std::vector<const srt::DeviceScene*> scenes(count * srt::kOmniFaces);
+        for (size_t l = 0; l < count; ++l) {
+            const rtd_light& lt = lights[l];
+            const std::string who = "Lighting: light " + std::to_string(l);
+            if (lt.struct_size != sizeof(rtd_light)) {
+                throw std::runtime_error(who + ": rtd_light.struct_size is " + std::to_string(lt.struct_size) +
+                                         ", expected " + std::to_string(sizeof(rtd_light)));
+            }
+            if ((lt.spot != nullptr) == (lt.point != nullptr)) {
+                throw std::runtime_error(who + ": exactly one of spot and point must be set, got " +
+                                         (lt.spot != nullptr ? "both" : "neither"));
+            }
+            const srt::DeviceScene** mine = scenes.data() + l * srt::kOmniFaces;
+            const bool point = lt.point != nullptr;
+            for (int k = 0; k < (point ? srt::kOmniFaces : 1); ++k) {
+                mine[k] = point ? lt.point->faces[k].get() : FromHandle(lt.spot);
+            }
+            in[l] = srt::DeviceScene::Light{mine, point, {lt.color[0], lt.color[1], lt.color[2]}, lt.falloff, lt.bias};
+        }
+        if (row_count != 0) {
+            if (d_offsets == nullptr) {
+                throw std::runtime_error("Bad buffer argument: d_offsets is NULL");
+            }
+            if (d_ids == nullptr) {
+                throw std::runtime_error("Bad buffer argument: d_ids is NULL");
+            }
+            if (d_rgba == nullptr) {
+                throw std::runtime_error("Bad buffer argument: d_rgba is NULL");
+            }
+        }
+        srt::DeviceScene* s = FromHandle(view);
+        Bind bind(s->device());
+        s->Lighting(in.data(), count, ambient, d_offsets, d_ids, row_begin, row_count, d_rgba, d_classes,
+                    static_cast<hipStream_t>(stream));
+    });
+}
+
+RTD_API int rtdLightHost(const char* scene_path, size_t width, size_t height, const rtd_light_host* lights, size_t count,
+                         const float ambient[3], const float* offsets, const int* ids, size_t row_begin, size_t row_count,
+                         float* rgba, unsigned char* classes) {
+    return Guarded([&] {
+        if (scene_path == nullptr) {
+            throw std::runtime_error("Bad argument: scene_path is NULL");
+        }
+        if (width == 0 || height == 0) {
+            throw std::runtime_error("Bad argument: frame dimensions must be non-zero");
+        }
+        srt::DeviceScene::CheckLightCount(count);
+        if (count != 0 && lights == nullptr) {
+            throw std::runtime_error("Bad argument: lights is NULL");
+        }
+        if (ambient == nullptr) {
+            throw std::runtime_error("Bad argument: ambient is NULL");
+        }
+        std::vector<srt::DeviceScene::LightTerms> terms(count);
+        for (size_t l = 0; l < count; ++l) {
+            const rtd_light_host& lt = lights[l];
+            const std::string who = "Lighting: light " + std::to_string(l);
+            if (lt.struct_size != sizeof(rtd_light_host)) {
+                throw std::runtime_error(who + ": rtd_light_host.struct_size is " + std::to_string(lt.struct_size) +
+                                         ", expected " + std::to_string(sizeof(rtd_light_host)));
+            }
+            if (lt.kind != 0 && lt.kind != 1) {
+                throw std::runtime_error(who + ": kind must be 0 (spot) or 1 (point), got " + std::to_string(lt.kind));
+            }
+            terms[l] = srt::DeviceScene::LightTerms{lt.kind == 1, lt.color, lt.falloff, lt.bias};
+        }
+        srt::DeviceScene::CheckLights(terms.data(), count, ambient);
+        std::vector<srt::HostLight> in(count);
+        for (size_t l = 0; l < count; ++l) {
+            const rtd_light_host& lt = lights[l];
+            srt::HostLight& h = in[l];
+            h = srt::HostLight{};
+            h.point = lt.kind == 1;
+            try {
+                if (h.point) {
+                    CheckedOrigin(lt.origin);
+                    if (lt.face_size == 0) {
+                        throw std::runtime_error("face_size must be non-zero");
+                    }
+                    std::copy(lt.origin, lt.origin + 3, h.origin);
+                    h.face_size = lt.face_size;
+                } else {
+                    if (lt.width == 0 || lt.height == 0) {
+                        throw std::runtime_error("frame dimensions must be non-zero");
+                    }
+                    h.camera = CheckedCamera(lt.camera10);
+                    h.width = lt.width;
+                    h.height = lt.height;
+                }
+            } catch (std::exception& e) {
+                throw std::runtime_error("Lighting: light " + std::to_string(l) + ": " + e.what());
+            }
+            std::copy(lt.color, lt.color + 3, h.color);
+            h.falloff = lt.falloff;
+            h.bias = lt.bias;
+        }
+        if (row_begin > height || row_count > height - row_begin) {
+            throw std::runtime_error("Bad argument: row band outside the frame");
+        }
+        if (row_count == 0) {
+            return;
+        }
+        if (offsets == nullptr) {
+            throw std::runtime_error("Bad buffer argument: offsets is NULL");
+        }
+        if (ids == nullptr) {
+            throw std::runtime_error("Bad buffer argument: ids is NULL");
+        }
+        if (rgba == nullptr) {
+            throw std::runtime_error("Bad buffer argument: rgba is NULL");
+        }
+        const srt::Scene scene = srt::LoadScene(scene_path);
+        srt::HostLighting(scene, width, height, in.data(), count, ambient, offsets, ids, row_begin, row_count, rgba,
+                          classes);
+    });
 }
 
 #ifdef SRT_DIAG

@@ -1,7 +1,7 @@
 """Scene files, the device-level render stages (include/srt_render.h), point queries
 (include/srt_query.h), G-buffer outputs (include/srt_gbuffer.h), multi-sample frames
-(include/srt_samples.h), spot-light shadow masks (include/srt_light.h) and omni-light shadow masks
-(include/srt_omni.h).
+(include/srt_samples.h), spot-light shadow masks (include/srt_light.h), omni-light shadow masks
+(include/srt_omni.h) and direct lighting (include/srt_lighting.h; the lights: lighting.py).
 
 ``DeviceScene`` keeps a scene resident on one GPU and launches the two stages on a caller's
 HIP stream with caller-owned device buffers (torch tensors or raw pointers):
@@ -15,6 +15,7 @@ HIP stream with caller-owned device buffers (torch tensors or raw pointers):
     scene.shadow(light, offsets, ids, mask, rgba, stream=s)      # which pixels a spot light (a second scene) reaches
     scene.layer_frame(offsets, ids_k, t_k, stream=s)             # the K nearest hits per pixel (also layers(), composite())
     scene.omni_shadow(omni, offsets, ids, mask, face, stream=s)  # which pixels a point light (an OmniLight) reaches
+    scene.light(lights, offsets, ids, rgba, ambient, stream=s)   # the lit picture under several lights (also render_lit())
 
 This is the path bench.py times (inputs resident in HBM) and the one-process-per-GPU
 band renderer uses; ``runner.render`` is the host-image ml* path.
@@ -303,6 +304,34 @@ def omni_shadow_host(path: str, width: int, height: int, origin, face_size: int,
                                        off.ctypes.data, idv.ctypes.data, row_begin, row_count, bias, mask.ctypes.data,
                                        face.ctypes.data, rgba.ctypes.data, dim))
     return mask, face, rgba
+
+
+def lighting_host(path: str, width: int, height: int, lights, ambient, offsets, ids, row_begin: int = 0,
+                  row_count: int | None = None):
+    """Direct lighting on the host (rtdLightHost: brute force, the library's canonical math, no
+    device): the band rows of path's width x height frame under `lights`, a sequence of 0 to 8
+    lighting.SpotLightHost / lighting.PointLightHost of path's triangles, and the ambient colour;
+    offsets (rows, W, 2) float32 and ids (rows, W) int32 -> (rgba (rows, W, 4) float32, classes
+    (len(lights), rows, W) uint8 of shadow_host()'s classes, light-major)."""
+    import numpy as np
+
+    from . import lighting
+
+    if row_count is None:
+        row_count = height - row_begin
+    off = np.ascontiguousarray(offsets, np.float32)
+    idv = np.ascontiguousarray(ids, np.int32)
+    if off.shape != (row_count, width, 2):
+        raise ValueError(f"offsets must be {(row_count, width, 2)}, got {off.shape}")
+    if idv.shape != (row_count, width):
+        raise ValueError(f"ids must be {(row_count, width)}, got {idv.shape}")
+    arr, count = lighting.pack_host(lights)
+    rgba = np.empty((row_count, width, 4), np.float32)
+    classes = np.empty((count, row_count, width), np.uint8)
+    _check(_native.lib().rtdLightHost(os.fsencode(path), width, height, ctypes.addressof(arr) if arr is not None else None,
+                                      count, lighting.ambient3(ambient), off.ctypes.data, idv.ctypes.data, row_begin,
+                                      row_count, rgba.ctypes.data, classes.ctypes.data))
+    return rgba, classes
 
 
 def tile_of(width: int, height: int, fx: float, fy: float):
@@ -722,6 +751,38 @@ class DeviceScene:
             self._check_buffer("rgba", rgba, row_count, 4, "f32")
         _check(self._lib.rtoShadowAsync(self.handle, light.handle, _ptr(offsets), _ptr(ids), row_begin, row_count, bias,
                                         _ptr(mask), _ptr(face), _ptr(rgba), dim, _stream(stream)))
+
+    def light(self, lights, offsets, ids, rgba, ambient=(0.0, 0.0, 0.0), classes=None, row_begin: int = 0,
+              row_count: int | None = None, stream=None):
+        """Direct lighting of the prepared frame's rows (include/srt_lighting.h): `lights` is a
+        sequence of 0 to 8 lighting.SpotLight / lighting.PointLight over prepared scenes of the same
+        triangles (at most 16 light frames: 1 per spot, 6 per point light). offsets, ids as
+        shadow()'s; rgba (rows, W, 4) float32: albedo . (ambient + the lights that reach the pixel
+        from the eye's side of its triangle), alpha = the id, the background and -1 without a
+        surface; classes (len(lights), rows, W) uint8, optional: plane l is shadow()'s /
+        omni_shadow()'s mask under light l alone at its bias. One launch whatever len(lights)."""
+        from . import lighting
+
+        if row_count is None:
+            row_count = self.height - row_begin
+        self._check_buffer("offsets", offsets, row_count, 2, "f32")
+        self._check_buffer("ids", ids, row_count, 0, "i32")
+        self._check_buffer("rgba", rgba, row_count, 4, "f32")
+        arr, count = lighting.pack_device(lights)
+        if classes is not None:
+            if hasattr(classes, "shape") and tuple(classes.shape) != (count, row_count, self.width):
+                raise ValueError(f"classes must be {(count, row_count, self.width)}, got {tuple(classes.shape)}")
+            self._check_tensor("classes", classes, "u8")
+        _check(self._lib.rtdLightAsync(self.handle, ctypes.addressof(arr) if arr is not None else None, count,
+                                       lighting.ambient3(ambient), _ptr(offsets), _ptr(ids), row_begin, row_count,
+                                       _ptr(rgba), _ptr(classes), _stream(stream)))
+
+    def render_lit(self, lights, offsets, ids, rgba, ambient=(0.0, 0.0, 0.0), classes=None, variant: str = "cull",
+                   stream=None):
+        """The lit picture of the whole prepared frame: trace_ids() into ids ((H, W) int32; they stay
+        available), then light() from them, both on `stream`."""
+        self.trace_ids(offsets, ids, variant=variant, stream=stream)
+        self.light(lights, offsets, ids, rgba, ambient=ambient, classes=classes, stream=stream)
 
     def close(self):
         if self.handle:
