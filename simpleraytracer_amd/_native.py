@@ -1,5 +1,5 @@
 """ctypes binding of libModelRunner.so (include/model_runner.h + include/srt_render.h + include/srt_query.h +
-include/srt_gbuffer.h + include/srt_samples.h).
+include/srt_gbuffer.h + include/srt_samples.h and the later families' headers, include/srt_motion.h the last).
 
 The shared library is built in-tree by ``make`` (or ``__graft_entry__.build()``) into
 ``simpleraytracer_amd/lib/libModelRunner.so``. There is no fallback: importing the renderer
@@ -43,6 +43,8 @@ SRT_ENGINE_RCCL_SELF = 1  # srt_engine_options.flags
 SRT_TILE_ROWS = 16  # include/srt_render.h: rows per tile row (interleaved bands deal these)
 RTS_MAX_SAMPLES = 16  # include/srt_samples.h: sample planes per rtsResolveAsync / rtsRenderAsync call
 RTK_MAX_LAYERS = 8  # include/srt_layers.h: layers per rtkLayersAsync / rtkFrameAsync / rtkCompositeAsync call
+RTM_REORDER = 0     # include/srt_motion.h: rebuild the spatial order under the new pose
+RTM_KEEP_ORDER = 1  # keep the standing order
 
 
 class ImageInfo(ctypes.Structure):
@@ -268,6 +270,15 @@ _SIGNATURES = {
                                      ctypes.c_void_p]),
     "rtkCompositeHost": (ctypes.c_int, [ctypes.c_char_p, _SZ, _SZ, ctypes.c_void_p, ctypes.c_void_p, _SZ, ctypes.c_void_p,
                                         _SZ, _SZ, ctypes.c_void_p]),
+    # include/srt_motion.h: dynamic scenes (camera10, origin3: ctypes float arrays; d_vertices: a device address)
+    "rtmSetCameraAsync": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_float), ctypes.c_int, ctypes.c_void_p]),
+    "rtmSetVerticesAsync": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]),
+    "rtmGetCamera": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_float)]),
+    "rtmLightSetOriginAsync": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_float), ctypes.c_int,
+                                              ctypes.c_void_p]),
+    "rtmLightSetVerticesAsync": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]),
+    "rtmOrderHost": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_ulonglong, ctypes.POINTER(ctypes.c_float), ctypes.c_void_p,
+                                    ctypes.c_void_p]),
 }
 
 _lib = None

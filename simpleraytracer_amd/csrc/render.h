@@ -602,6 +602,31 @@ void BuildSpatialOrder(const float* d_vertices, std::uint64_t n, const Camera& c
                        unsigned* d_rank, float* d_svertices, hipStream_t stream, hipEvent_t ev_begin = nullptr,
                        hipEvent_t ev_end = nullptr);
 
+// Motion (spatial.hip; include/srt_motion.h): the same order rebuilt in place after the camera or
+// the vertices moved, enqueued on `stream` only -- no allocation, no host synchronisation. The sort
+// scratch (keys, sorted keys, ids and the rocPRIM temporary: 3 x 4 n bytes + temp_bytes, a function
+// of n alone) belongs to the scene: allocated by its first reordering update, freed with it.
+struct OrderScratch {
+    unsigned* keys = nullptr;
+    unsigned* keys_sorted = nullptr;
+    unsigned* ids = nullptr;
+    void* temp = nullptr;
+    std::size_t temp_bytes = 0;
+};
+void AllocOrderScratch(OrderScratch& scratch, std::uint64_t n, hipStream_t stream);  // throws; leaves none on failure
+void FreeOrderScratch(OrderScratch& scratch) noexcept;
+// One pass over the n triangles (MotionKeysKernel): d_shade non-null, row 0 of its shading table
+// (ShadingNormal; row 1, the albedo, is not touched); scratch non-null, the Morton keys under
+// `camera` and the ids, then the stable radix sort into d_order. Then the gather (RankKernel) of
+// d_vertices through d_order into d_rank and d_svertices -- through the standing d_order when
+// scratch is null. Throws std::runtime_error on a failed enqueue.
+void EnqueueMotion(const float* d_vertices, std::uint64_t n, const Camera& camera, float* d_shade,
+                   const OrderScratch* scratch, unsigned* d_order, unsigned* d_rank, float* d_svertices,
+                   hipStream_t stream);
+// The host twin (rtmOrderHost): MortonKey and ShadingNormal themselves over host vertices, a stable
+// sort by key; order (n) and normals (n x 4) may each be null.
+void OrderHost(const float* vertices, std::uint64_t n, const Camera& camera, unsigned* order, float* normals);
+
 // Element-wise IEEE binary16 <-> binary32 conversion on the device (ML_FLOAT16 images):
 // float -> half rounds to nearest even (overflow -> inf, NaN stays NaN); half -> float is exact.
 // `half` buffers are uint16 bit patterns on the host side.

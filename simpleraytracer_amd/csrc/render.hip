@@ -10,6 +10,7 @@
 #include "samples_math.h"
 #include "screen_box.h"
 #include "omni_math.h"
+#include "shading_normal.h"
 #include "shadow_math.h"
 #include "tile_lookup.h"
 
@@ -390,15 +391,7 @@ __device__ __forceinline__ uint2 QuantizeBox(const float4& sb) {
     return make_uint2(PackI16(QuantHi(sb.y), -QuantLo(sb.x)), PackI16(QuantHi(sb.w), -QuantLo(sb.z)));
 }
 
-// Shading normal of the triangle with vertex coordinates v[0..9): the exact expressions the
-// shading epilogue used to evaluate per hit.
-__device__ __forceinline__ float4 ShadingNormal(const float* __restrict__ v) {
-    const float e1x = v[3] - v[0], e1y = v[4] - v[1], e1z = v[5] - v[2];
-    const float e2x = v[6] - v[0], e2y = v[7] - v[1], e2z = v[8] - v[2];
-    float nx, ny, nz;
-    Cross3(e1x, e1y, e1z, e2x, e2y, e2z, nx, ny, nz);
-    return make_float4(nx, ny, nz, sqrtf(Dot3(nx, ny, nz, nx, ny, nz)));
-}
+// (ShadingNormal: shading_normal.h -- shared with the motion kernels, spatial.hip, and their host twin.)
 
 // Shading table of a scene (once, at load): triangle i -> (ShadingNormal, (albedo, 0)).
 __global__ __launch_bounds__(256) void ShadeTableKernel(const float* __restrict__ vertices,

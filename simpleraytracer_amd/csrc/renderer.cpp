@@ -169,6 +169,10 @@ DeviceScene::~DeviceScene() {
     (void)hipFree(m_order);
     (void)hipFree(m_rank);
     (void)hipFree(m_svertices);
+    if (m_scratch != nullptr) {
+        FreeOrderScratch(*m_scratch);
+        delete m_scratch;
+    }
     (void)hipFree(m_block_ext);
     (void)hipFree(m_setup);
     (void)hipFree(m_stream);
@@ -219,6 +223,74 @@ void DeviceScene::Prepare(std::size_t width, std::size_t height, hipStream_t str
     (void)stream;
     m_prepare_pending = true;
     m_ext_pending = true;
+}
+
+// What a pose shapes, and how each piece comes back (DESIGN.md section 5 "Motion"):
+//   m_frame                      recomputed here, as Prepare(W, H) would (a prepared scene stays prepared);
+//   edge slot 0, the BVH boxes   the next unbinned trace's record pass (m_prepare_pending; the bvh
+//                                trace rebuilds its boxes from the records on every call);
+//   m_block_ext                  the next binned trace (m_ext_pending);
+//   the shared setup, its record stream and plan counts (m_stream_on, m_stream_records,
+//   m_list_descs, m_empty_descs) the next whole-frame trace or query (m_setup_pending, set here
+//                                explicitly: Prepare sets it only when the frame's bytes changed, and
+//                                moved vertices leave the frame identical);
+//   every arena's per-slot plans DropPlans: scheduling only, but built from the old pose's bins.
+// The per-slot counters reset themselves at the end of the launches that use them, and an update is
+// stream-ordered after those, so they are left alone, as are the count parity (CullSlotState::uses),
+// m_cull_gen and the parameter tables (rewritten per call). Nothing else is keyed on the pose:
+// m_vertices, m_shade, m_order, m_rank and m_svertices are rewritten by the update itself.
+void DeviceScene::PoseChanged(bool vertices) {
+    (void)vertices;  // (a camera move invalidates all a vertex move does: every cache reads both)
+    if (m_width != 0) {
+        m_frame = MakeFrame(m_camera, m_width, m_height);
+    }
+    m_prepare_pending = true;
+    m_ext_pending = true;
+    m_setup_pending = true;
+    m_stream_on = false;
+    m_stream_records = 0;
+    m_list_descs = 0;
+    m_empty_descs = 0;
+    DropPlans(~std::size_t{0});
+}
+
+void DeviceScene::SetCamera(const Camera& camera, bool reorder, hipStream_t stream) {
+    if (reorder && m_n != 0) {
+        if (m_scratch == nullptr) {
+            m_scratch = new OrderScratch{};
+        }
+        AllocOrderScratch(*m_scratch, m_n, stream);  // (first use only)
+        OrderAfterPrevious(stream);
+        EnqueueMotion(m_vertices, m_n, camera, nullptr, m_scratch, m_order, m_rank, m_svertices, stream);
+        RecordOrder(stream);
+    }
+    m_camera = camera;
+    PoseChanged(false);
+}
+
+void DeviceScene::SetVertices(const float* d_vertices, bool reorder, hipStream_t stream) {
+    if (m_n == 0) {
+        return;
+    }
+    if (reorder) {
+        if (m_scratch == nullptr) {
+            m_scratch = new OrderScratch{};
+        }
+        AllocOrderScratch(*m_scratch, m_n, stream);  // (first use only)
+    }
+    OrderAfterPrevious(stream);
+    HipCheck(hipMemcpyAsync(m_vertices, d_vertices, m_n * 9 * sizeof(float), hipMemcpyDeviceToDevice, stream),
+             "hipMemcpyAsync(vertices)");
+    // (a failed enqueue below leaves the copy queued: the pose counts as changed either way)
+    try {
+        EnqueueMotion(m_vertices, m_n, m_camera, m_shade, reorder ? m_scratch : nullptr, m_order, m_rank, m_svertices,
+                      stream);
+    } catch (...) {
+        PoseChanged(true);
+        throw;
+    }
+    RecordOrder(stream);
+    PoseChanged(true);
 }
 
 // The block extents of the prepared frame, once per Prepare (on the first binned trace's stream,

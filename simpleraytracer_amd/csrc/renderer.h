@@ -20,6 +20,7 @@ namespace srt {
 struct CullBins;     // render.h
 struct CullSetup;    // render.h
 struct StageEvents;  // render.h
+struct OrderScratch;  // render.h
 
 // Throws std::runtime_error("HIP error: <what>: <reason>") on failure.
 void HipCheck(hipError_t err, const char* what);
@@ -192,6 +193,17 @@ public:
     void RenderSamples(const float* const* d_offsets, int* const* d_ids, std::size_t samples, float* d_rgba,
                        int variant, hipStream_t stream) const;
 
+    // Motion (include/srt_motion.h): the scene takes another camera, or other vertices (d_vertices:
+    // device, triangles x 9, copied on `stream`), in place. Afterwards it is the scene a fresh
+    // construction over the new pose would be, for every call above, bit for bit; a prepared scene
+    // stays prepared at its W x H. reorder: the spatial order is rebuilt under the new pose on
+    // `stream` (keys, radix sort, gather; the sort scratch is allocated by the first such update);
+    // else it stands -- a camera change then enqueues nothing, a vertex change the normals and the
+    // gather. A call on the scene for the ordering rule; no allocation besides that scratch, no
+    // host synchronisation.
+    void SetCamera(const Camera& camera, bool reorder, hipStream_t stream);
+    void SetVertices(const float* d_vertices, bool reorder, hipStream_t stream);
+
     std::size_t width() const { return m_width; }
     // The spatial order (device, triangles entries) and the time its build took at load (ms).
     const unsigned* order() const { return m_order; }
@@ -239,6 +251,12 @@ private:
     float* m_shade = nullptr;  // shading table: 8 floats per triangle (LaunchShadeTable)
     mutable float* m_edges = nullptr;        // kEdgeFloatsPerTriangle per padded record, per frame slot
     mutable std::size_t m_edge_slots = 1;    // frame slots of m_edges (TraceBatch grows it; slot 0 = Trace's)
+    // Sort scratch of the reordering updates (render.h OrderScratch): sizes depend on the triangle
+    // count only; allocated by the first such update, freed with the scene.
+    OrderScratch* m_scratch = nullptr;
+    // The one place that knows what a pose (camera, vertices) shapes: every cache below that is a
+    // function of it is dropped or marked for its lazy rebuild (renderer.cpp).
+    void PoseChanged(bool vertices);
     unsigned* m_order = nullptr;  // record ids in spatial order (BuildSpatialOrder), for the cull bins
     unsigned* m_rank = nullptr;   // its inverse: record id -> position
     float* m_svertices = nullptr; // vertices in spatial order (svertices[i] = vertices[order[i]])

@@ -457,4 +457,34 @@ Frame MakeFrame(const Camera& c, std::size_t width, std::size_t height) {
     return fr;
 }
 
+// camera10 = eye, lookat, up, vfov_deg, validated: what MakeFrame needs to give a finite frame.
+Camera CheckedCamera(const float camera10[10]) {
+    for (int k = 0; k < 10; ++k) {
+        if (!std::isfinite(camera10[k])) {
+            throw std::runtime_error("Bad camera: value " + std::to_string(k) + " is not finite");
+        }
+    }
+    Camera c{};
+    std::copy(camera10, camera10 + 3, c.eye);
+    std::copy(camera10 + 3, camera10 + 6, c.lookat);
+    std::copy(camera10 + 6, camera10 + 9, c.up);
+    c.vfov_deg = camera10[9];
+    if (!(c.vfov_deg > 0.f && c.vfov_deg < 180.f)) {
+        throw std::runtime_error("Bad camera: vfov must be in (0, 180) degrees");
+    }
+    double f[3];
+    for (int k = 0; k < 3; ++k) {
+        f[k] = static_cast<double>(c.lookat[k]) - static_cast<double>(c.eye[k]);
+    }
+    if (f[0] == 0.0 && f[1] == 0.0 && f[2] == 0.0) {
+        throw std::runtime_error("Bad camera: eye equals lookat");
+    }
+    const double r[3] = {f[1] * c.up[2] - f[2] * c.up[1], f[2] * c.up[0] - f[0] * c.up[2],
+                         f[0] * c.up[1] - f[1] * c.up[0]};
+    if (r[0] == 0.0 && r[1] == 0.0 && r[2] == 0.0) {
+        throw std::runtime_error("Bad camera: up is parallel to the view direction");
+    }
+    return c;
+}
+
 }  // namespace srt

@@ -61,4 +61,9 @@ Scene MakeScene(int kind, std::uint64_t triangles, std::uint64_t seed, float siz
 // Camera -> affine frame for a W x H image. Computed in double, rounded once to float.
 Frame MakeFrame(const Camera& camera, std::size_t width, std::size_t height);
 
+// camera10 = eye, lookat, up, vfov_deg as a Camera, validated: what MakeFrame needs to give a finite
+// frame (finite values, vfov in (0, 180), eye != lookat, up not parallel to the view). Throws
+// std::runtime_error("Bad camera: ..."). The one check of every entry point that takes a camera.
+Camera CheckedCamera(const float camera10[10]);
+
 }  // namespace srt

@@ -4,12 +4,18 @@
 // (a bin block's 256 consecutive records fall in few tiles) and the BVH variant's implicit
 // 8-wide tree is built over it. Only performance depends on the order: every frame is the
 // lexicographic (t, id) minimum, whatever order the records are visited in.
+// A moved scene (include/srt_motion.h) rebuilds the order in place from the same pieces, enqueued on
+// the caller's stream with the scene's own scratch (EnqueueMotion), or keeps it.
 #include <rocprim/device/device_radix_sort.hpp>
 
+#include <algorithm>
 #include <cmath>
 #include <stdexcept>
+#include <string>
+#include <vector>
 
 #include "render.h"
+#include "shading_normal.h"
 
 namespace srt {
 namespace {
@@ -21,6 +27,15 @@ struct KeyFrame {
     int valid;
 };
 
+// (isfinite names a device-only overload in HIP's headers; the host path takes the standard one)
+__device__ __host__ inline bool Finite(double x) {
+#ifdef __HIP_DEVICE_COMPILE__
+    return isfinite(x);
+#else
+    return std::isfinite(x);
+#endif
+}
+
 // Image-plane Morton code of triangle i's centroid: 16-bit cells of the half-height-scaled
 // image coordinates clamped to [-4, 4], y bit above x bit; 0xFFFFFFFF behind the eye (or a
 // degenerate camera). Double arithmetic in a fixed order (-ffp-contract=off): the code is the
@@ -31,14 +46,14 @@ __device__ __host__ inline unsigned MortonKey(const float* v, const KeyFrame& c)
         d[k] = (static_cast<double>(v[k]) + v[3 + k] + v[6 + k]) / 3.0 - c.eye[k];
     }
     const double z = (d[0] * c.f[0] + d[1] * c.f[1] + d[2] * c.f[2]) / c.fl;
-    if (!(c.valid != 0 && z > 0.0 && isfinite(z))) {
+    if (!(c.valid != 0 && z > 0.0 && Finite(z))) {
         return 0xFFFFFFFFu;
     }
     const double sx = (d[0] * c.r[0] + d[1] * c.r[1] + d[2] * c.r[2]) / c.rl / z / c.half_h;
     const double sy = -(d[0] * c.u[0] + d[1] * c.u[1] + d[2] * c.u[2]) / c.ul / z / c.half_h;
     auto cell = [](double w) {
         const double q = (fmin(fmax(w, -4.0), 4.0) + 4.0) / 8.0 * 65535.0;
-        return static_cast<unsigned>(isfinite(q) ? q : 0.0);
+        return static_cast<unsigned>(Finite(q) ? q : 0.0);
     };
     const unsigned qx = cell(sx), qy = cell(sy);
     unsigned key = 0;
@@ -53,6 +68,32 @@ __global__ __launch_bounds__(256) void MortonKeysKernel(const float* __restrict_
     const unsigned i = blockIdx.x * 256 + threadIdx.x;
     if (i < n) {
         keys[i] = MortonKey(vertices + 9ull * i, c);
+        ids[i] = i;
+    }
+}
+
+// The update pass of a moved scene (include/srt_motion.h), fusing what ShadeTableKernel and
+// MortonKeysKernel do at load in two passes over the same 36 bytes per triangle: kNormals, row 0 of
+// the shading table through ShadingNormal itself (row 1, the albedo, stays); kKeys, the Morton key
+// and the id. Moved vertices with the order kept: normals only; a moved camera: keys only.
+template <bool kNormals, bool kKeys>
+__global__ __launch_bounds__(256) void MotionKeysKernel(const float* __restrict__ vertices, unsigned n, KeyFrame c,
+                                                        float4* __restrict__ table, unsigned* __restrict__ keys,
+                                                        unsigned* __restrict__ ids) {
+    const unsigned i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) {
+        return;
+    }
+    float v[9];
+#pragma unroll
+    for (int k = 0; k < 9; ++k) {
+        v[k] = vertices[9ull * i + k];
+    }
+    if (kNormals) {
+        table[2ull * i] = ShadingNormal(v);
+    }
+    if (kKeys) {
+        keys[i] = MortonKey(v, c);
         ids[i] = i;
     }
 }
@@ -153,6 +194,92 @@ void BuildSpatialOrder(const float* d_vertices, std::uint64_t n, const Camera& c
         throw;
     }
     release();
+}
+
+void FreeOrderScratch(OrderScratch& s) noexcept {
+    (void)hipFree(s.keys);
+    (void)hipFree(s.keys_sorted);
+    (void)hipFree(s.ids);
+    (void)hipFree(s.temp);
+    s = OrderScratch{};
+}
+
+void AllocOrderScratch(OrderScratch& s, std::uint64_t n, hipStream_t stream) {
+    if (s.keys != nullptr || n == 0) {
+        return;
+    }
+    OrderScratch a;
+    try {
+        Check(hipMalloc(&a.keys, n * 4), "hipMalloc(morton keys)");
+        Check(hipMalloc(&a.keys_sorted, n * 4), "hipMalloc(sorted keys)");
+        Check(hipMalloc(&a.ids, n * 4), "hipMalloc(ids)");
+        unsigned* none = nullptr;
+        Check(rocprim::radix_sort_pairs(nullptr, a.temp_bytes, a.keys, a.keys_sorted, a.ids, none,
+                                        static_cast<unsigned>(n), 0, 32, stream),
+              "rocprim::radix_sort_pairs (size query)");
+        Check(hipMalloc(&a.temp, a.temp_bytes == 0 ? 4 : a.temp_bytes), "hipMalloc(sort temporary)");
+    } catch (...) {
+        FreeOrderScratch(a);
+        throw;
+    }
+    s = a;
+}
+
+void EnqueueMotion(const float* d_vertices, std::uint64_t n, const Camera& camera, float* d_shade,
+                   const OrderScratch* scratch, unsigned* d_order, unsigned* d_rank, float* d_svertices,
+                   hipStream_t stream) {
+    if (n == 0) {
+        return;
+    }
+    const unsigned un = static_cast<unsigned>(n);
+    const unsigned blocks = (un + 255) / 256;
+    float4* table = reinterpret_cast<float4*>(d_shade);
+    if (scratch != nullptr) {
+        const KeyFrame kf = MakeKeyFrame(camera);
+        if (d_shade != nullptr) {
+            hipLaunchKernelGGL((MotionKeysKernel<true, true>), dim3(blocks), dim3(256), 0, stream, d_vertices, un, kf, table,
+                               scratch->keys, scratch->ids);
+        } else {
+            hipLaunchKernelGGL((MotionKeysKernel<false, true>), dim3(blocks), dim3(256), 0, stream, d_vertices, un, kf,
+                               table, scratch->keys, scratch->ids);
+        }
+        Check(hipGetLastError(), "MotionKeysKernel launch");
+        // stable LSD radix sort: equal codes keep id order, so the order is unique, as at load
+        std::size_t temp_bytes = scratch->temp_bytes;
+        Check(rocprim::radix_sort_pairs(scratch->temp, temp_bytes, scratch->keys, scratch->keys_sorted, scratch->ids,
+                                        d_order, un, 0, 32, stream),
+              "rocprim::radix_sort_pairs");
+    } else if (d_shade != nullptr) {
+        hipLaunchKernelGGL((MotionKeysKernel<true, false>), dim3(blocks), dim3(256), 0, stream, d_vertices, un, KeyFrame{},
+                           table, static_cast<unsigned*>(nullptr), static_cast<unsigned*>(nullptr));
+        Check(hipGetLastError(), "MotionKeysKernel launch");
+    }
+    hipLaunchKernelGGL(RankKernel, dim3(blocks), dim3(256), 0, stream, d_order, un, d_vertices, d_rank, d_svertices);
+    Check(hipGetLastError(), "RankKernel launch");
+}
+
+void OrderHost(const float* vertices, std::uint64_t n, const Camera& camera, unsigned* order, float* normals) {
+    if (n > 0xFFFFFFFFull) {
+        throw std::runtime_error("Bad argument: more than 2^32 - 1 triangles");
+    }
+    if (normals != nullptr) {
+        for (std::uint64_t i = 0; i < n; ++i) {
+            const float4 nn = ShadingNormal(vertices + 9 * i);
+            normals[4 * i + 0] = nn.x;
+            normals[4 * i + 1] = nn.y;
+            normals[4 * i + 2] = nn.z;
+            normals[4 * i + 3] = nn.w;
+        }
+    }
+    if (order != nullptr) {
+        const KeyFrame kf = MakeKeyFrame(camera);
+        std::vector<unsigned> keys(n);
+        for (std::uint64_t i = 0; i < n; ++i) {
+            keys[i] = MortonKey(vertices + 9 * i, kf);
+            order[i] = static_cast<unsigned>(i);
+        }
+        std::stable_sort(order, order + n, [&](unsigned a, unsigned b) { return keys[a] < keys[b]; });
+    }
 }
 
 }  // namespace srt

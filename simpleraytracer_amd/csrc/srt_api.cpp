@@ -20,6 +20,7 @@
 #include "srt_layers.h"
 #include "srt_light.h"
 #include "srt_lighting.h"
+#include "srt_motion.h"
 #include "srt_omni.h"
 #include "srt_query.h"
 #include "srt_render.h"
@@ -1089,39 +1090,7 @@ RTK_API int rtkCompositeHost(const char* scene_path, size_t width, size_t height
 }
 
 // Spot-light shadow masks (include/srt_light.h): the rtl family.
-namespace {
-
-// camera10 = eye, lookat, up, vfov_deg, validated: what MakeFrame needs to give a finite frame.
-srt::Camera CheckedCamera(const float camera10[10]) {
-    for (int k = 0; k < 10; ++k) {
-        if (!std::isfinite(camera10[k])) {
-            throw std::runtime_error("Bad camera: value " + std::to_string(k) + " is not finite");
-        }
-    }
-    srt::Camera c{};
-    std::copy(camera10, camera10 + 3, c.eye);
-    std::copy(camera10 + 3, camera10 + 6, c.lookat);
-    std::copy(camera10 + 6, camera10 + 9, c.up);
-    c.vfov_deg = camera10[9];
-    if (!(c.vfov_deg > 0.f && c.vfov_deg < 180.f)) {
-        throw std::runtime_error("Bad camera: vfov must be in (0, 180) degrees");
-    }
-    double f[3];
-    for (int k = 0; k < 3; ++k) {
-        f[k] = static_cast<double>(c.lookat[k]) - static_cast<double>(c.eye[k]);
-    }
-    if (f[0] == 0.0 && f[1] == 0.0 && f[2] == 0.0) {
-        throw std::runtime_error("Bad camera: eye equals lookat");
-    }
-    const double r[3] = {f[1] * c.up[2] - f[2] * c.up[1], f[2] * c.up[0] - f[0] * c.up[2],
-                         f[0] * c.up[1] - f[1] * c.up[0]};
-    if (r[0] == 0.0 && r[1] == 0.0 && r[2] == 0.0) {
-        throw std::runtime_error("Bad camera: up is parallel to the view direction");
-    }
-    return c;
-}
-
-}  // namespace
+using srt::CheckedCamera;  // scene.h: shared with the rtm family below
 
 RTL_API srt_device_scene rtlSceneCreate(const char* path, int device, const float camera10[10]) {
     srt::DeviceScene* out = nullptr;
@@ -1539,6 +1508,119 @@ RTD_API int rtdLightHost(const char* scene_path, size_t width, size_t height, co
         const srt::Scene scene = srt::LoadScene(scene_path);
         srt::HostLighting(scene, width, height, in.data(), count, ambient, offsets, ids, row_begin, row_count, rgba,
                           classes);
+    });
+}
+
+// Dynamic scenes (include/srt_motion.h): the rtm family. Checks in the order flags, camera / origin,
+// handle, device buffer, so every refusal but the last is reachable without a device.
+static_assert(RTM_REORDER == 0 && RTM_KEEP_ORDER == 1, "include/srt_motion.h flags");
+
+namespace {
+
+bool CheckedReorder(int flags) {
+    if ((flags & ~RTM_KEEP_ORDER) != 0) {
+        throw std::runtime_error("Unknown motion flags " + std::to_string(flags));
+    }
+    return (flags & RTM_KEEP_ORDER) == 0;
+}
+
+srt::Camera CheckedCameraArg(const float camera10[10]) {
+    if (camera10 == nullptr) {
+        throw std::runtime_error("Bad argument: camera10 is NULL");
+    }
+    return CheckedCamera(camera10);
+}
+
+}  // namespace
+
+RTM_API int rtmSetCameraAsync(srt_device_scene scene, const float camera10[10], int flags, void* stream) {
+    return Guarded([&] {
+        const bool reorder = CheckedReorder(flags);
+        const srt::Camera camera = CheckedCameraArg(camera10);
+        if (scene == nullptr) {
+            throw std::runtime_error("Bad scene handle");
+        }
+        srt::DeviceScene* s = FromHandle(scene);
+        Bind bind(s->device());
+        s->SetCamera(camera, reorder, static_cast<hipStream_t>(stream));
+    });
+}
+
+RTM_API int rtmSetVerticesAsync(srt_device_scene scene, const float* d_vertices, int flags, void* stream) {
+    return Guarded([&] {
+        const bool reorder = CheckedReorder(flags);
+        if (scene == nullptr) {
+            throw std::runtime_error("Bad scene handle");
+        }
+        srt::DeviceScene* s = FromHandle(scene);
+        if (d_vertices == nullptr && s->triangles() != 0) {
+            throw std::runtime_error("Bad buffer argument: d_vertices is NULL");
+        }
+        Bind bind(s->device());
+        s->SetVertices(d_vertices, reorder, static_cast<hipStream_t>(stream));
+    });
+}
+
+RTM_API int rtmGetCamera(srt_device_scene scene, float camera10[10]) {
+    return Guarded([&] {
+        if (scene == nullptr) {
+            throw std::runtime_error("Bad scene handle");
+        }
+        if (camera10 == nullptr) {
+            throw std::runtime_error("Bad argument: camera10 is NULL");
+        }
+        const srt::Camera& c = FromHandle(scene)->camera();
+        std::copy(c.eye, c.eye + 3, camera10);
+        std::copy(c.lookat, c.lookat + 3, camera10 + 3);
+        std::copy(c.up, c.up + 3, camera10 + 6);
+        camera10[9] = c.vfov_deg;
+    });
+}
+
+RTM_API int rtmLightSetOriginAsync(rto_light light, const float origin3[3], int flags, void* stream) {
+    return Guarded([&] {
+        const bool reorder = CheckedReorder(flags);
+        CheckedOrigin(origin3);
+        srt::Camera cameras[srt::kOmniFaces];
+        for (int k = 0; k < srt::kOmniFaces; ++k) {  // (all six before the first face moves)
+            float c10[10];
+            srt::OmniFaceCamera(origin3, k, c10);
+            cameras[k] = CheckedCamera(c10);
+        }
+        if (light == nullptr) {
+            throw std::runtime_error("Bad light handle");
+        }
+        Bind bind(light->device);
+        for (int k = 0; k < srt::kOmniFaces; ++k) {
+            light->faces[k]->SetCamera(cameras[k], reorder, static_cast<hipStream_t>(stream));
+        }
+    });
+}
+
+RTM_API int rtmLightSetVerticesAsync(rto_light light, const float* d_vertices, int flags, void* stream) {
+    return Guarded([&] {
+        const bool reorder = CheckedReorder(flags);
+        if (light == nullptr) {
+            throw std::runtime_error("Bad light handle");
+        }
+        if (d_vertices == nullptr && light->faces[0]->triangles() != 0) {
+            throw std::runtime_error("Bad buffer argument: d_vertices is NULL");
+        }
+        Bind bind(light->device);
+        for (auto& f : light->faces) {
+            f->SetVertices(d_vertices, reorder, static_cast<hipStream_t>(stream));
+        }
+    });
+}
+
+RTM_API int rtmOrderHost(const float* vertices, unsigned long long n, const float camera10[10], unsigned* order,
+                         float* normals) {
+    return Guarded([&] {
+        const srt::Camera camera = CheckedCameraArg(camera10);
+        if (vertices == nullptr && n != 0) {
+            throw std::runtime_error("Bad argument: vertices is NULL");
+        }
+        srt::OrderHost(vertices, n, camera, order, normals);
     });
 }
 

@@ -1,7 +1,8 @@
 """Scene files, the device-level render stages (include/srt_render.h), point queries
 (include/srt_query.h), G-buffer outputs (include/srt_gbuffer.h), multi-sample frames
 (include/srt_samples.h), spot-light shadow masks (include/srt_light.h), omni-light shadow masks
-(include/srt_omni.h) and direct lighting (include/srt_lighting.h; the lights: lighting.py).
+(include/srt_omni.h), direct lighting (include/srt_lighting.h; the lights: lighting.py) and dynamic
+scenes (include/srt_motion.h).
 
 ``DeviceScene`` keeps a scene resident on one GPU and launches the two stages on a caller's
 HIP stream with caller-owned device buffers (torch tensors or raw pointers):
@@ -16,6 +17,7 @@ HIP stream with caller-owned device buffers (torch tensors or raw pointers):
     scene.layer_frame(offsets, ids_k, t_k, stream=s)             # the K nearest hits per pixel (also layers(), composite())
     scene.omni_shadow(omni, offsets, ids, mask, face, stream=s)  # which pixels a point light (an OmniLight) reaches
     scene.light(lights, offsets, ids, rgba, ambient, stream=s)   # the lit picture under several lights (also render_lit())
+    scene.set_camera(camera, stream=s)                           # move the camera in place (also set_vertices(), OmniLight.set_origin())
 
 This is the path bench.py times (inputs resident in HBM) and the one-process-per-GPU
 band renderer uses; ``runner.render`` is the host-image ml* path.
@@ -26,7 +28,7 @@ import ctypes
 import os
 
 from . import _native
-from ._native import (RTK_MAX_LAYERS, RTS_MAX_SAMPLES, SRT_MAX_BATCH, SRT_SCENE_CORNELL, SRT_SCENE_SOUP, SRT_SCENE_TRIANGLE, SRT_TRACE_BVH,
+from ._native import (RTK_MAX_LAYERS, RTM_KEEP_ORDER, RTM_REORDER, RTS_MAX_SAMPLES, SRT_MAX_BATCH, SRT_SCENE_CORNELL, SRT_SCENE_SOUP, SRT_SCENE_TRIANGLE, SRT_TRACE_BVH,
                       SRT_TRACE_CULL, SRT_TRACE_LDS, SRT_TRACE_SCALAR)
 
 SCENE_KINDS = {"triangle": SRT_SCENE_TRIANGLE, "cornell": SRT_SCENE_CORNELL, "soup": SRT_SCENE_SOUP}
@@ -343,6 +345,25 @@ def tile_of(width: int, height: int, fx: float, fy: float):
             return None
         raise SrtError(_native.last_error())
     return c.value, r.value
+
+
+def order_host(vertices, camera):
+    """The spatial order and the shading normals on the host (rtmOrderHost: the library's own Morton
+    key and a stable sort, no device): vertices (n, 9) or (n, 3, 3) float32 and camera (10 floats)
+    -> (order (n,) uint32: what spatial_order() reports for these triangles under this camera,
+    normals (n, 4) float32: (cross(v1 - v0, v2 - v0), its length), row 0 of the shading table)."""
+    import numpy as np
+
+    v = np.ascontiguousarray(vertices, np.float32)
+    if v.ndim == 3 and v.shape[1:] == (3, 3):
+        v = v.reshape(-1, 9)
+    if v.ndim != 2 or v.shape[1] != 9:
+        raise ValueError(f"vertices must be (n, 9) or (n, 3, 3), got {v.shape}")
+    n = v.shape[0]
+    order = np.empty(n, np.uint32)
+    normals = np.empty((n, 4), np.float32)
+    _check(_native.lib().rtmOrderHost(v.ctypes.data, n, _camera10(camera), order.ctypes.data, normals.ctypes.data))
+    return order, normals
 
 
 def _ptr(x) -> int:
@@ -712,9 +733,42 @@ class DeviceScene:
         _check(self._lib.rtsRenderAsync(self.handle, offs, idp, samples, _ptr(rgba), TRACE_VARIANTS[variant],
                                         _stream(stream)))
 
+    @property
+    def camera(self):
+        """The scene's camera (eye, lookat, up, vfov_deg: 10 floats): the file's, the constructor's
+        or the last one set (rtmGetCamera; host state, no device work)."""
+        cam = (ctypes.c_float * 10)()
+        _check(self._lib.rtmGetCamera(self.handle, cam))
+        return tuple(cam)
+
+    def set_camera(self, camera, reorder: bool = True, stream=None):
+        """Move the camera in place (include/srt_motion.h): afterwards every call answers as a fresh
+        DeviceScene(path, device, camera=camera) would, bit for bit; a prepared scene stays prepared.
+        reorder=True rebuilds the spatial order under the new camera on `stream`; False keeps the
+        standing order (no kernel at all: the same answers, only speed differs)."""
+        _check(self._lib.rtmSetCameraAsync(self.handle, _camera10(camera), RTM_REORDER if reorder else RTM_KEEP_ORDER,
+                                           _stream(stream)))
+
+    def _check_vertices(self, vertices):
+        if hasattr(vertices, "shape") and tuple(vertices.shape) not in ((self.triangles, 9), (self.triangles, 3, 3)):
+            raise ValueError(f"vertices must be {(self.triangles, 9)} or {(self.triangles, 3, 3)}, "
+                             f"got {tuple(vertices.shape)}")
+        self._check_tensor("vertices", vertices, "f32")
+
+    def set_vertices(self, vertices, reorder: bool = True, stream=None):
+        """Move the triangles in place (rtmSetVerticesAsync): vertices (n, 9) or (n, 3, 3) float32, a
+        contiguous device buffer read on `stream` (reusable once the stream has passed the call). The
+        triangle count and the albedo stay. Afterwards every call answers as a fresh scene over a
+        file of these vertices would. reorder as set_camera()'s; with False the shading normals and
+        the vertices' spatial copy are still rewritten."""
+        self._check_vertices(vertices)
+        _check(self._lib.rtmSetVerticesAsync(self.handle, _ptr(vertices), RTM_REORDER if reorder else RTM_KEEP_ORDER,
+                                             _stream(stream)))
+
     def spatial_order(self):
         """(order, build_ms): the record ids in spatial order (numpy uint32), built on the device
-        at load, and the build's device time."""
+        at load (and again by a reordering set_camera() / set_vertices()), and the load-time build's
+        device time."""
         import numpy as np
 
         out = np.empty(max(1, self.triangles), np.uint32)
@@ -815,6 +869,21 @@ class OmniLight:
         self.face_size = face_size
         for f in self._faces.values():
             f.width = f.height = face_size
+
+    def set_origin(self, origin, reorder: bool = True, stream=None):
+        """Move the light in place (rtmLightSetOriginAsync): the six faces take the cameras
+        omni_face_camera(origin, k) on one stream; the face size stays. reorder as
+        DeviceScene.set_camera()'s."""
+        _check(self._lib.rtmLightSetOriginAsync(self.handle, _float3("origin", origin),
+                                                RTM_REORDER if reorder else RTM_KEEP_ORDER, _stream(stream)))
+        self.origin = tuple(float(v) for v in origin)
+
+    def set_vertices(self, vertices, reorder: bool = True, stream=None):
+        """Move the triangles of all six faces in place (rtmLightSetVerticesAsync); vertices and
+        reorder as DeviceScene.set_vertices()'s."""
+        self.face(0)._check_vertices(vertices)
+        _check(self._lib.rtmLightSetVerticesAsync(self.handle, _ptr(vertices),
+                                                  RTM_REORDER if reorder else RTM_KEEP_ORDER, _stream(stream)))
 
     def face(self, k: int):
         """Face k (0 .. 5) as a DeviceScene that does not own its handle: every DeviceScene call

@@ -7,6 +7,9 @@ DeviceScene.render_lit() and device.lighting_host() take.
 
 A device light wraps a prepared scene of the same triangles -- a DeviceScene under the light's
 camera (a spot light) or an OmniLight (a point light) -- and may appear in a call more than once.
+It holds that scene by reference, so a moved light scene is a moved light: after
+scene.set_camera() / OmniLight.set_origin() / set_vertices() (include/srt_motion.h) the same
+SpotLight / PointLight object lights from the new pose, with nothing to rebuild here.
 The host twins describe the same lights without a device: a camera and its frame, or an origin and
 the cube faces' size.
 """
