@@ -3586,24 +3586,98 @@ __global__ __launch_bounds__(kCullThreads, SRT_TRACE_OCC) void TraceCullKernel(c
 }
 
 // ---------------------------------------------------------------------------------------
+// The candidate walk (DESIGN.md section 5 "Point queries"): every record that can pass the exact
+// test at one position of a prepared frame, visited by the LANES lanes that share the position.
+// The query, layers, shadow, omni-shadow and lighting kernels all answer "what does this position
+// see" with it, so their exactness rests on this one argument.
+// The setup's lists were binned against the analytic tile boxes, and that binning is about boxes,
+// not pixel grids: BoxMayHit bounds the edge functions at every (fx, fy) of the box, and a record's
+// screen box contains every position with |fx|, |fy| <= kScreenBoxRange at which its float test can
+// pass. So a position inside a usable tile box passes the exact test of no record outside that
+// tile's list and the large list (listed: entries [0, cnt) of the tile's list, then the large
+// list's). A position outside [0, 1]^2 (NaN included), a tile whose list overflowed or whose box is
+// not ScreenBoxUsable, and a frame without a setup (tile_info null) stream every record instead:
+// positions [0, stream_end), pad records included (disabled: they pass nowhere).
+// FindCandidates serves TraceParams and LightFrame through their common field names and copies each
+// field it uses into a local once: a frame selected per lane is read with vector loads from the
+// argument segment, a uniform one with scalar loads.
+// WalkCandidates: the lanes stride the candidates (a coalesced 4-B entry load, then each lane
+// gathers its record), AHEAD candidates per lane and round, so a round has that many dependent
+// load pairs in flight: AHEAD entries, AHEAD record loads, AHEAD tests. A lane past the end repeats
+// the last candidate (no divergent tail), so `test` must be idempotent: a (t, id) minimum and
+// KeyList::Insert are. stop() is evaluated once per round, by every lane of the group alike;
+// returns whether it ended the walk.
+// ---------------------------------------------------------------------------------------
+struct Candidates {
+    const unsigned* list;        // the tile's list
+    const unsigned* large_list;
+    unsigned cnt;                // entries of the tile's list
+    unsigned total;              // candidates: cnt + the large list's entries, or stream_end
+    bool listed;                 // from the lists; else streamed
+    __device__ __forceinline__ unsigned Entry(unsigned k) const {
+        if (!listed) {
+            return k;
+        }
+        const unsigned* at = k < cnt ? list + k : large_list + (k - cnt);
+        return *at;
+    }
+};
+
+template <class F>
+__device__ __forceinline__ Candidates FindCandidates(const F& f, int tiles_y, unsigned stream_end, float fx, float fy) {
+    Candidates c{nullptr, nullptr, 0u, stream_end, false};
+    int col = 0, row = 0;
+    const TileInfo* tile_info = f.tile_info;
+    const int tiles_x = f.tiles_x;
+    if (tile_info != nullptr && TileOfPosition(fx, fy, f.wf, f.hf, kCullTileCols, kTileRows, tiles_x, tiles_y, col, row)) {
+        const unsigned tile = static_cast<unsigned>(row) * static_cast<unsigned>(tiles_x) + static_cast<unsigned>(col);
+        const unsigned* counts = f.bin_counts;
+        const unsigned capacity = f.bin_capacity;
+        c.cnt = counts[tile];
+        const unsigned large = counts[f.tiles];
+        c.list = f.bin_lists + static_cast<size_t>(tile) * capacity;
+        c.large_list = f.large_list;
+        c.listed = c.cnt <= capacity && tile_info[tile].usable != 0u;
+        c.total = c.listed ? c.cnt + large : stream_end;
+    }
+    return c;
+}
+
+template <int LANES, int AHEAD, class Raw, class Load, class Test, class Stop>
+__device__ __forceinline__ bool WalkCandidates(const Candidates& c, unsigned lane, Load load, Test test, Stop stop) {
+    for (unsigned base = 0u; base < c.total; base += AHEAD * LANES) {
+        unsigned pos[AHEAD];
+        Raw raw[AHEAD];
+#pragma unroll
+        for (int a = 0; a < AHEAD; ++a) {
+            pos[a] = c.Entry(min(base + a * LANES + lane, c.total - 1u));
+        }
+#pragma unroll
+        for (int a = 0; a < AHEAD; ++a) {
+            raw[a] = load(pos[a]);
+        }
+#pragma unroll
+        for (int a = 0; a < AHEAD; ++a) {
+            test(raw[a]);
+        }
+        if (stop()) {
+            return true;
+        }
+    }
+    return false;
+}
+
+// ---------------------------------------------------------------------------------------
 // Point queries (render.h LaunchQuery; DESIGN.md section 5 "Point queries"): the closest hit at
-// arbitrary image positions of the prepared frame, answered from the shared setup's lists.
-// The lists were binned against the analytic tile boxes, and that binning is about boxes, not pixel
-// grids: BoxMayHit bounds the edge functions at every (fx, fy) of the box, and a record's screen box
-// contains every position with |fx|, |fy| <= kScreenBoxRange at which its float test can pass. So a
-// position inside a usable tile box passes the exact test of no record outside that tile's list and
-// the large list. A position outside [0, 1]^2 (NaN included), a tile whose list overflowed or whose
-// box is not ScreenBoxUsable, and a scene without a setup stream every record instead.
-// A group of kQueryLanes lanes per query: the lanes stride the candidates (a coalesced 4-B entry
-// load, then each lane gathers its record), run the trace kernels' exact test on them
-// (ExactTestAnyOrder, one ray) and the group reduces the (t, id) key with shuffles -- no LDS, no
-// atomics, no cross-block traffic. kQueryAhead candidates per lane and round, so a round has that
-// many dependent load pairs in flight; a lane past the end repeats the last candidate, which
-// changes no minimum (no divergent tail). The kernel is bound by the latency of its chain of
-// dependent loads (position -> tile counts -> list entries -> records), not by bandwidth or VALU, so
-// fewer, fuller waves win: 16 lanes x 2 candidates measured best of 64 / 32 / 16 / 8 lanes and
-// 1 / 2 / 4 candidates at C3 (profiles/query/). SRT_QUERY_LANES, SRT_QUERY_AHEAD:
-// measurement builds.
+// arbitrary image positions of the prepared frame, answered from the shared setup's lists by the
+// candidate walk above.
+// A group of kQueryLanes lanes per query runs the trace kernels' exact test on the candidates
+// (ExactTestAnyOrder, one ray) and reduces the (t, id) key with shuffles -- no LDS, no atomics, no
+// cross-block traffic; a repeated last candidate changes no minimum. The kernel is bound by the
+// latency of its chain of dependent loads (position -> tile counts -> list entries -> records), not
+// by bandwidth or VALU, so fewer, fuller waves win: 16 lanes x 2 candidates measured best of
+// 64 / 32 / 16 / 8 lanes and 1 / 2 / 4 candidates at C3 (profiles/query/).
+// SRT_QUERY_LANES, SRT_QUERY_AHEAD: measurement builds.
 // ---------------------------------------------------------------------------------------
 #ifndef SRT_QUERY_LANES
 #define SRT_QUERY_LANES 16
@@ -3646,47 +3720,14 @@ __global__ __launch_bounds__(kQueryThreads) void QueryKernel(const QueryParams q
     s.fy[0] = f.y;
     s.bt[0] = __builtin_inff();
     s.bi[0] = -1;
-    int col = 0, row = 0;
-    bool listed = p.tile_info != nullptr &&
-                  TileOfPosition(f.x, f.y, p.wf, p.hf, kCullTileCols, kTileRows, p.tiles_x, q.tiles_y, col, row);
-    unsigned cnt = 0u, large = 0u;
-    const unsigned* list = nullptr;
-    if (listed) {
-        const unsigned tile = static_cast<unsigned>(row) * static_cast<unsigned>(p.tiles_x) + static_cast<unsigned>(col);
-        cnt = p.bin_counts[tile];
-        large = p.bin_counts[p.tiles];
-        list = p.bin_lists + static_cast<size_t>(tile) * p.bin_capacity;
-        listed = cnt <= p.bin_capacity && p.tile_info[tile].usable != 0u;
-    }
-    const unsigned total = listed ? cnt + large : q.stream_end;
-    auto entry = [&](unsigned k) {
-        if (!listed) {
-            return k;
-        }
-        const unsigned* at = k < cnt ? list + k : p.large_list + (k - cnt);
-        return *at;
-    };
+    const Candidates cand = FindCandidates(p, q.tiles_y, q.stream_end, f.x, f.y);
     auto test = [&](const typename Recs::Raw& raw) {
         const CullRecord r = Recs::Make(p, raw);
         const Record rec{r.a.x, r.a.y, r.a.z, r.a.w, r.b.x, r.b.y, r.b.z, r.b.w, r.x.x};
         ExactTestAnyOrder<1, false>(s, rec, r.x.y, static_cast<int>(__float_as_uint(r.x.z)));
     };
-    for (unsigned base = 0u; base < total; base += kQueryAhead * kQueryLanes) {
-        unsigned pos[kQueryAhead];
-        typename Recs::Raw raw[kQueryAhead];
-#pragma unroll
-        for (int a = 0; a < kQueryAhead; ++a) {
-            pos[a] = entry(min(base + a * kQueryLanes + lane, total - 1u));
-        }
-#pragma unroll
-        for (int a = 0; a < kQueryAhead; ++a) {
-            raw[a] = Recs::Load(p, pos[a]);
-        }
-#pragma unroll
-        for (int a = 0; a < kQueryAhead; ++a) {
-            test(raw[a]);
-        }
-    }
+    WalkCandidates<kQueryLanes, kQueryAhead, typename Recs::Raw>(
+        cand, lane, [&](unsigned pos) { return Recs::Load(p, pos); }, test, [] { return false; });
     // The lanes' (t, id) minimum; a miss is (+inf, -1), above every hit's key (a hit's t < +inf).
     unsigned long long key = HitKey(s.bt[0], s.bi[0]);
 #pragma unroll
@@ -3700,7 +3741,7 @@ __global__ __launch_bounds__(kQueryThreads) void QueryKernel(const QueryParams q
         q.ids[query] = static_cast<int>(static_cast<unsigned>(key));
         q.t[query] = __uint_as_float(static_cast<unsigned>(key >> 32));
         if (q.how != nullptr) {
-            q.how[query] = listed ? 0 : 1;
+            q.how[query] = cand.listed ? 0 : 1;
         }
     }
 }
@@ -3708,11 +3749,9 @@ __global__ __launch_bounds__(kQueryThreads) void QueryKernel(const QueryParams q
 // ---------------------------------------------------------------------------------------
 // Depth layers (render.h LaunchLayers; DESIGN.md section 5 "Depth layers"): the K lexicographically
 // smallest (t, id) keys among the records that pass the exact test at an image position, K <=
-// kMaxLayers -- QueryKernel keeping K keys instead of one. The exactness argument is the query's:
-// the tile's list plus the large list hold every record that can pass anywhere in the tile's box, so
-// the K smallest keys over them are the K smallest over all records. Mapping, streaming conditions
-// and loads are QueryKernel's (a group of kLayersLanes lanes per position, kLayersAhead candidates
-// per lane and round, a lane past the end repeats the last candidate). POINTS: position i is read
+// kMaxLayers -- QueryKernel keeping K keys instead of one: the candidate walk visits every record
+// that can pass at the position, so the K smallest keys over it are the K smallest over all records.
+// The mapping is QueryKernel's (a group of kLayersLanes lanes per position). POINTS: position i is read
 // from `where`; else element (x, y) is pixel (x, row_begin + y) of the frame and its position ray
 // generation's expression of its sample offset (GBufferKernel's convention, buffers band-local).
 // Each lane keeps its CAP smallest keys sorted in registers (KeyList: compile-time indices only, no
@@ -3821,26 +3860,7 @@ __global__ __launch_bounds__(kLayersThreads) void LayersKernel(const LayersParam
         f.x = (static_cast<float>(x) + f.x) / q.wf;
         f.y = (static_cast<float>(q.row_begin + row) + f.y) / q.hf;
     }
-    int col = 0, trow = 0;
-    bool listed = p.tile_info != nullptr &&
-                  TileOfPosition(f.x, f.y, p.wf, p.hf, kCullTileCols, kTileRows, p.tiles_x, q.tiles_y, col, trow);
-    unsigned cnt = 0u, large = 0u;
-    const unsigned* list = nullptr;
-    if (listed) {
-        const unsigned tile = static_cast<unsigned>(trow) * static_cast<unsigned>(p.tiles_x) + static_cast<unsigned>(col);
-        cnt = p.bin_counts[tile];
-        large = p.bin_counts[p.tiles];
-        list = p.bin_lists + static_cast<size_t>(tile) * p.bin_capacity;
-        listed = cnt <= p.bin_capacity && p.tile_info[tile].usable != 0u;
-    }
-    const unsigned total = listed ? cnt + large : q.stream_end;
-    auto entry = [&](unsigned k) {
-        if (!listed) {
-            return k;
-        }
-        const unsigned* e = k < cnt ? list + k : p.large_list + (k - cnt);
-        return *e;
-    };
+    const Candidates cand = FindCandidates(p, q.tiles_y, q.stream_end, f.x, f.y);
     KeyList<CAP> keys;
     keys.Clear();
     auto test = [&](const typename Recs::Raw& raw) {
@@ -3851,24 +3871,10 @@ __global__ __launch_bounds__(kLayersThreads) void LayersKernel(const LayersParam
             keys.Insert(HitKey(t, static_cast<int>(__float_as_uint(r.x.z))));
         }
     };
-    for (unsigned base = 0u; base < total; base += kLayersAhead * kLanes) {
-        unsigned pos[kLayersAhead];
-        typename Recs::Raw raw[kLayersAhead];
-#pragma unroll
-        for (int a = 0; a < kLayersAhead; ++a) {
-            pos[a] = entry(min(base + a * kLanes + lane, total - 1u));
-        }
-#pragma unroll
-        for (int a = 0; a < kLayersAhead; ++a) {
-            raw[a] = Recs::Load(p, pos[a]);
-        }
-#pragma unroll
-        for (int a = 0; a < kLayersAhead; ++a) {
-            test(raw[a]);
-        }
-    }
+    WalkCandidates<kLanes, kLayersAhead, typename Recs::Raw>(
+        cand, lane, [&](unsigned pos) { return Recs::Load(p, pos); }, test, [] { return false; });
     if (lane == 0u && q.how != nullptr) {
-        q.how[at] = listed ? 0 : 1;
+        q.how[at] = cand.listed ? 0 : 1;
     }
 #pragma unroll
     for (int k = 0; k < CAP; ++k) {
@@ -3977,22 +3983,193 @@ __global__ __launch_bounds__(kCompositeThreads) void CompositeKernel(const Compo
 }
 
 // ---------------------------------------------------------------------------------------
+// What the shadow kernels share (ShadowKernel, OmniShadowKernel, LightingKernel): the pixel of a band
+// of the view frame, a light frame, and the occlusion test of the pixel's surface point in it.
+// A group of LANES lanes per pixel, QueryKernel's mapping; every lane of the group computes the
+// pixel's facts (its own loads are the group's: one address, one request).
+// ---------------------------------------------------------------------------------------
+// The band of the view frame a launch covers, and the view scene's buffers.
+struct ViewBand {
+    const float* __restrict__ vertices;  // the view scene's, by id
+    const float4* __restrict__ shade;    // the view scene's shading table
+    const float2* __restrict__ offsets;  // band-local
+    const int* __restrict__ ids;         // band-local
+    unsigned n;                          // triangles of every scene of the launch
+    unsigned width;
+    unsigned row_begin;
+    unsigned pixels;  // of the band
+    float wf, hf;     // the view frame's
+    float eye[3], base[3], du[3], dv[3], bg[3];
+};
+
+// A pixel of the band: its hit id, its position, and -- on a surface -- the depth of the hit from the
+// view scene's vertices (ComputeEdges, the traces' bits).
+struct ViewPixel {
+    int code;
+    float fx, fy;
+    bool surface;
+    float t;
+};
+__device__ __forceinline__ ViewPixel ViewPixelAt(const ViewBand& v, unsigned pixel) {
+    ViewPixel px;
+    px.code = v.ids[pixel];
+    const float2 o = v.offsets[pixel];
+    const unsigned y = pixel / v.width, x = pixel - y * v.width;
+    px.fx = (static_cast<float>(x) + o.x) / v.wf;
+    px.fy = (static_cast<float>(v.row_begin + y) + o.y) / v.hf;
+    px.surface = static_cast<unsigned>(px.code) < v.n;
+    px.t = 0.f;
+    if (px.surface) {
+        const float* at = v.vertices + 9ull * static_cast<unsigned>(px.code);
+        float vx[9], c[9], vol;
+#pragma unroll
+        for (int j = 0; j < 9; ++j) {
+            vx[j] = at[j];
+        }
+        ComputeEdges(v.eye, v.base, v.du, v.dv, vx, true, c, vol);
+        px.t = ShadowDepth(c, vol, px.fx, px.fy);
+    }
+    return px;
+}
+
+// The shaded pixel of a mask kernel (background, id -1 off a surface), computed before the scan: the
+// view frame's vectors need not stay live across it. StoreDimmed scales it by the class's factor.
+__device__ __forceinline__ F4 ShadedPixel(const ViewBand& v, const ViewPixel& px, bool wanted) {
+    F4 out{v.bg[0], v.bg[1], v.bg[2], -1.f};
+    if (wanted && px.surface) {
+        const float4* sr = v.shade + 2ull * static_cast<unsigned>(px.code);
+        const float4 nr = sr[0], al = sr[1];
+        const ResolveRgb c = ResolveShadeHit(v.base, v.du, v.dv, px.fx, px.fy, nr.x, nr.y, nr.z, nr.w, al.x, al.y, al.z);
+        out = F4{c.r, c.g, c.b, static_cast<float>(px.code)};
+    }
+    return out;
+}
+__device__ __forceinline__ void StoreDimmed(F4* at, F4 out, bool surface, unsigned char cls, float dim) {
+    if (surface) {
+        const float k = ShadowScale(cls, dim);
+        out = F4{out.x * k, out.y * k, out.z * k, out.w};
+    }
+    StoreNontemporal(at, out);
+}
+
+// A light frame: what the occlusion test reads of a prepared frame under a light's camera (a spot
+// light's one, a cube face of a point light) -- 168 B, not a TraceParams, so that up to sixteen
+// travel by value in the kernel-argument segment.
+struct LightFrame {
+    const CullRecord* cull;        // stored records by position (RC = false)
+    const float* svertices;        // vertices by position (RC = true)
+    const unsigned* rank;          // the light scene's record id -> position
+    const TileInfo* tile_info;     // null: no setup, every pixel of the frame streams
+    const unsigned* bin_lists;
+    const unsigned* bin_counts;
+    const unsigned* large_list;
+    unsigned bin_capacity;
+    unsigned tiles;
+    int tiles_x, tiles_y;
+    unsigned stream_end;           // records of a streamed pixel: positions [0, stream_end)
+    float wf, hf;                  // the light frame's
+    float base[3], du[3], dv[3];
+    float rows[9];                 // the frame's projection rows (px, py, pz)
+    float origin[3];
+};
+static_assert(sizeof(LightFrame) == 168, "light frames travel in the kernel-argument segment");
+
+// Whether a lane of the caller's group of LANES holds `mine` (the same value in every lane of the
+// group): a ballot, so an exit on it is uniform for the group whatever the wave's other groups do.
+template <int LANES>
+__device__ __forceinline__ bool GroupAny(bool mine) {
+    const unsigned long long b = __ballot(mine);
+    if constexpr (LANES == kWave) {
+        return b != 0ull;
+    } else {
+        const unsigned first = (threadIdx.x & (kWave - 1)) & ~static_cast<unsigned>(LANES - 1);
+        return ((b >> first) & ((1ull << LANES) - 1ull)) != 0ull;
+    }
+}
+
+// A light frame's candidate record by position, as TraceRecords<RC> gives a trace its own (the
+// screen box, which the exact test does not read, left out).
+template <bool RC>
+struct LightRecords {
+    struct Raw {
+        float4 a, b, x;
+    };
+    static __device__ __forceinline__ Raw Load(const LightFrame& f, unsigned, unsigned pos) {
+        const float4* at = reinterpret_cast<const float4*>(f.cull + pos);
+        return Raw{at[0], at[1], at[2]};
+    }
+    static __device__ __forceinline__ Raw Make(const LightFrame&, unsigned, const Raw& r) { return r; }
+};
+template <>
+struct LightRecords<true> {
+    struct Raw {
+        float v[9];
+        unsigned id;
+    };
+    using Made = LightRecords<false>::Raw;
+    static __device__ __forceinline__ Raw Load(const LightFrame& f, unsigned n, unsigned pos) {
+        Raw r;
+        const bool real = pos < n;
+        const float4* v = reinterpret_cast<const float4*>(f.svertices + static_cast<size_t>(kSpatialStride) * (real ? pos : 0u));
+        const float4 v0 = v[0], v1 = v[1], v2 = v[2];
+        r.v[0] = v0.x, r.v[1] = v0.y, r.v[2] = v0.z, r.v[3] = v0.w;
+        r.v[4] = v1.x, r.v[5] = v1.y, r.v[6] = v1.z, r.v[7] = v1.w;
+        r.v[8] = v2.x;
+        r.id = real ? __float_as_uint(v2.y) : pos;
+        return r;
+    }
+    static __device__ __forceinline__ Made Make(const LightFrame& f, unsigned n, const Raw& r) {
+        float c[9], vol;
+        ComputeEdges(f.origin, f.base, f.du, f.dv, r.v, r.id < n, c, vol);
+        return Made{make_float4(c[0], c[1], c[2], c[3]), make_float4(c[4], c[5], c[6], c[7]),
+                    make_float4(c[8], vol, __uint_as_float(r.id), 0.f)};
+    }
+};
+
+// The class (shadowed or lit) of the surface point of triangle `code` that projects to sp in light
+// frame f (sp.inside). First the exact test of the point's OWN triangle under the frame's records
+// (position = the light scene's rank of the id): its t_id there, +inf if it does not pass. The point
+// is shadowed iff some record j != id passes the exact test at (gx, gy) with t_j < thr and
+// (t_j, j) < (t_id, id) -- ExactTestAnyOrder started from the bound min((thr, below every id),
+// (t_id, id)) takes a candidate exactly then (the own triangle's entry in the list ties with the
+// bound and is not taken) -- so the group walks the frame's candidates and leaves at the end of the
+// first round in which a lane took one.
+template <bool RC, int LANES, int AHEAD>
+__device__ __forceinline__ unsigned char OccludedAt(const LightFrame& f, unsigned n, int code, const ShadowPoint& sp,
+                                                    unsigned lane) {
+    using Recs = LightRecords<RC>;
+    Rays<1> s;
+    s.fx[0] = sp.gx;
+    s.fy[0] = sp.gy;
+    s.bt[0] = __builtin_inff();
+    s.bi[0] = -1;
+    const Candidates cand = FindCandidates(f, f.tiles_y, f.stream_end, sp.gx, sp.gy);
+    auto load = [&](unsigned pos) { return Recs::Load(f, n, pos); };
+    auto test = [&](const typename Recs::Raw& raw) {
+        const auto r = Recs::Make(f, n, raw);
+        const Record rec{r.a.x, r.a.y, r.a.z, r.a.w, r.b.x, r.b.y, r.b.z, r.b.w, r.x.x};
+        ExactTestAnyOrder<1, false>(s, rec, r.x.y, static_cast<int>(__float_as_uint(r.x.z)));
+    };
+    test(load(f.rank[static_cast<unsigned>(code)]));
+    if (sp.thr <= s.bt[0]) {  // the bound: (thr, below every id) or (t_id, id), whichever is lower
+        s.bt[0] = sp.thr;
+        s.bi[0] = static_cast<int>(0x80000000u);
+    }
+    const int bound_id = s.bi[0];
+    const bool occluded = WalkCandidates<LANES, AHEAD, typename Recs::Raw>(
+        cand, lane, load, test, [&] { return GroupAny<LANES>(s.bi[0] != bound_id); });  // below the bound: an occluder
+    return occluded ? kShadowShadowed : kShadowLit;
+}
+
+// ---------------------------------------------------------------------------------------
 // Spot-light shadow mask (render.h LaunchShadow; DESIGN.md section 5 "Shadow"): the class of every
 // pixel of a band of the view frame -- shadowed, lit, outside the light's frustum, no surface
 // (shadow_math.h) -- from its hit id, with the light given as a second prepared frame: a point query
 // in the light's frame at the position the pixel's surface point projects to, fused with the
 // projection and stopped at the first occluder.
-// A group of kShadowLanes lanes per pixel, QueryKernel's mapping. Every lane of the group computes
-// the pixel's facts (its own loads are the group's: one address, one request): the depth of the hit
-// from the view scene's vertices (ComputeEdges, the traces' bits), the surface point and its
-// light-frame position (gx, gy), z and thr. Then the light's tile, and the exact test of the pixel's
-// OWN triangle under the light's records (position = the light scene's rank of the id): its t_id
-// there, +inf if it does not pass. The pixel is shadowed iff some record j != id passes the exact
-// test at (gx, gy) with t_j < thr and (t_j, j) < (t_id, id) -- ExactTestAnyOrder started from the
-// bound min((thr, lowest id), (t_id, id)) takes a candidate exactly then (the own triangle's entry in
-// the list ties with the bound and is not taken) -- so the lanes stride the tile's list and the
-// large list as the query does and the group leaves at the end of the first round in which a lane
-// took one: a ballot, so the exit is uniform for the group whatever the wave's other groups do.
+// A group of kShadowLanes lanes per pixel: ViewPixelAt, the surface point and its light-frame
+// position (gx, gy), z and thr (ShadowProject), then OccludedAt in the light's frame, which is one
+// LightFrame and uniform here (scalar loads).
 // No LDS, no atomics, no scratch. Lane 0 stores the class byte and, asked for, the shaded pixel
 // times the class's scale. Lanes x candidates per round, measured at C3 under two lights and two
 // light-frame sizes (64 ... 2 lanes, 1 / 2 / 4 candidates: DESIGN.md; profiles/shadow/): most pixels
@@ -4013,144 +4190,36 @@ constexpr int kShadowThreads = 256;
 constexpr int kShadowBlock = kShadowThreads / kShadowLanes;  // pixels per block
 static_assert(kShadowLanes >= 2 && kWave % kShadowLanes == 0, "a pixel's lanes share a wave");
 struct ShadowParams {
-    TraceParams rec;  // the light: its records (TraceRecords), frame vectors, setup tiles, lists and counts
-    const unsigned* __restrict__ rank;   // the light scene's record id -> position
-    const float* __restrict__ vertices;  // the view scene's, by id
-    const float4* __restrict__ shade;    // the view scene's shading table
-    const float2* __restrict__ offsets;  // band-local
-    const int* __restrict__ ids;         // band-local
+    LightFrame light;
+    ViewBand view;
     unsigned char* __restrict__ mask;
     F4* __restrict__ rgba;  // null: not stored
-    unsigned n;             // triangles of either scene
-    unsigned width;
-    unsigned row_begin;
-    unsigned pixels;        // of the band
-    unsigned stream_end;    // records of a streamed pixel: positions [0, stream_end)
-    int tiles_y;
-    float wf, hf;           // the view frame's
-    float eye[3], base[3], du[3], dv[3], bg[3];
-    float rows[9];          // the light's projection rows (px, py, pz)
-    float light_origin[3];
     float bias, dim;
 };
 
-// Whether a lane of the caller's group holds `mine` (the same value in every lane of the group).
-__device__ __forceinline__ bool ShadowGroupAny(bool mine) {
-    const unsigned long long b = __ballot(mine);
-    if constexpr (kShadowLanes == kWave) {
-        return b != 0ull;
-    } else {
-        const unsigned first = (threadIdx.x & (kWave - 1)) & ~static_cast<unsigned>(kShadowLanes - 1);
-        return ((b >> first) & ((1ull << kShadowLanes) - 1ull)) != 0ull;
-    }
-}
-
 template <bool RC>
 __global__ __launch_bounds__(kShadowThreads) void ShadowKernel(const ShadowParams q) {
-    const TraceParams& p = q.rec;
-    using Recs = TraceRecords<RC>;
     const unsigned lane = threadIdx.x & (kShadowLanes - 1);
     const unsigned pixel = blockIdx.x * kShadowBlock + threadIdx.x / kShadowLanes;
-    if (pixel >= q.pixels) {
+    if (pixel >= q.view.pixels) {
         return;
     }
-    const int code = q.ids[pixel];
-    const float2 o = q.offsets[pixel];
-    const unsigned y = pixel / q.width, x = pixel - y * q.width;
-    const float fx = (static_cast<float>(x) + o.x) / q.wf;
-    const float fy = (static_cast<float>(q.row_begin + y) + o.y) / q.hf;
-    const bool surface = static_cast<unsigned>(code) < q.n;
+    const ViewBand& v = q.view;
+    const ViewPixel px = ViewPixelAt(v, pixel);
     unsigned char cls = kShadowNoSurface;
     ShadowPoint sp{false, 0.f, 0.f, 0.f};
-    if (surface) {
-        const float* at = q.vertices + 9ull * static_cast<unsigned>(code);
-        float v[9], c[9], vol;
-#pragma unroll
-        for (int j = 0; j < 9; ++j) {
-            v[j] = at[j];
-        }
-        ComputeEdges(q.eye, q.base, q.du, q.dv, v, true, c, vol);
-        const float t = ShadowDepth(c, vol, fx, fy);
-        sp = ShadowProject(q.eye, q.base, q.du, q.dv, fx, fy, t, q.light_origin, q.rows, q.bias);
+    if (px.surface) {
+        sp = ShadowProject(v.eye, v.base, v.du, v.dv, px.fx, px.fy, px.t, q.light.origin, q.light.rows, q.bias);
         cls = kShadowOutside;
     }
-    // The shaded pixel, before the scan: the view frame's vectors need not stay live across it.
-    F4 out{q.bg[0], q.bg[1], q.bg[2], -1.f};
-    if (q.rgba != nullptr && surface) {
-        const float4* sr = q.shade + 2ull * static_cast<unsigned>(code);
-        const float4 nr = sr[0], al = sr[1];
-        const ResolveRgb c = ResolveShadeHit(q.base, q.du, q.dv, fx, fy, nr.x, nr.y, nr.z, nr.w, al.x, al.y, al.z);
-        out = F4{c.r, c.g, c.b, static_cast<float>(code)};
-    }
+    const F4 out = ShadedPixel(v, px, q.rgba != nullptr);
     if (sp.inside) {
-        Rays<1> s;
-        s.fx[0] = sp.gx;
-        s.fy[0] = sp.gy;
-        s.bt[0] = __builtin_inff();
-        s.bi[0] = -1;
-        int col = 0, row = 0;
-        bool listed = p.tile_info != nullptr &&
-                      TileOfPosition(sp.gx, sp.gy, p.wf, p.hf, kCullTileCols, kTileRows, p.tiles_x, q.tiles_y, col, row);
-        unsigned cnt = 0u, large = 0u;
-        const unsigned* list = nullptr;
-        if (listed) {
-            const unsigned tile = static_cast<unsigned>(row) * static_cast<unsigned>(p.tiles_x) + static_cast<unsigned>(col);
-            cnt = p.bin_counts[tile];
-            large = p.bin_counts[p.tiles];
-            list = p.bin_lists + static_cast<size_t>(tile) * p.bin_capacity;
-            listed = cnt <= p.bin_capacity && p.tile_info[tile].usable != 0u;
-        }
-        const unsigned total = listed ? cnt + large : q.stream_end;
-        auto entry = [&](unsigned k) {
-            if (!listed) {
-                return k;
-            }
-            const unsigned* at = k < cnt ? list + k : p.large_list + (k - cnt);
-            return *at;
-        };
-        auto test = [&](const typename Recs::Raw& raw) {
-            const CullRecord r = Recs::Make(p, raw);
-            const Record rec{r.a.x, r.a.y, r.a.z, r.a.w, r.b.x, r.b.y, r.b.z, r.b.w, r.x.x};
-            ExactTestAnyOrder<1, false>(s, rec, r.x.y, static_cast<int>(__float_as_uint(r.x.z)));
-        };
-        // The own triangle under the light's records: (t_id, id), or (+inf, -1) if it does not pass.
-        test(Recs::Load(p, q.rank[static_cast<unsigned>(code)]));
-        if (sp.thr <= s.bt[0]) {  // the bound: (thr, below every id) or (t_id, id), whichever is lower
-            s.bt[0] = sp.thr;
-            s.bi[0] = static_cast<int>(0x80000000u);
-        }
-        const int bound_id = s.bi[0];
-        bool occluded = false;
-        for (unsigned base = 0u; base < total; base += kShadowAhead * kShadowLanes) {
-            unsigned pos[kShadowAhead];
-            typename Recs::Raw raw[kShadowAhead];
-#pragma unroll
-            for (int a = 0; a < kShadowAhead; ++a) {
-                pos[a] = entry(min(base + a * kShadowLanes + lane, total - 1u));
-            }
-#pragma unroll
-            for (int a = 0; a < kShadowAhead; ++a) {
-                raw[a] = Recs::Load(p, pos[a]);
-            }
-#pragma unroll
-            for (int a = 0; a < kShadowAhead; ++a) {
-                test(raw[a]);
-            }
-            if (ShadowGroupAny(s.bi[0] != bound_id)) {  // a candidate below the bound: an occluder
-                occluded = true;
-                break;
-            }
-        }
-        cls = occluded ? kShadowShadowed : kShadowLit;
+        cls = OccludedAt<RC, kShadowLanes, kShadowAhead>(q.light, v.n, px.code, sp, lane);
     }
     if (lane == 0u) {
         q.mask[pixel] = cls;
         if (q.rgba != nullptr) {
-            if (surface) {
-                const float k = ShadowScale(cls, q.dim);
-                out = F4{out.x * k, out.y * k, out.z * k, out.w};
-            }
-            StoreNontemporal(q.rgba + pixel, out);
+            StoreDimmed(q.rgba + pixel, out, px.surface, cls, q.dim);
         }
     }
 }
@@ -4158,14 +4227,11 @@ __global__ __launch_bounds__(kShadowThreads) void ShadowKernel(const ShadowParam
 // ---------------------------------------------------------------------------------------
 // Omni-light shadow mask (render.h LaunchOmniShadow; DESIGN.md section 5 "Omni shadow"): ShadowKernel
 // under a point light given as six cube-face frames. The pixel's facts as ShadowKernel computes them
-// (ComputeEdges on the view scene's vertices, the traces' bits), q = surface point - light, the face
-// OmniFace(q) picks, and then ShadowKernel's scan against that face's setup alone: the own
-// triangle's (t_id, id) first, the bound min((thr, below every id), (t_id, id)), the lanes striding
-// the tile's list then the large list (every record of the face where it has no usable list), the
-// group leaving at the end of the first round in which a lane took a candidate.
-// The face is a per-pixel value, so what the scan reads of a face -- OmniFaceParams, 168 B, not a
-// TraceParams -- is read through a per-lane index into the six entries of the argument segment
-// (6 x 168 B + the view's part, 1168 B: under 4 KB, no table, no upload): vector loads from constant
+// (ViewPixelAt), q = surface point - light, the face OmniFace(q) picks, and then OccludedAt in that
+// face's frame alone.
+// The face is a per-pixel value, so what the scan reads of a face -- its LightFrame -- is read
+// through a per-lane index into the six entries of the argument segment
+// (6 x 168 B + the view's part, 1176 B: under 4 KB, no table, no upload): vector loads from constant
 // memory, no scratch. A wave whose pixels agree on the face (most do: faces are large on screen)
 // reads one address. No LDS, no atomics, plain vector stores. Lanes x candidates per round,
 // measured at C3 under a light inside and a light outside the soup with faces of 512, 1024 and 2048
@@ -4186,198 +4252,39 @@ constexpr int kOmniAhead = SRT_OMNI_AHEAD;  // candidates per lane and round
 constexpr int kOmniThreads = 256;
 constexpr int kOmniBlock = kOmniThreads / kOmniLanes;  // pixels per block
 static_assert(kOmniLanes >= 2 && kWave % kOmniLanes == 0, "a pixel's lanes share a wave");
-struct OmniFaceParams {
-    const CullRecord* cull;        // stored records by position (RC = false)
-    const float* svertices;        // vertices by position (RC = true)
-    const unsigned* rank;          // the face scene's record id -> position
-    const TileInfo* tile_info;     // null: no setup, every pixel of the face streams
-    const unsigned* bin_lists;
-    const unsigned* bin_counts;
-    const unsigned* large_list;
-    unsigned bin_capacity;
-    unsigned tiles;
-    int tiles_x, tiles_y;
-    unsigned stream_end;           // records of a streamed pixel: positions [0, stream_end)
-    float wf, hf;                  // the face frame's
-    float base[3], du[3], dv[3];
-    float rows[9];                 // the face's projection rows (px, py, pz)
-    float origin[3];
-};
 struct OmniParams {
-    OmniFaceParams face[kOmniFaces];
-    const float* __restrict__ vertices;  // the view scene's, by id
-    const float4* __restrict__ shade;    // the view scene's shading table
-    const float2* __restrict__ offsets;  // band-local
-    const int* __restrict__ ids;         // band-local
+    LightFrame face[kOmniFaces];
+    ViewBand view;
     unsigned char* __restrict__ mask;
     unsigned char* __restrict__ face_out;  // null: not stored
     F4* __restrict__ rgba;                 // null: not stored
-    unsigned n;  // triangles of every scene
-    unsigned width;
-    unsigned row_begin;
-    unsigned pixels;  // of the band
-    float wf, hf;     // the view frame's
-    float eye[3], base[3], du[3], dv[3], bg[3];
     float light[3];
     float bias, dim;
 };
-static_assert(sizeof(OmniFaceParams) == 168 && sizeof(OmniParams) == 1168, "the faces travel in the kernel-argument segment (< 4 KB)");
-
-__device__ __forceinline__ bool OmniGroupAny(bool mine) {
-    const unsigned long long b = __ballot(mine);
-    if constexpr (kOmniLanes == kWave) {
-        return b != 0ull;
-    } else {
-        const unsigned first = (threadIdx.x & (kWave - 1)) & ~static_cast<unsigned>(kOmniLanes - 1);
-        return ((b >> first) & ((1ull << kOmniLanes) - 1ull)) != 0ull;
-    }
-}
-
-// A face's candidate record by position, as TraceRecords<RC> gives a trace its own (the screen box,
-// which the exact test does not read, left out).
-template <bool RC>
-struct OmniRecords {
-    struct Raw {
-        float4 a, b, x;
-    };
-    static __device__ __forceinline__ Raw Load(const OmniFaceParams& f, unsigned, unsigned pos) {
-        const float4* at = reinterpret_cast<const float4*>(f.cull + pos);
-        return Raw{at[0], at[1], at[2]};
-    }
-    static __device__ __forceinline__ Raw Make(const OmniFaceParams&, unsigned, const Raw& r) { return r; }
-};
-template <>
-struct OmniRecords<true> {
-    struct Raw {
-        float v[9];
-        unsigned id;
-    };
-    using Made = OmniRecords<false>::Raw;
-    static __device__ __forceinline__ Raw Load(const OmniFaceParams& f, unsigned n, unsigned pos) {
-        Raw r;
-        const bool real = pos < n;
-        const float4* v = reinterpret_cast<const float4*>(f.svertices + static_cast<size_t>(kSpatialStride) * (real ? pos : 0u));
-        const float4 v0 = v[0], v1 = v[1], v2 = v[2];
-        r.v[0] = v0.x, r.v[1] = v0.y, r.v[2] = v0.z, r.v[3] = v0.w;
-        r.v[4] = v1.x, r.v[5] = v1.y, r.v[6] = v1.z, r.v[7] = v1.w;
-        r.v[8] = v2.x;
-        r.id = real ? __float_as_uint(v2.y) : pos;
-        return r;
-    }
-    static __device__ __forceinline__ Made Make(const OmniFaceParams& f, unsigned n, const Raw& r) {
-        float c[9], vol;
-        ComputeEdges(f.origin, f.base, f.du, f.dv, r.v, r.id < n, c, vol);
-        return Made{make_float4(c[0], c[1], c[2], c[3]), make_float4(c[4], c[5], c[6], c[7]),
-                    make_float4(c[8], vol, __uint_as_float(r.id), 0.f)};
-    }
-};
+static_assert(sizeof(OmniParams) == 1176, "the faces travel in the kernel-argument segment (< 4 KB)");
 
 template <bool RC>
 __global__ __launch_bounds__(kOmniThreads) void OmniShadowKernel(const OmniParams q) {
-    using Recs = OmniRecords<RC>;
     const unsigned lane = threadIdx.x & (kOmniLanes - 1);
     const unsigned pixel = blockIdx.x * kOmniBlock + threadIdx.x / kOmniLanes;
-    if (pixel >= q.pixels) {
+    if (pixel >= q.view.pixels) {
         return;
     }
-    const int code = q.ids[pixel];
-    const float2 o = q.offsets[pixel];
-    const unsigned y = pixel / q.width, x = pixel - y * q.width;
-    const float fx = (static_cast<float>(x) + o.x) / q.wf;
-    const float fy = (static_cast<float>(q.row_begin + y) + o.y) / q.hf;
-    const bool surface = static_cast<unsigned>(code) < q.n;
+    const ViewBand& v = q.view;
+    const ViewPixel px = ViewPixelAt(v, pixel);
     unsigned char cls = kShadowNoSurface;
     unsigned char face = kOmniNoFace;
     ShadowPoint sp{false, 0.f, 0.f, 0.f};
-    if (surface) {
-        const float* at = q.vertices + 9ull * static_cast<unsigned>(code);
-        float v[9], c[9], vol;
-#pragma unroll
-        for (int j = 0; j < 9; ++j) {
-            v[j] = at[j];
-        }
-        ComputeEdges(q.eye, q.base, q.du, q.dv, v, true, c, vol);
-        const float t = ShadowDepth(c, vol, fx, fy);
+    if (px.surface) {
         float off[3];
-        ShadowOffset(q.eye, q.base, q.du, q.dv, fx, fy, t, q.light, off);
+        ShadowOffset(v.eye, v.base, v.du, v.dv, px.fx, px.fy, px.t, q.light, off);
         face = static_cast<unsigned char>(OmniFace(off));
         sp = ShadowProjectOffset(off, q.face[face].rows, q.bias);
         cls = kShadowOutside;
     }
-    // The shaded pixel, before the scan: the view frame's vectors need not stay live across it.
-    F4 out{q.bg[0], q.bg[1], q.bg[2], -1.f};
-    if (q.rgba != nullptr && surface) {
-        const float4* sr = q.shade + 2ull * static_cast<unsigned>(code);
-        const float4 nr = sr[0], al = sr[1];
-        const ResolveRgb c = ResolveShadeHit(q.base, q.du, q.dv, fx, fy, nr.x, nr.y, nr.z, nr.w, al.x, al.y, al.z);
-        out = F4{c.r, c.g, c.b, static_cast<float>(code)};
-    }
+    const F4 out = ShadedPixel(v, px, q.rgba != nullptr);
     if (sp.inside) {
-        const OmniFaceParams& f = q.face[face];
-        Rays<1> s;
-        s.fx[0] = sp.gx;
-        s.fy[0] = sp.gy;
-        s.bt[0] = __builtin_inff();
-        s.bi[0] = -1;
-        int col = 0, row = 0;
-        const TileInfo* tile_info = f.tile_info;
-        bool listed = tile_info != nullptr &&
-                      TileOfPosition(sp.gx, sp.gy, f.wf, f.hf, kCullTileCols, kTileRows, f.tiles_x, f.tiles_y, col, row);
-        unsigned cnt = 0u, large = 0u, capacity = 0u;
-        const unsigned* list = nullptr;
-        const unsigned* large_list = nullptr;
-        if (listed) {
-            const unsigned tile = static_cast<unsigned>(row) * static_cast<unsigned>(f.tiles_x) + static_cast<unsigned>(col);
-            const unsigned* counts = f.bin_counts;
-            capacity = f.bin_capacity;
-            cnt = counts[tile];
-            large = counts[f.tiles];
-            list = f.bin_lists + static_cast<size_t>(tile) * capacity;
-            large_list = f.large_list;
-            listed = cnt <= capacity && tile_info[tile].usable != 0u;
-        }
-        const unsigned total = listed ? cnt + large : f.stream_end;
-        auto entry = [&](unsigned k) {
-            if (!listed) {
-                return k;
-            }
-            const unsigned* at = k < cnt ? list + k : large_list + (k - cnt);
-            return *at;
-        };
-        auto test = [&](const typename Recs::Raw& raw) {
-            const auto r = Recs::Make(f, q.n, raw);
-            const Record rec{r.a.x, r.a.y, r.a.z, r.a.w, r.b.x, r.b.y, r.b.z, r.b.w, r.x.x};
-            ExactTestAnyOrder<1, false>(s, rec, r.x.y, static_cast<int>(__float_as_uint(r.x.z)));
-        };
-        // The own triangle under the face's records: (t_id, id), or (+inf, -1) if it does not pass.
-        test(Recs::Load(f, q.n, f.rank[static_cast<unsigned>(code)]));
-        if (sp.thr <= s.bt[0]) {  // the bound: (thr, below every id) or (t_id, id), whichever is lower
-            s.bt[0] = sp.thr;
-            s.bi[0] = static_cast<int>(0x80000000u);
-        }
-        const int bound_id = s.bi[0];
-        bool occluded = false;
-        for (unsigned base = 0u; base < total; base += kOmniAhead * kOmniLanes) {
-            unsigned pos[kOmniAhead];
-            typename Recs::Raw raw[kOmniAhead];
-#pragma unroll
-            for (int a = 0; a < kOmniAhead; ++a) {
-                pos[a] = entry(min(base + a * kOmniLanes + lane, total - 1u));
-            }
-#pragma unroll
-            for (int a = 0; a < kOmniAhead; ++a) {
-                raw[a] = Recs::Load(f, q.n, pos[a]);
-            }
-#pragma unroll
-            for (int a = 0; a < kOmniAhead; ++a) {
-                test(raw[a]);
-            }
-            if (OmniGroupAny(s.bi[0] != bound_id)) {  // a candidate below the bound: an occluder
-                occluded = true;
-                break;
-            }
-        }
-        cls = occluded ? kShadowShadowed : kShadowLit;
+        cls = OccludedAt<RC, kOmniLanes, kOmniAhead>(q.face[face], v.n, px.code, sp, lane);
     }
     if (lane == 0u) {
         q.mask[pixel] = cls;
@@ -4385,11 +4292,7 @@ __global__ __launch_bounds__(kOmniThreads) void OmniShadowKernel(const OmniParam
             q.face_out[pixel] = face;
         }
         if (q.rgba != nullptr) {
-            if (surface) {
-                const float k = ShadowScale(cls, q.dim);
-                out = F4{out.x * k, out.y * k, out.z * k, out.w};
-            }
-            StoreNontemporal(q.rgba + pixel, out);
+            StoreDimmed(q.rgba + pixel, out, px.surface, cls, q.dim);
         }
     }
 }
@@ -4397,17 +4300,14 @@ __global__ __launch_bounds__(kOmniThreads) void OmniShadowKernel(const OmniParam
 // ---------------------------------------------------------------------------------------
 // Direct lighting (render.h LaunchLighting; lighting_math.h; DESIGN.md section 5 "Lighting"): the lit
 // pixel of a band under up to kLightingMaxLights spot and point lights, one launch. The pixel's
-// facts are computed once, as OmniShadowKernel computes them (ComputeEdges on the view scene's
-// vertices, the traces' bits: t, d, the surface point P) together with the shading-table row (N,
-// albedo: one 32-B line); every light then adds q = P - its origin, its frame -- frame `first` of a
-// spot light, first + OmniFace(q) of a point light -- ShadowProjectOffset in that frame (the frustum
-// test decides for a spot light and never fires for a selected cube face) and OmniShadowKernel's scan
-// there: the own triangle's (t_id, id) first, the bound min((thr, below every id), (t_id, id)), the
-// lanes striding the tile's list then the large list (every record where the frame has no usable
-// list), the group leaving at the end of the first round in which a lane took a candidate. A light
-// that reaches the pixel from the eye's side of the triangle adds color . w to E (lighting_math.h);
-// E stays in three registers across the lights.
-// The light frames (up to 16 OmniFaceParams, 168 B each) and the per-light table travel by value in
+// facts are computed once, as OmniShadowKernel computes them (ViewPixelAt: t; then d, the surface
+// point P) together with the shading-table row (N, albedo: one 32-B line); every light then adds
+// q = P - its origin, its frame -- frame `first` of a spot light, first + OmniFace(q) of a point
+// light -- ShadowProjectOffset in that frame (the frustum test decides for a spot light and never
+// fires for a selected cube face) and OccludedAt there. A light that reaches the pixel from the
+// eye's side of the triangle adds color . w to E (lighting_math.h); E stays in three registers
+// across the lights.
+// The light frames (up to 16 LightFrame, 168 B each) and the per-light table travel by value in
 // the kernel-argument segment: the light index is uniform (scalar loads), the frame index per lane
 // (vector loads from constant memory, OmniShadowKernel's pattern). No device table, no upload, no
 // LDS, no atomics, no scratch. Without class planes a light that is not facing is not scanned: it
@@ -4433,64 +4333,35 @@ struct LightingLightParams {
     unsigned point;  // 1: six frames, selected by OmniFace(q); 0: one
 };
 struct LightingParams {
-    OmniFaceParams frame[kLightingMaxFrames];
+    LightFrame frame[kLightingMaxFrames];
     LightingLightParams light[kLightingMaxLights];
-    const float* __restrict__ vertices;  // the view scene's, by id
-    const float4* __restrict__ shade;    // the view scene's shading table
-    const float2* __restrict__ offsets;  // band-local
-    const int* __restrict__ ids;         // band-local
+    ViewBand view;
     F4* __restrict__ rgba;
     unsigned char* __restrict__ classes;  // null: not stored; else count planes of `pixels` bytes
-    unsigned n;  // triangles of every scene
-    unsigned width;
-    unsigned row_begin;
-    unsigned pixels;  // of the band
-    unsigned count;   // lights
-    float wf, hf;     // the view frame's
-    float eye[3], base[3], du[3], dv[3], bg[3], ambient[3];
+    unsigned count;                       // lights
+    float ambient[3];
 };
 static_assert(sizeof(LightingLightParams) == 40 && sizeof(LightingParams) == 3160 && sizeof(LightingParams) < 4096,
               "the light frames and the light table travel in the kernel-argument segment (< 4 KB)");
 
-__device__ __forceinline__ bool LightingGroupAny(bool mine) {
-    const unsigned long long b = __ballot(mine);
-    if constexpr (kLightingLanes == kWave) {
-        return b != 0ull;
-    } else {
-        const unsigned first = (threadIdx.x & (kWave - 1)) & ~static_cast<unsigned>(kLightingLanes - 1);
-        return ((b >> first) & ((1ull << kLightingLanes) - 1ull)) != 0ull;
-    }
-}
-
 template <bool RC>
 __global__ __launch_bounds__(kLightingThreads) void LightingKernel(const LightingParams q) {
-    using Recs = OmniRecords<RC>;
     const unsigned lane = threadIdx.x & (kLightingLanes - 1);
     const unsigned pixel = blockIdx.x * kLightingBlock + threadIdx.x / kLightingLanes;
-    if (pixel >= q.pixels) {
+    if (pixel >= q.view.pixels) {
         return;
     }
-    const int code = q.ids[pixel];
-    const float2 o = q.offsets[pixel];
-    const unsigned y = pixel / q.width, x = pixel - y * q.width;
-    const float fx = (static_cast<float>(x) + o.x) / q.wf;
-    const float fy = (static_cast<float>(q.row_begin + y) + o.y) / q.hf;
-    const bool surface = static_cast<unsigned>(code) < q.n;
+    const ViewBand& v = q.view;
+    const ViewPixel px = ViewPixelAt(v, pixel);
+    const bool surface = px.surface;
+    const int code = px.code;
     // The pixel's facts, once for all lights.
     float P[3] = {0.f, 0.f, 0.f}, N[3] = {0.f, 0.f, 0.f}, al[3] = {0.f, 0.f, 0.f};
     float nn = 0.f, nd = 0.f;
     if (surface) {
-        const float* at = q.vertices + 9ull * static_cast<unsigned>(code);
-        float v[9], c[9], vol;
-#pragma unroll
-        for (int j = 0; j < 9; ++j) {
-            v[j] = at[j];
-        }
-        ComputeEdges(q.eye, q.base, q.du, q.dv, v, true, c, vol);
-        const float t = ShadowDepth(c, vol, fx, fy);
         float d[3];
-        LightingPoint(q.eye, q.base, q.du, q.dv, fx, fy, t, d, P);
-        const float4* sr = q.shade + 2ull * static_cast<unsigned>(code);
+        LightingPoint(v.eye, v.base, v.du, v.dv, px.fx, px.fy, px.t, d, P);
+        const float4* sr = v.shade + 2ull * static_cast<unsigned>(code);
         const float4 nr = sr[0], ar = sr[1];
         N[0] = nr.x, N[1] = nr.y, N[2] = nr.z;
         al[0] = ar.x, al[1] = ar.y, al[2] = ar.z;
@@ -4512,74 +4383,10 @@ __global__ __launch_bounds__(kLightingThreads) void LightingKernel(const Lightin
             cls = kShadowOutside;
             if (facing || q.classes != nullptr) {  // (a light that is not facing adds nothing)
                 const unsigned fi = lt.first + (lt.point != 0u ? static_cast<unsigned>(OmniFace(off)) : 0u);
-                const OmniFaceParams& f = q.frame[fi];
+                const LightFrame& f = q.frame[fi];
                 const ShadowPoint sp = ShadowProjectOffset(off, f.rows, lt.bias);
                 if (sp.inside) {
-                    Rays<1> s;
-                    s.fx[0] = sp.gx;
-                    s.fy[0] = sp.gy;
-                    s.bt[0] = __builtin_inff();
-                    s.bi[0] = -1;
-                    int col = 0, row = 0;
-                    const TileInfo* tile_info = f.tile_info;
-                    bool listed = tile_info != nullptr && TileOfPosition(sp.gx, sp.gy, f.wf, f.hf, kCullTileCols, kTileRows,
-                                                                         f.tiles_x, f.tiles_y, col, row);
-                    unsigned cnt = 0u, large = 0u, capacity = 0u;
-                    const unsigned* list = nullptr;
-                    const unsigned* large_list = nullptr;
-                    if (listed) {
-                        const unsigned tile =
-                            static_cast<unsigned>(row) * static_cast<unsigned>(f.tiles_x) + static_cast<unsigned>(col);
-                        const unsigned* counts = f.bin_counts;
-                        capacity = f.bin_capacity;
-                        cnt = counts[tile];
-                        large = counts[f.tiles];
-                        list = f.bin_lists + static_cast<size_t>(tile) * capacity;
-                        large_list = f.large_list;
-                        listed = cnt <= capacity && tile_info[tile].usable != 0u;
-                    }
-                    const unsigned total = listed ? cnt + large : f.stream_end;
-                    auto entry = [&](unsigned k) {
-                        if (!listed) {
-                            return k;
-                        }
-                        const unsigned* at = k < cnt ? list + k : large_list + (k - cnt);
-                        return *at;
-                    };
-                    auto test = [&](const typename Recs::Raw& raw) {
-                        const auto r = Recs::Make(f, q.n, raw);
-                        const Record rec{r.a.x, r.a.y, r.a.z, r.a.w, r.b.x, r.b.y, r.b.z, r.b.w, r.x.x};
-                        ExactTestAnyOrder<1, false>(s, rec, r.x.y, static_cast<int>(__float_as_uint(r.x.z)));
-                    };
-                    // The own triangle under the frame's records: (t_id, id), or (+inf, -1) if it does not pass.
-                    test(Recs::Load(f, q.n, f.rank[static_cast<unsigned>(code)]));
-                    if (sp.thr <= s.bt[0]) {  // the bound: (thr, below every id) or (t_id, id), whichever is lower
-                        s.bt[0] = sp.thr;
-                        s.bi[0] = static_cast<int>(0x80000000u);
-                    }
-                    const int bound_id = s.bi[0];
-                    bool occluded = false;
-                    for (unsigned base = 0u; base < total; base += kLightingAhead * kLightingLanes) {
-                        unsigned pos[kLightingAhead];
-                        typename Recs::Raw raw[kLightingAhead];
-#pragma unroll
-                        for (int a = 0; a < kLightingAhead; ++a) {
-                            pos[a] = entry(min(base + a * kLightingLanes + lane, total - 1u));
-                        }
-#pragma unroll
-                        for (int a = 0; a < kLightingAhead; ++a) {
-                            raw[a] = Recs::Load(f, q.n, pos[a]);
-                        }
-#pragma unroll
-                        for (int a = 0; a < kLightingAhead; ++a) {
-                            test(raw[a]);
-                        }
-                        if (LightingGroupAny(s.bi[0] != bound_id)) {  // a candidate below the bound: an occluder
-                            occluded = true;
-                            break;
-                        }
-                    }
-                    cls = occluded ? kShadowShadowed : kShadowLit;
+                    cls = OccludedAt<RC, kLightingLanes, kLightingAhead>(f, v.n, code, sp, lane);
                 }
             }
             if (cls == kShadowLit && facing) {
@@ -4590,11 +4397,11 @@ __global__ __launch_bounds__(kLightingThreads) void LightingKernel(const Lightin
             }
         }
         if (lane == 0u && q.classes != nullptr) {
-            q.classes[static_cast<size_t>(l) * q.pixels + pixel] = cls;
+            q.classes[static_cast<size_t>(l) * v.pixels + pixel] = cls;
         }
     }
     if (lane == 0u) {
-        F4 out{q.bg[0], q.bg[1], q.bg[2], -1.f};
+        F4 out{v.bg[0], v.bg[1], v.bg[2], -1.f};
         if (surface) {
             out = F4{al[0] * e0, al[1] * e1, al[2] * e2, static_cast<float>(code)};
         }
@@ -5840,6 +5647,14 @@ hipError_t LaunchSharedCullFrames(const CullFrame* frames, std::size_t count, co
     return hipGetLastError();
 }
 
+// One record source per launch: the kernel's template argument.
+template <class P>
+static hipError_t LaunchBySource(bool recompute, void (*recomputed)(P), void (*stored)(P), dim3 grid, int threads,
+                                 hipStream_t stream, const P& q) {
+    hipLaunchKernelGGL(recompute ? recomputed : stored, grid, dim3(threads), 0, stream, q);
+    return hipGetLastError();
+}
+
 // The records a point query (or a shadow test) reads, as TraceParams: the setup's, or -- setup ==
 // null -- the scene's spatial inputs for TraceRecords<true>. Returns whether the records are
 // recomputed (the kernel's RC).
@@ -5900,12 +5715,7 @@ hipError_t LaunchQuery(const CullSetup* setup, std::uint64_t n, const Frame& fra
     q.count = static_cast<unsigned>(args.count);
     q.stream_end = n == 0 ? 0u : p.n_pad;  // (an empty scene: every query misses)
     const dim3 grid(static_cast<unsigned>((args.count + kQueryBlock - 1) / kQueryBlock));
-    if (recompute) {
-        hipLaunchKernelGGL(QueryKernel<true>, grid, dim3(kQueryThreads), 0, stream, q);
-    } else {
-        hipLaunchKernelGGL(QueryKernel<false>, grid, dim3(kQueryThreads), 0, stream, q);
-    }
-    return hipGetLastError();
+    return LaunchBySource(recompute, QueryKernel<true>, QueryKernel<false>, grid, kQueryThreads, stream, q);
 }
 
 hipError_t LaunchLayers(const CullSetup* setup, std::uint64_t n, const Frame& frame, std::size_t width,
@@ -6008,58 +5818,102 @@ hipError_t LaunchComposite(const float* d_shade, std::uint64_t n, const Frame& f
     return hipGetLastError();
 }
 
+// The view's part of a shadow launch (ShadowArgs, LightingArgs: the same band fields), `block`
+// pixels per block. False: a band or a buffer the launchers refuse.
+template <class Args>
+static bool FillViewBand(ViewBand& v, const float* d_vertices, const float* d_shade, std::uint64_t n, const Frame& frame,
+                         const float background[3], const Args& args, int block) {
+    if (args.offsets == nullptr || args.ids == nullptr || d_shade == nullptr || (n != 0 && d_vertices == nullptr) ||
+        n > 0x7FFFFFFFull || args.height == 0 || args.height > 0x7FFFFFFFull || args.row_begin > args.height ||
+        args.row_count > args.height - args.row_begin || args.width > 0xFFFFFFFFull ||
+        args.row_count > (0xFFFFFFFFull - static_cast<unsigned>(block)) / args.width) {
+        return false;
+    }
+    v.vertices = d_vertices;
+    v.shade = reinterpret_cast<const float4*>(d_shade);
+    v.offsets = reinterpret_cast<const float2*>(args.offsets);
+    v.ids = args.ids;
+    v.n = static_cast<unsigned>(n);
+    v.width = static_cast<unsigned>(args.width);
+    v.row_begin = static_cast<unsigned>(args.row_begin);
+    v.pixels = static_cast<unsigned>(args.width * args.row_count);
+    v.wf = static_cast<float>(args.width);
+    v.hf = static_cast<float>(args.height);
+    for (int k = 0; k < 3; ++k) {
+        v.eye[k] = frame.origin[k];
+        v.base[k] = frame.base[k];
+        v.du[k] = frame.du[k];
+        v.dv[k] = frame.dv[k];
+        v.bg[k] = background[k];
+    }
+    return true;
+}
+static dim3 ViewBandGrid(const ViewBand& v, int block) {
+    return dim3(static_cast<unsigned>((static_cast<std::size_t>(v.pixels) + block - 1) / block));
+}
+
+// A light frame of n triangles from its scene's ShadowLight. False: one the launchers refuse; else
+// `recompute` is its record source (QueryRecords).
+static bool FillLightFrame(LightFrame& f, const ShadowLight& l, std::uint64_t n, bool& recompute) {
+    if ((n != 0 && l.rank == nullptr) || l.svertices == nullptr || l.edges == nullptr ||
+        (l.setup != nullptr && (l.width == 0 || l.height == 0 || !CullBinnable(l.width, l.height) ||
+                                l.setup->tiles != CullTiles(l.width, l.height)))) {
+        return false;
+    }
+    TraceParams p{};
+    int tiles_y = 0;
+    recompute = QueryRecords(p, tiles_y, l.setup, n, l.frame, l.width, l.height, l.svertices, l.edges);
+    f.cull = p.cull;
+    f.svertices = p.svertices;
+    f.rank = l.rank;
+    f.tile_info = p.tile_info;
+    f.bin_lists = p.bin_lists;
+    f.bin_counts = p.bin_counts;
+    f.large_list = p.large_list;
+    f.bin_capacity = p.bin_capacity;
+    f.tiles = p.tiles;
+    f.tiles_x = p.tiles_x;
+    f.tiles_y = tiles_y;
+    f.stream_end = n == 0 ? 0u : p.n_pad;
+    f.wf = p.wf;
+    f.hf = p.hf;
+    for (int c = 0; c < 3; ++c) {
+        f.base[c] = l.frame.base[c];
+        f.du[c] = l.frame.du[c];
+        f.dv[c] = l.frame.dv[c];
+        f.origin[c] = l.frame.origin[c];
+    }
+    ShadowProjectionRows(l.frame.base, l.frame.du, l.frame.dv, f.rows);
+    return true;
+}
+
+// The frames of one light after its first: the first's size and origin.
+static bool SameLight(const ShadowLight& l, const ShadowLight& first) {
+    return l.width == first.width && l.height == first.height &&
+           std::memcmp(l.frame.origin, first.frame.origin, sizeof l.frame.origin) == 0;
+}
+
+static bool BiasAndDimValid(float bias, float dim) { return bias >= 0.f && std::isfinite(bias) && std::isfinite(dim); }
+
 hipError_t LaunchShadow(const float* d_vertices, const float* d_shade, std::uint64_t n, const Frame& frame,
                         const float background[3], const ShadowLight& light, const ShadowArgs& args,
                         hipStream_t stream) {
     if (args.width == 0 || args.row_count == 0) {
         return hipSuccess;
     }
-    const std::size_t pixels = args.width * args.row_count;
-    if (args.offsets == nullptr || args.ids == nullptr || args.mask == nullptr || d_shade == nullptr ||
-        (n != 0 && (d_vertices == nullptr || light.rank == nullptr)) || light.svertices == nullptr ||
-        light.edges == nullptr || n > 0x7FFFFFFFull || args.height == 0 || args.height > 0x7FFFFFFFull ||
-        args.row_begin > args.height || args.row_count > args.height - args.row_begin ||
-        args.width > 0xFFFFFFFFull || args.row_count > (0xFFFFFFFFull - kShadowBlock) / args.width ||
-        !(args.bias >= 0.f) || !std::isfinite(args.bias) || !std::isfinite(args.dim) ||
-        (light.setup != nullptr && (light.width == 0 || light.height == 0 || !CullBinnable(light.width, light.height) ||
-                                    light.setup->tiles != CullTiles(light.width, light.height)))) {
+    ShadowParams q{};
+    bool recompute = false;
+    if (args.mask == nullptr || !BiasAndDimValid(args.bias, args.dim) ||
+        !FillViewBand(q.view, d_vertices, d_shade, n, frame, background, args, kShadowBlock) ||
+        !FillLightFrame(q.light, light, n, recompute)) {
         return hipErrorInvalidValue;
     }
-    ShadowParams q{};
-    const bool recompute = QueryRecords(q.rec, q.tiles_y, light.setup, n, light.frame, light.width, light.height,
-                                        light.svertices, light.edges);
-    q.rank = light.rank;
-    q.vertices = d_vertices;
-    q.shade = reinterpret_cast<const float4*>(d_shade);
-    q.offsets = reinterpret_cast<const float2*>(args.offsets);
-    q.ids = args.ids;
     q.mask = args.mask;
     q.rgba = reinterpret_cast<F4*>(args.rgba);
-    q.n = static_cast<unsigned>(n);
-    q.width = static_cast<unsigned>(args.width);
-    q.row_begin = static_cast<unsigned>(args.row_begin);
-    q.pixels = static_cast<unsigned>(pixels);
-    q.stream_end = n == 0 ? 0u : q.rec.n_pad;
-    q.wf = static_cast<float>(args.width);
-    q.hf = static_cast<float>(args.height);
-    for (int k = 0; k < 3; ++k) {
-        q.eye[k] = frame.origin[k];
-        q.base[k] = frame.base[k];
-        q.du[k] = frame.du[k];
-        q.dv[k] = frame.dv[k];
-        q.bg[k] = background[k];
-        q.light_origin[k] = light.frame.origin[k];
-    }
-    ShadowProjectionRows(light.frame.base, light.frame.du, light.frame.dv, q.rows);
     q.bias = args.bias;
     q.dim = args.dim;
-    const dim3 grid(static_cast<unsigned>((pixels + kShadowBlock - 1) / kShadowBlock));
-    if (recompute) {
-        hipLaunchKernelGGL(ShadowKernel<true>, grid, dim3(kShadowThreads), 0, stream, q);
-    } else {
-        hipLaunchKernelGGL(ShadowKernel<false>, grid, dim3(kShadowThreads), 0, stream, q);
-    }
-    return hipGetLastError();
+    return LaunchBySource(recompute, ShadowKernel<true>, ShadowKernel<false>, ViewBandGrid(q.view, kShadowBlock),
+                          kShadowThreads, stream, q);
 }
 
 hipError_t LaunchOmniShadow(const float* d_vertices, const float* d_shade, std::uint64_t n, const Frame& frame,
@@ -6068,85 +5922,30 @@ hipError_t LaunchOmniShadow(const float* d_vertices, const float* d_shade, std::
     if (args.width == 0 || args.row_count == 0) {
         return hipSuccess;
     }
-    const std::size_t pixels = args.width * args.row_count;
-    if (args.offsets == nullptr || args.ids == nullptr || args.mask == nullptr || d_shade == nullptr ||
-        (n != 0 && d_vertices == nullptr) || n > 0x7FFFFFFFull || args.height == 0 || args.height > 0x7FFFFFFFull ||
-        args.row_begin > args.height || args.row_count > args.height - args.row_begin ||
-        args.width > 0xFFFFFFFFull || args.row_count > (0xFFFFFFFFull - kOmniBlock) / args.width ||
-        !(args.bias >= 0.f) || !std::isfinite(args.bias) || !std::isfinite(args.dim)) {
+    OmniParams q{};
+    if (args.mask == nullptr || !BiasAndDimValid(args.bias, args.dim) ||
+        !FillViewBand(q.view, d_vertices, d_shade, n, frame, background, args, kOmniBlock)) {
         return hipErrorInvalidValue;
     }
-    OmniParams q{};
     bool recompute = false;
     for (int k = 0; k < kOmniFaces; ++k) {
-        const ShadowLight& l = faces[k];
-        if ((n != 0 && l.rank == nullptr) || l.svertices == nullptr || l.edges == nullptr ||
-            l.width != faces[0].width || l.height != faces[0].height || (l.setup == nullptr) != (faces[0].setup == nullptr) ||
-            std::memcmp(l.frame.origin, faces[0].frame.origin, sizeof l.frame.origin) != 0 ||
-            (l.setup != nullptr && (l.width == 0 || l.height == 0 || !CullBinnable(l.width, l.height) ||
-                                    l.setup->tiles != CullTiles(l.width, l.height)))) {
-            return hipErrorInvalidValue;
-        }
-        TraceParams p{};
-        int tiles_y = 0;
-        const bool rc = QueryRecords(p, tiles_y, l.setup, n, l.frame, l.width, l.height, l.svertices, l.edges);
-        if (k != 0 && rc != recompute) {
+        bool rc = false;
+        if (!SameLight(faces[k], faces[0]) || (faces[k].setup == nullptr) != (faces[0].setup == nullptr) ||
+            !FillLightFrame(q.face[k], faces[k], n, rc) || (k != 0 && rc != recompute)) {
             return hipErrorInvalidValue;
         }
         recompute = rc;
-        OmniFaceParams& f = q.face[k];
-        f.cull = p.cull;
-        f.svertices = p.svertices;
-        f.rank = l.rank;
-        f.tile_info = p.tile_info;
-        f.bin_lists = p.bin_lists;
-        f.bin_counts = p.bin_counts;
-        f.large_list = p.large_list;
-        f.bin_capacity = p.bin_capacity;
-        f.tiles = p.tiles;
-        f.tiles_x = p.tiles_x;
-        f.tiles_y = tiles_y;
-        f.stream_end = n == 0 ? 0u : p.n_pad;
-        f.wf = p.wf;
-        f.hf = p.hf;
-        for (int c = 0; c < 3; ++c) {
-            f.base[c] = l.frame.base[c];
-            f.du[c] = l.frame.du[c];
-            f.dv[c] = l.frame.dv[c];
-            f.origin[c] = l.frame.origin[c];
-        }
-        ShadowProjectionRows(l.frame.base, l.frame.du, l.frame.dv, f.rows);
     }
-    q.vertices = d_vertices;
-    q.shade = reinterpret_cast<const float4*>(d_shade);
-    q.offsets = reinterpret_cast<const float2*>(args.offsets);
-    q.ids = args.ids;
     q.mask = args.mask;
     q.face_out = d_face;
     q.rgba = reinterpret_cast<F4*>(args.rgba);
-    q.n = static_cast<unsigned>(n);
-    q.width = static_cast<unsigned>(args.width);
-    q.row_begin = static_cast<unsigned>(args.row_begin);
-    q.pixels = static_cast<unsigned>(pixels);
-    q.wf = static_cast<float>(args.width);
-    q.hf = static_cast<float>(args.height);
     for (int k = 0; k < 3; ++k) {
-        q.eye[k] = frame.origin[k];
-        q.base[k] = frame.base[k];
-        q.du[k] = frame.du[k];
-        q.dv[k] = frame.dv[k];
-        q.bg[k] = background[k];
         q.light[k] = faces[0].frame.origin[k];
     }
     q.bias = args.bias;
     q.dim = args.dim;
-    const dim3 grid(static_cast<unsigned>((pixels + kOmniBlock - 1) / kOmniBlock));
-    if (recompute) {
-        hipLaunchKernelGGL(OmniShadowKernel<true>, grid, dim3(kOmniThreads), 0, stream, q);
-    } else {
-        hipLaunchKernelGGL(OmniShadowKernel<false>, grid, dim3(kOmniThreads), 0, stream, q);
-    }
-    return hipGetLastError();
+    return LaunchBySource(recompute, OmniShadowKernel<true>, OmniShadowKernel<false>, ViewBandGrid(q.view, kOmniBlock),
+                          kOmniThreads, stream, q);
 }
 
 hipError_t LaunchLighting(const float* d_vertices, const float* d_shade, std::uint64_t n, const Frame& frame,
@@ -6155,15 +5954,11 @@ hipError_t LaunchLighting(const float* d_vertices, const float* d_shade, std::ui
     if (args.width == 0 || args.row_count == 0) {
         return hipSuccess;
     }
-    const std::size_t pixels = args.width * args.row_count;
-    if (args.offsets == nullptr || args.ids == nullptr || args.rgba == nullptr || d_shade == nullptr ||
-        (n != 0 && d_vertices == nullptr) || n > 0x7FFFFFFFull || args.height == 0 || args.height > 0x7FFFFFFFull ||
-        args.row_begin > args.height || args.row_count > args.height - args.row_begin ||
-        args.width > 0xFFFFFFFFull || args.row_count > (0xFFFFFFFFull - kLightingBlock) / args.width ||
-        count > static_cast<std::size_t>(kLightingMaxLights) || (count != 0 && lights == nullptr)) {
+    LightingParams q{};
+    if (args.rgba == nullptr || count > static_cast<std::size_t>(kLightingMaxLights) || (count != 0 && lights == nullptr) ||
+        !FillViewBand(q.view, d_vertices, d_shade, n, frame, background, args, kLightingBlock)) {
         return hipErrorInvalidValue;
     }
-    LightingParams q{};
     bool recompute = false;
     unsigned frames = 0u;
     for (std::size_t i = 0; i < count; ++i) {
@@ -6182,74 +5977,23 @@ hipError_t LaunchLighting(const float* d_vertices, const float* d_shade, std::ui
             lt.origin[c] = in.frames[0].frame.origin[c];
             lt.color[c] = in.color[c];
         }
-        for (unsigned k = 0; k < faces; ++k) {
-            const ShadowLight& l = in.frames[k];
-            if ((n != 0 && l.rank == nullptr) || l.svertices == nullptr || l.edges == nullptr ||
-                l.width != in.frames[0].width || l.height != in.frames[0].height ||
-                std::memcmp(l.frame.origin, in.frames[0].frame.origin, sizeof l.frame.origin) != 0 ||
-                (l.setup != nullptr && (l.width == 0 || l.height == 0 || !CullBinnable(l.width, l.height) ||
-                                        l.setup->tiles != CullTiles(l.width, l.height)))) {
-                return hipErrorInvalidValue;
-            }
-            TraceParams p{};
-            int tiles_y = 0;
-            const bool rc = QueryRecords(p, tiles_y, l.setup, n, l.frame, l.width, l.height, l.svertices, l.edges);
-            if (frames != 0u && rc != recompute) {
-                return hipErrorInvalidValue;  // one record source per launch (the kernel's template argument)
+        for (unsigned k = 0; k < faces; ++k, ++frames) {
+            bool rc = false;
+            if (!SameLight(in.frames[k], in.frames[0]) || !FillLightFrame(q.frame[frames], in.frames[k], n, rc) ||
+                (frames != 0u && rc != recompute)) {
+                return hipErrorInvalidValue;  // (the last: one record source per launch)
             }
             recompute = rc;
-            OmniFaceParams& f = q.frame[frames++];
-            f.cull = p.cull;
-            f.svertices = p.svertices;
-            f.rank = l.rank;
-            f.tile_info = p.tile_info;
-            f.bin_lists = p.bin_lists;
-            f.bin_counts = p.bin_counts;
-            f.large_list = p.large_list;
-            f.bin_capacity = p.bin_capacity;
-            f.tiles = p.tiles;
-            f.tiles_x = p.tiles_x;
-            f.tiles_y = tiles_y;
-            f.stream_end = n == 0 ? 0u : p.n_pad;
-            f.wf = p.wf;
-            f.hf = p.hf;
-            for (int c = 0; c < 3; ++c) {
-                f.base[c] = l.frame.base[c];
-                f.du[c] = l.frame.du[c];
-                f.dv[c] = l.frame.dv[c];
-                f.origin[c] = l.frame.origin[c];
-            }
-            ShadowProjectionRows(l.frame.base, l.frame.du, l.frame.dv, f.rows);
         }
     }
-    q.vertices = d_vertices;
-    q.shade = reinterpret_cast<const float4*>(d_shade);
-    q.offsets = reinterpret_cast<const float2*>(args.offsets);
-    q.ids = args.ids;
     q.rgba = reinterpret_cast<F4*>(args.rgba);
     q.classes = args.classes;
-    q.n = static_cast<unsigned>(n);
-    q.width = static_cast<unsigned>(args.width);
-    q.row_begin = static_cast<unsigned>(args.row_begin);
-    q.pixels = static_cast<unsigned>(pixels);
     q.count = static_cast<unsigned>(count);
-    q.wf = static_cast<float>(args.width);
-    q.hf = static_cast<float>(args.height);
     for (int k = 0; k < 3; ++k) {
-        q.eye[k] = frame.origin[k];
-        q.base[k] = frame.base[k];
-        q.du[k] = frame.du[k];
-        q.dv[k] = frame.dv[k];
-        q.bg[k] = background[k];
         q.ambient[k] = args.ambient[k];
     }
-    const dim3 grid(static_cast<unsigned>((pixels + kLightingBlock - 1) / kLightingBlock));
-    if (recompute) {
-        hipLaunchKernelGGL(LightingKernel<true>, grid, dim3(kLightingThreads), 0, stream, q);
-    } else {
-        hipLaunchKernelGGL(LightingKernel<false>, grid, dim3(kLightingThreads), 0, stream, q);
-    }
-    return hipGetLastError();
+    return LaunchBySource(recompute, LightingKernel<true>, LightingKernel<false>, ViewBandGrid(q.view, kLightingBlock),
+                          kLightingThreads, stream, q);
 }
 
 hipError_t LaunchGBuffer(const float* d_vertices, const float* d_shade, std::uint64_t n, const Frame& frame,

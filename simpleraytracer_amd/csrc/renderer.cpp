@@ -1083,6 +1083,32 @@ bool DeviceScene::QuerySetup(CullSetup& setup, hipStream_t stream) const {
     return shared;
 }
 
+void DeviceScene::CheckLightScene(const DeviceScene& f, const DeviceScene& first, const LightWords& w) const {
+    const auto who = [&w] { return std::string(w.who); };  // (built only to be thrown)
+    if (f.m_width == 0) {
+        throw std::runtime_error(who() + w.unprepared);
+    }
+    if (f.m_width != first.m_width || f.m_height != first.m_height) {
+        throw std::runtime_error(who() + ": " + w.faces + " are prepared at different sizes");
+    }
+    if (f.m_device != m_device) {
+        throw std::runtime_error(who() + ": the view scene lives on device " + std::to_string(m_device) + ", " + w.light +
+                                 " on device " + std::to_string(f.m_device));
+    }
+    if (f.m_n != m_n) {
+        throw std::runtime_error(who() + ": the view scene has " + std::to_string(m_n) + " triangles, " + w.its_scene + " " +
+                                 std::to_string(f.m_n));
+    }
+}
+
+ShadowLight DeviceScene::AsLightFrame(const DeviceScene& view, CullSetup& setup, hipStream_t stream) const {
+    if (this != &view) {  // (the view scene orders itself)
+        OrderAfterPrevious(stream);
+    }
+    const bool shared = QuerySetup(setup, stream);
+    return ShadowLight{shared ? &setup : nullptr, m_frame, m_width, m_height, m_svertices, m_edges, m_rank};
+}
+
 // The shadow mask of a band of this scene's prepared frame under `light`'s prepared frame (render.h
 // LaunchShadow). The launch reads both scenes' buffers, so it is ordered after the previous call
 // of either and both record it. The light's vertices are a second copy of this scene's (the scenes
@@ -1093,17 +1119,8 @@ void DeviceScene::Shadow(const DeviceScene& light, const float* d_offsets, const
     if (m_width == 0) {
         throw std::runtime_error("Shadow: Prepare() has not been called on the view scene");
     }
-    if (light.m_width == 0) {
-        throw std::runtime_error("Shadow: Prepare() has not been called on the light scene");
-    }
-    if (light.m_device != m_device) {
-        throw std::runtime_error("Shadow: the view scene lives on device " + std::to_string(m_device) +
-                                 ", the light scene on device " + std::to_string(light.m_device));
-    }
-    if (light.m_n != m_n) {
-        throw std::runtime_error("Shadow: the view scene has " + std::to_string(m_n) + " triangles, the light scene " +
-                                 std::to_string(light.m_n));
-    }
+    CheckLightScene(light, light,
+                    {"Shadow", ": Prepare() has not been called on the light scene", "", "the light scene", "the light scene"});
     if (!(bias >= 0.f) || !std::isfinite(bias)) {
         throw std::runtime_error("Shadow: bias must be finite and >= 0");
     }
@@ -1117,13 +1134,8 @@ void DeviceScene::Shadow(const DeviceScene& light, const float* d_offsets, const
         return;
     }
     OrderAfterPrevious(stream);
-    if (&light != this) {
-        light.OrderAfterPrevious(stream);
-    }
     CullSetup setup{};
-    const bool shared = light.QuerySetup(setup, stream);
-    const ShadowLight sl{shared ? &setup : nullptr, light.m_frame, light.m_width, light.m_height,
-                         light.m_svertices, light.m_edges, light.m_rank};
+    const ShadowLight sl = light.AsLightFrame(*this, setup, stream);
     const ShadowArgs args{d_offsets, d_ids, m_width, m_height, row_begin, row_count, bias, d_mask, d_rgba, dim};
     HipCheck(LaunchShadow(m_vertices, m_shade, m_n, m_frame, m_background, sl, args, stream), "shadow launch");
     RecordOrder(stream);
@@ -1142,21 +1154,8 @@ void DeviceScene::OmniShadow(const DeviceScene* const faces[6], const float* d_o
         throw std::runtime_error("Omni shadow: Prepare() has not been called on the view scene");
     }
     for (int k = 0; k < 6; ++k) {
-        const DeviceScene& f = *faces[k];
-        if (f.m_width == 0) {
-            throw std::runtime_error("Omni shadow: the light has not been prepared");
-        }
-        if (f.m_width != faces[0]->m_width || f.m_height != faces[0]->m_height) {
-            throw std::runtime_error("Omni shadow: the light's faces are prepared at different sizes");
-        }
-        if (f.m_device != m_device) {
-            throw std::runtime_error("Omni shadow: the view scene lives on device " + std::to_string(m_device) +
-                                     ", the light on device " + std::to_string(f.m_device));
-        }
-        if (f.m_n != m_n) {
-            throw std::runtime_error("Omni shadow: the view scene has " + std::to_string(m_n) +
-                                     " triangles, the light's scene " + std::to_string(f.m_n));
-        }
+        CheckLightScene(*faces[k], *faces[0],
+                        {"Omni shadow", ": the light has not been prepared", "the light's faces", "the light", "the light's scene"});
     }
     if (!(bias >= 0.f) || !std::isfinite(bias)) {
         throw std::runtime_error("Omni shadow: bias must be finite and >= 0");
@@ -1174,11 +1173,7 @@ void DeviceScene::OmniShadow(const DeviceScene* const faces[6], const float* d_o
     CullSetup setups[6] = {};
     ShadowLight lights[6];
     for (int k = 0; k < 6; ++k) {
-        const DeviceScene& f = *faces[k];
-        f.OrderAfterPrevious(stream);
-        const bool shared = f.QuerySetup(setups[k], stream);
-        lights[k] = ShadowLight{shared ? &setups[k] : nullptr, f.m_frame, f.m_width, f.m_height,
-                                f.m_svertices,                 f.m_edges, f.m_rank};
+        lights[k] = faces[k]->AsLightFrame(*this, setups[k], stream);
     }
     const ShadowArgs args{d_offsets, d_ids, m_width, m_height, row_begin, row_count, bias, d_mask, d_rgba, dim};
     HipCheck(LaunchOmniShadow(m_vertices, m_shade, m_n, m_frame, m_background, lights, args, d_face, stream),
@@ -1257,20 +1252,8 @@ void DeviceScene::Lighting(const Light* lights, std::size_t count, const float a
         const std::string who = "Lighting: light " + std::to_string(l);
         for (std::size_t k = 0; k < (in.point ? 6u : 1u); ++k) {
             const DeviceScene& f = *in.scenes[k];
-            if (f.m_width == 0) {
-                throw std::runtime_error(who + " has not been prepared");
-            }
-            if (f.m_width != in.scenes[0]->m_width || f.m_height != in.scenes[0]->m_height) {
-                throw std::runtime_error(who + ": the faces are prepared at different sizes");
-            }
-            if (f.m_device != m_device) {
-                throw std::runtime_error(who + ": the view scene lives on device " + std::to_string(m_device) +
-                                         ", the light on device " + std::to_string(f.m_device));
-            }
-            if (f.m_n != m_n) {
-                throw std::runtime_error(who + ": the view scene has " + std::to_string(m_n) +
-                                         " triangles, the light's scene " + std::to_string(f.m_n));
-            }
+            CheckLightScene(f, *in.scenes[0],
+                            {who.c_str(), " has not been prepared", "the faces", "the light", "the light's scene"});
             // One record source per launch (the kernel's template argument; LaunchOmniShadow's rule
             // for its six faces). A frame that cannot be binned has no shared cull setup and
             // recomputes its records; a frame with one reads stored records unless the env says otherwise.
@@ -1302,13 +1285,7 @@ void DeviceScene::Lighting(const Light* lights, std::size_t count, const float a
         const Light& in = lights[l];
         ll[l] = LightingLight{sl + frames, in.point, {in.color[0], in.color[1], in.color[2]}, in.falloff, in.bias};
         for (std::size_t k = 0; k < (in.point ? 6u : 1u); ++k, ++frames) {
-            const DeviceScene& f = *in.scenes[k];
-            if (&f != this) {
-                f.OrderAfterPrevious(stream);
-            }
-            const bool shared = f.QuerySetup(setups[frames], stream);
-            sl[frames] = ShadowLight{shared ? &setups[frames] : nullptr, f.m_frame, f.m_width, f.m_height,
-                                     f.m_svertices,                      f.m_edges, f.m_rank};
+            sl[frames] = in.scenes[k]->AsLightFrame(*this, setups[frames], stream);
         }
     }
     const LightingArgs args{d_offsets, d_ids,  m_width,  m_height, row_begin, row_count, {ambient[0], ambient[1], ambient[2]},

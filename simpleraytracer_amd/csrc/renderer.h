@@ -19,6 +19,7 @@ namespace srt {
 
 struct CullBins;     // render.h
 struct CullSetup;    // render.h
+struct ShadowLight;  // render.h
 struct StageEvents;  // render.h
 struct OrderScratch;  // render.h
 
@@ -309,6 +310,20 @@ private:
     // its records: known without building anything.
     bool QuerySetupUsable() const;
     bool QueryRecomputes() const;
+    // A light frame's scene `f` against this view scene (Shadow, OmniShadow, Lighting): prepared, at
+    // its light's size (`first`: the light's first frame), on this device, of as many triangles --
+    // else thrown in the family's own words.
+    struct LightWords {
+        const char* who;         // "Shadow", "Omni shadow", "Lighting: light 3"
+        const char* unprepared;  // who + this
+        const char* faces;       // "the light's faces" or "the faces": prepared at different sizes
+        const char* light;       // "the light scene" or "the light": what lives on another device
+        const char* its_scene;   // "the light scene" or "the light's scene": whose triangles are counted
+    };
+    void CheckLightScene(const DeviceScene& f, const DeviceScene& first, const LightWords& w) const;
+    // This scene as a light frame of `view`'s launch on `stream`: ordered after its previous call,
+    // its query setup (re)built into `setup` if it has one.
+    ShadowLight AsLightFrame(const DeviceScene& view, CullSetup& setup, hipStream_t stream) const;
     Frame m_frame{};
     std::size_t m_width = 0;
     std::size_t m_height = 0;

@@ -281,6 +281,67 @@ def odd_layers(name: str):
     return ids, t
 
 
+# The shadow families (test_gpu_count.test_shadow_families): two spot lights beside the view's eye,
+# looking at the middle of the grid, and a point light at the first one's eye.
+L1 = (0.6, 0.0, 0.0, 0.0, 0.0, 5.0, 0.0, 1.0, 0.0, 70.0)
+L2 = (0.0, 0.6, 0.0, 0.0, 0.0, 5.0, 0.0, 1.0, 0.0, 70.0)
+LIGHT_CAMS = {"L1": L1, "L2": L2}
+POINT_ORIGIN = L1[:3]
+FACE_SIZE = 64
+SHADOW_DIM = 0.25
+LIGHT_COLORS = ((1.0, 0.9, 0.8), (0.2, 0.3, 0.9), (0.6, 0.8, 0.4))  # L1, L2, the point light
+LIGHT_FALLOFF = (0.0, 0.0, 9.0)
+AMBIENT = (0.05, 0.04, 0.03)
+SHADOW_NAMES = ("n9", "n255", "n256", "n257", "n4095", "n4096", "n4097", "n257d1", "n4097d1")
+# The light under which the last live record of the *light's* order decides a pixel of the mask
+# (guard (b) of shadow_answers). n9 and n257 have none: no light position tried (sixteen eyes around
+# the view's) puts that record between the light and another triangle's visible pixel, so those two
+# cases run without the guard.
+KNOCK_OUT = {"n255": "L2", "n256": "L1", "n4095": "L1", "n4096": "L1", "n4097": "L2", "n257d1": "L1", "n4097d1": "L1"}
+
+
+def host_lights():
+    from simpleraytracer_amd import PointLightHost, SpotLightHost
+
+    return [SpotLightHost(L1, W, H, LIGHT_COLORS[0], LIGHT_FALLOFF[0], 0.0),
+            SpotLightHost(L2, W, H, LIGHT_COLORS[1], LIGHT_FALLOFF[1], 0.0),
+            PointLightHost(POINT_ORIGIN, FACE_SIZE, LIGHT_COLORS[2], LIGHT_FALLOFF[2], 0.0)]
+
+
+@functools.lru_cache(maxsize=None)
+def shadow_answers(name: str) -> SimpleNamespace:
+    """The host paths' answers for the whole 256 x 144 frame under offsets() and frame_ids(): spot
+    (mask, rgba) under L1 at SHADOW_DIM, omni (mask, face, rgba) under the point light, lighting (rgba,
+    classes) under host_lights() and AMBIENT. Guards: (a) L1's mask holds at least 100 shadowed (n9: 9)
+    and 100 lit pixels; (b) for the cases of KNOCK_OUT, moving the last live record of the light's order
+    behind both eyes changes the mask at a pixel of another triangle -- a walk that drops the last
+    record of a list or of the stream answers wrongly there."""
+    from simpleraytracer_amd import device
+
+    c = case(name)
+    off, ids = offsets(W, H), frame_ids(name)
+    spot = device.shadow_host(c.path, W, H, L1, W, H, off, ids, dim=SHADOW_DIM)
+    omni = device.omni_shadow_host(c.path, W, H, POINT_ORIGIN, FACE_SIZE, off, ids, dim=SHADOW_DIM)
+    lighting = device.lighting_host(c.path, W, H, host_lights(), AMBIENT, off, ids)
+    counts = np.bincount(spot[0].ravel(), minlength=4)
+    # (n9's nine triangles shadow 9 pixels of one another under L1; every other case at least 277)
+    assert counts[0] >= (9 if name == "n9" else 100) and counts[1] >= 100, f"{name}: classes {counts.tolist()} of L1's mask"
+    assert np.array_equal(lighting[1][0], spot[0]) and np.array_equal(lighting[1][2], omni[0])
+    if name in KNOCK_OUT:
+        cam = LIGHT_CAMS[KNOCK_OUT[name]]
+        sc = device.read_scene(c.path)
+        v = sc["vertices"].copy()
+        j = int(device.order_host(v, cam)[0][c.live - 1])
+        v[j] = (0.0, 0.0, -5.0, 0.1, 0.0, -5.0, 0.0, 0.1, -5.0)  # behind the view's eye and the light's
+        without = _write(_dir() / f"{name}_without_{j}.srt", v, sc["albedo"])
+        full = spot[0] if cam is L1 else device.shadow_host(c.path, W, H, cam, W, H, off, ids)[0]
+        mask = device.shadow_host(without, W, H, cam, W, H, off, ids)[0]
+        assert ((mask != full) & (ids != j)).any(), f"{name}: the light order's last record {j} decides no pixel"
+    for a in (*spot, *omni, *lighting):
+        a.setflags(write=False)
+    return SimpleNamespace(spot=spot, omni=omni, lighting=lighting)
+
+
 def id_planes(n: int) -> int:
     """The bit planes above 16 that the packed hit ids of n triangles need: the codes are 0 .. n - 1
     and the miss code is all ones, so they fit 16 + p bits while n <= 2^(16 + p) - 1."""

@@ -149,6 +149,55 @@ def test_query_and_layers(monkeypatch, name, cap):
             assert np.all(h[inside] == 0)
 
 
+@pytest.mark.parametrize("cap", ["", "8"], ids=["default", "cap8"])
+@pytest.mark.parametrize("name", cc.SHADOW_NAMES)
+def test_shadow_families(monkeypatch, name, cap):
+    """scene.shadow under L1, omni_shadow under the point light at L1's eye and scene.light under both
+    spot lights and the point light, whole frame, ids the oracle's: every class byte, the face plane
+    and the RGBA equal the host paths' on the bits (count_cases.shadow_answers, whose guards say what
+    the light orders' tails decide; n9 and n257 run without the knock-out guard: count_cases.KNOCK_OUT).
+    With the lists capped at 8 entries the overflowed tiles of every light frame stream through n_pad."""
+    import torch
+
+    import simpleraytracer_amd as srt
+
+    if cap:
+        monkeypatch.setenv("SRT_CULL_BIN_CAP", cap)
+    c = cc.case(name)
+    want = cc.shadow_answers(name)
+    stream = torch.cuda.current_stream()
+    view = srt.DeviceScene(c.path, 0)
+    view.prepare(W, H, stream)
+    spots = [srt.DeviceScene(c.path, 0, camera=cam) for cam in (cc.L1, cc.L2)]
+    for s in spots:
+        s.prepare(W, H, stream)
+    point = srt.OmniLight(c.path, 0, cc.POINT_ORIGIN)
+    point.prepare(cc.FACE_SIZE, stream)
+    off = torch.from_numpy(cc.offsets(W, H)).cuda()
+    ids = torch.from_numpy(np.array(cc.frame_ids(name))).cuda()
+    mask, omask, face = (torch.full((H, W), 9, dtype=torch.uint8, device="cuda") for _ in range(3))
+    rgba, orgba, lrgba = (torch.full((H, W, 4), float("nan"), dtype=torch.float32, device="cuda") for _ in range(3))
+    classes = torch.full((3, H, W), 9, dtype=torch.uint8, device="cuda")
+    view.shadow(spots[0], off, ids, mask, rgba, dim=cc.SHADOW_DIM, stream=stream)
+    view.omni_shadow(point, off, ids, omask, face, orgba, dim=cc.SHADOW_DIM, stream=stream)
+    lights = [srt.SpotLight(spots[0], cc.LIGHT_COLORS[0], cc.LIGHT_FALLOFF[0]),
+              srt.SpotLight(spots[1], cc.LIGHT_COLORS[1], cc.LIGHT_FALLOFF[1]),
+              srt.PointLight(point, cc.LIGHT_COLORS[2], cc.LIGHT_FALLOFF[2])]
+    view.light(lights, off, ids, lrgba, ambient=cc.AMBIENT, classes=classes, stream=stream)
+    torch.cuda.synchronize()
+    got = [a.cpu().numpy() for a in (mask, rgba, omask, face, orgba, lrgba, classes)]
+    point.close()
+    for s in spots:
+        s.close()
+    view.close()
+    names = ("shadow mask", "shadow rgba", "omni mask", "omni face", "omni rgba", "lighting rgba", "lighting classes")
+    for what, g, w in zip(names, got, (*want.spot, *want.omni, *want.lighting)):
+        if g.dtype == np.uint8:
+            assert w.dtype == np.uint8 and np.array_equal(g, w), f"{what}: {int((g != w).sum())} bytes differ"
+        else:
+            lc.same_bits(what, g, w)
+
+
 @pytest.mark.parametrize("name", SMALL_AND_DEAD)
 def test_layer_frame_odd(name):
     """scene.layer_frame at 200 x 72 equals the peeled oracle, every pixel answered from the lists."""
