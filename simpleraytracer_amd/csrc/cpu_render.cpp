@@ -7,6 +7,7 @@
 #include "samples_math.h"
 #include "screen_box.h"
 #include "shadow_math.h"
+#include "surface_math.h"
 
 #include <algorithm>
 #include <atomic>
@@ -262,6 +263,124 @@ void HostGBuffer(const Scene& scene, std::size_t width, std::size_t height, cons
         if (albedo != nullptr) {
             const float v[4] = {o.r, o.g, o.b, o.a};
             std::copy(v, v + 4, albedo + 4 * q);
+        }
+    });
+}
+
+void HostSurface(const Scene& scene, std::size_t width, std::size_t height, const float* positions, const int* ids,
+                 std::size_t count, const float* normals, const float* uvs, const float* texture,
+                 std::size_t tex_width, std::size_t tex_height, unsigned flags, float* normal, float* albedo,
+                 float* rgba, float* uv) {
+    if (width == 0 || height == 0) {
+        throw std::runtime_error("Host surface: frame dimensions must be non-zero");
+    }
+    if ((flags & ~kSurfaceFlags) != 0u) {
+        throw std::runtime_error("Host surface: unknown flags");
+    }
+    if (texture != nullptr && (uvs == nullptr || tex_width < 1 || tex_width > kSurfaceMaxTexture || tex_height < 1 ||
+                               tex_height > kSurfaceMaxTexture)) {
+        throw std::runtime_error("Host surface: a texture needs uvs and 1 to 16384 texels per side");
+    }
+    if (normal == nullptr && albedo == nullptr && rgba == nullptr && uv == nullptr) {
+        return;  // (no plane: nothing is read either)
+    }
+    const Frame f = MakeFrame(scene.camera, width, height);
+    const std::size_t n = scene.triangle_count();
+    const bool clamp = (flags & kSurfaceWrapClamp) != 0u, nearest = (flags & kSurfaceFilterNearest) != 0u;
+    const bool modulate = (flags & kSurfaceModulate) != 0u;
+    const int tw = static_cast<int>(tex_width), th = static_cast<int>(tex_height);
+    ParallelFor(count, 256, [&](std::size_t q) {
+        const int id = ids[q];
+        float on[4] = {0.f, 0.f, 0.f, 1.f};
+        float oa[4] = {scene.background[0], scene.background[1], scene.background[2], -1.f};
+        float ouv[2] = {0.f, 0.f};
+        if (id >= 0 && static_cast<std::size_t>(id) < n) {
+            const std::size_t i = static_cast<std::size_t>(id);
+            const float fx = positions[2 * q], fy = positions[2 * q + 1];
+            const Rec r = MakeRecord(scene.vertices.data() + 9 * i, f);
+            const SurfaceWeights bw = SurfaceBary(r.c, fx, fy);
+            const float* a = scene.albedo.data() + 3 * i;
+            if (normals != nullptr) {
+                const float* cn = normals + 9 * i;
+                const SurfaceNormal s = SurfaceSmoothNormal(SurfaceMix(bw, cn[0], cn[3], cn[6]),
+                                                            SurfaceMix(bw, cn[1], cn[4], cn[7]),
+                                                            SurfaceMix(bw, cn[2], cn[5], cn[8]), f.base, f.du, f.dv, fx, fy);
+                const float v[4] = {s.x, s.y, s.z, s.cosv};
+                std::copy(v, v + 4, on);
+            } else {
+                const GBufferTexel g = GBufferHit(r.c, r.vol, f.base, f.du, f.dv, fx, fy, id, r.n[0], r.n[1], r.n[2],
+                                                  r.n[3], a[0], a[1], a[2]);
+                const float v[4] = {g.nx, g.ny, g.nz, g.cosv};
+                std::copy(v, v + 4, on);
+            }
+            if (uvs != nullptr) {
+                const float* ct = uvs + 6 * i;
+                ouv[0] = SurfaceMix(bw, ct[0], ct[2], ct[4]);
+                ouv[1] = SurfaceMix(bw, ct[1], ct[3], ct[5]);
+            }
+            std::copy(a, a + 3, oa);
+            if (texture != nullptr) {
+                float tex[3];
+                if (nearest) {
+                    const int ti = SurfaceNearest(SurfaceWrap(ouv[0], clamp), tw);
+                    const int tj = SurfaceNearest(SurfaceWrap(ouv[1], clamp), th);
+                    const float* t = texture + 4 * (static_cast<std::size_t>(tj) * tex_width + static_cast<std::size_t>(ti));
+                    std::copy(t, t + 3, tex);
+                } else {
+                    const SurfaceTaps sx = SurfaceBilinear(SurfaceWrap(ouv[0], clamp), tw, clamp);
+                    const SurfaceTaps sy = SurfaceBilinear(SurfaceWrap(ouv[1], clamp), th, clamp);
+                    const float* top = texture + 4 * static_cast<std::size_t>(sy.i0) * tex_width;
+                    const float* bot = texture + 4 * static_cast<std::size_t>(sy.i1) * tex_width;
+                    for (int c = 0; c < 3; ++c) {
+                        tex[c] = SurfaceLerp(SurfaceLerp(top[4 * sx.i0 + c], top[4 * sx.i1 + c], sx.a),
+                                             SurfaceLerp(bot[4 * sx.i0 + c], bot[4 * sx.i1 + c], sx.a), sy.a);
+                    }
+                }
+                for (int c = 0; c < 3; ++c) {
+                    oa[c] = modulate ? tex[c] * a[c] : tex[c];
+                }
+            }
+            oa[3] = static_cast<float>(id);
+        }
+        if (normal != nullptr) {
+            std::copy(on, on + 4, normal + 4 * q);
+        }
+        if (albedo != nullptr) {
+            std::copy(oa, oa + 4, albedo + 4 * q);
+        }
+        if (rgba != nullptr) {
+            const float v[4] = {oa[0] * on[3], oa[1] * on[3], oa[2] * on[3], oa[3]};
+            std::copy(v, v + 4, rgba + 4 * q);
+        }
+        if (uv != nullptr) {
+            uv[2 * q] = ouv[0];
+            uv[2 * q + 1] = ouv[1];
+        }
+    });
+}
+
+void HostInterpolate(const Scene& scene, std::size_t width, std::size_t height, const float* positions, const int* ids,
+                     std::size_t count, const float* table, std::size_t channels, float* out) {
+    if (width == 0 || height == 0) {
+        throw std::runtime_error("Host interpolation: frame dimensions must be non-zero");
+    }
+    if (channels < 1 || channels > static_cast<std::size_t>(kSurfaceMaxChannels)) {
+        throw std::runtime_error("Host interpolation: channels must be 1 to 4");
+    }
+    const Frame f = MakeFrame(scene.camera, width, height);
+    const std::size_t n = scene.triangle_count();
+    ParallelFor(count, 256, [&](std::size_t q) {
+        const int id = ids[q];
+        float* o = out + channels * q;
+        std::fill(o, o + channels, 0.f);
+        if (id >= 0 && static_cast<std::size_t>(id) < n) {
+            const std::size_t i = static_cast<std::size_t>(id);
+            const Rec r = MakeRecord(scene.vertices.data() + 9 * i, f);
+            const SurfaceWeights bw = SurfaceBary(r.c, positions[2 * q], positions[2 * q + 1]);
+            const float* a = table + 3 * channels * i;
+            for (std::size_t c = 0; c < channels; ++c) {
+                o[c] = SurfaceMix(bw, a[c], a[channels + c], a[2 * channels + c]);
+            }
         }
     });
 }

@@ -38,6 +38,21 @@ void HostClosestHits(const Scene& scene, std::size_t width, std::size_t height, 
 void HostGBuffer(const Scene& scene, std::size_t width, std::size_t height, const float* positions, const int* ids,
                  std::size_t count, float* depth, float* bary, float* normal, float* albedo);
 
+// The vertex attributes (surface_math.h) of `count` (position, triangle id) pairs of the scene's
+// width x height frame (the host answer of render.h LaunchSurface): the caller's corner normals
+// (n x 9), corner uvs (n x 6) and texture (tex_height x tex_width x 4), each null for none, under
+// `flags` (surface_math.h kSurface*), into the planes that are non-null: normal[count][4],
+// albedo[count][4], rgba[count][4], uv[count][2]. An id outside the scene gives the miss values.
+void HostSurface(const Scene& scene, std::size_t width, std::size_t height, const float* positions, const int* ids,
+                 std::size_t count, const float* normals, const float* uvs, const float* texture,
+                 std::size_t tex_width, std::size_t tex_height, unsigned flags, float* normal, float* albedo,
+                 float* rgba, float* uv);
+
+// The interpolation of one corner table (n x 3 x channels) at the pairs (the host answer of render.h
+// LaunchInterpolate): out[count][channels]; an id outside the scene gives zeros.
+void HostInterpolate(const Scene& scene, std::size_t width, std::size_t height, const float* positions, const int* ids,
+                     std::size_t count, const float* table, std::size_t channels, float* out);
+
 // The resolve of `samples` sample planes of the band rows [row_begin, row_begin + row_count) of the
 // scene's width x height frame (the host answer of render.h LaunchResolve; samples_math.h):
 // offsets[s] (row_count x width x 2) and ids[s] (row_count x width), band-local, into rgba

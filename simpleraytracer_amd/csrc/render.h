@@ -541,6 +541,55 @@ struct GBufferArgs {
 hipError_t LaunchGBuffer(const float* d_vertices, const float* d_shade, std::uint64_t n, const Frame& frame,
                          const float background[3], const GBufferArgs& args, hipStream_t stream);
 
+// Vertex attributes (render.hip SurfaceKernel / InterpolateKernel): what the surface looks like at
+// (image position, triangle id) pairs -- a smooth normal, a UV, a textured albedo and the shaded
+// pixel (surface_math.h; DESIGN.md section 2 "Vertex attributes") -- from hit ids and the caller's
+// per-triangle corner tables, a deferred pass like LaunchGBuffer. The weights come from the record
+// recomputed from the scene's vertices: no edge buffer, no cull setup is read. An id outside
+// [0, n) gives the miss values and reads nothing through it.
+struct SurfaceArgs {
+    // Elements as GBufferArgs'.
+    bool points;
+    const float* where;  // device
+    const int* ids;      // device
+    std::size_t width;
+    std::size_t height;
+    std::size_t row_begin;
+    std::size_t row_count;
+    // The surface (device; null: none): corner normals n x 9, corner uvs n x 6, texture th x tw x 4.
+    const float* normals;
+    const float* uvs;
+    const float* texture;
+    std::size_t tex_width;
+    std::size_t tex_height;
+    unsigned flags;  // surface_math.h kSurface*
+    // The planes (device; null: not written), each row_count x width elements.
+    float* normal;  // [4]: (unit normal towards the eye, cos)
+    float* albedo;  // [4]: (r, g, b, float(id))
+    float* rgba;    // [4]: (albedo.rgb * cos, float(id))
+    float* uv;      // [2]
+};
+// One launch; no elements or no plane: none.
+hipError_t LaunchSurface(const float* d_vertices, const float* d_shade, std::uint64_t n, const Frame& frame,
+                         const float background[3], const SurfaceArgs& args, hipStream_t stream);
+
+// The interpolation of one corner table (device, n x 3 x channels, 1 <= channels <= 4) at the
+// elements (as SurfaceArgs'): out = row_count x width x channels floats.
+struct InterpolateArgs {
+    bool points;
+    const float* where;
+    const int* ids;
+    std::size_t width;
+    std::size_t height;
+    std::size_t row_begin;
+    std::size_t row_count;
+    const float* table;
+    std::size_t channels;
+    float* out;
+};
+hipError_t LaunchInterpolate(const float* d_vertices, std::uint64_t n, const Frame& frame, const InterpolateArgs& args,
+                             hipStream_t stream);
+
 // Resolve (render.hip ResolveKernel): one RGBA pixel from `samples` (sample offset, hit id) planes
 // of a band -- every sample shaded as LaunchShade shades it, summed in ascending order and divided
 // by the count; alpha = the share of samples that hit (samples_math.h; DESIGN.md section 2

@@ -407,6 +407,52 @@ void DeviceScene::GBuffer(bool points, const float* d_where, const int* d_ids, s
     RecordOrder(stream);
 }
 
+void DeviceScene::Surface(bool points, const float* d_where, const int* d_ids, std::size_t row_begin, std::size_t count,
+                          const SurfaceArgs& planes, hipStream_t stream) const {
+    if (m_width == 0) {
+        throw std::runtime_error("Surface: Prepare() has not been called");
+    }
+    if (!points && (row_begin > m_height || count > m_height - row_begin)) {
+        throw std::runtime_error("Surface: row band outside the frame");
+    }
+    if (count == 0 ||
+        (planes.normal == nullptr && planes.albedo == nullptr && planes.rgba == nullptr && planes.uv == nullptr)) {
+        return;
+    }
+    OrderAfterPrevious(stream);
+    SurfaceArgs args = planes;
+    args.points = points;
+    args.where = d_where;
+    args.ids = d_ids;
+    args.width = points ? count : m_width;  // (points: one row of `count` elements)
+    args.height = m_height;
+    args.row_begin = points ? 0 : row_begin;
+    args.row_count = points ? 1 : count;
+    HipCheck(LaunchSurface(m_vertices, m_shade, m_n, m_frame, m_background, args, stream), "surface launch");
+    LogSetupStats();  // (the counters as they stand: this call builds nothing)
+    RecordOrder(stream);
+}
+
+void DeviceScene::Interpolate(bool points, const float* d_where, const int* d_ids, std::size_t row_begin,
+                              std::size_t count, const float* d_table, std::size_t channels, float* d_out,
+                              hipStream_t stream) const {
+    if (m_width == 0) {
+        throw std::runtime_error("Interpolate: Prepare() has not been called");
+    }
+    if (!points && (row_begin > m_height || count > m_height - row_begin)) {
+        throw std::runtime_error("Interpolate: row band outside the frame");
+    }
+    if (count == 0) {
+        return;
+    }
+    OrderAfterPrevious(stream);
+    const InterpolateArgs args{points, d_where, d_ids, points ? count : m_width, m_height, points ? 0 : row_begin,
+                               points ? 1 : count, d_table, channels, d_out};
+    HipCheck(LaunchInterpolate(m_vertices, m_n, m_frame, args, stream), "interpolation launch");
+    LogSetupStats();
+    RecordOrder(stream);
+}
+
 void DeviceScene::Resolve(const float* const* d_offsets, const int* const* d_ids, std::size_t samples,
                           std::size_t row_begin, std::size_t row_count, float* d_rgba, hipStream_t stream) const {
     if (m_width == 0) {

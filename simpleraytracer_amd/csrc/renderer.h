@@ -22,6 +22,7 @@ struct CullSetup;    // render.h
 struct ShadowLight;  // render.h
 struct StageEvents;  // render.h
 struct OrderScratch;  // render.h
+struct SurfaceArgs;   // render.h
 
 // Throws std::runtime_error("HIP error: <what>: <reason>") on failure.
 void HipCheck(hipError_t err, const char* what);
@@ -181,6 +182,17 @@ public:
     // Reads the scene's vertices and shading table only: no cull setup is built or read.
     void GBuffer(bool points, const float* d_where, const int* d_ids, std::size_t row_begin, std::size_t count,
                  float* d_depth, float* d_bary, float* d_normal, float* d_albedo, hipStream_t stream) const;
+
+    // Vertex attributes (render.h SurfaceArgs / InterpolateArgs) of hit ids on the prepared frame:
+    // elements as GBuffer's (points, d_where, d_ids, row_begin, count). Surface: the planes of
+    // `planes` asked for (its element fields are ignored) from the caller's device tables in it.
+    // Interpolate: one corner table (n x 3 x channels) into d_out (elements x channels). The scene
+    // keeps no table. Both read the scene's vertices and shading table only: no cull setup is built
+    // or read (neither calls EnsureSetup).
+    void Surface(bool points, const float* d_where, const int* d_ids, std::size_t row_begin, std::size_t count,
+                 const SurfaceArgs& planes, hipStream_t stream) const;
+    void Interpolate(bool points, const float* d_where, const int* d_ids, std::size_t row_begin, std::size_t count,
+                     const float* d_table, std::size_t channels, float* d_out, hipStream_t stream) const;
 
     // Multi-sample frames (render.h LaunchResolve). Resolve: the band rows [row_begin, row_begin +
     // row_count) of the prepared frame from `samples` (1 .. kMaxSamples) planes of sample offsets

@@ -1,5 +1,7 @@
 #include "scene.h"
 
+#include "shading_normal.h"
+
 #include <algorithm>
 #include <array>
 #include <cctype>
@@ -202,7 +204,8 @@ std::map<std::string, std::array<float, 3>> ReadMtl(const std::string& path) {
 // Wavefront OBJ subset: `v x y z [w]`, `f a b c ...` with `i`, `i/t`,
 // `i//n`, `i/t/n` and negative (relative) indices, polygons fan-triangulated (v0, vk, vk+1);
 // `mtllib` + `usemtl` give per-face albedo from the materials' Kd (default 0.8 grey);
-// every other statement (vt, vn, o, g, s, l, p, ...) is ignored. Two comment directives set
+// every other statement (vt, vn, o, g, s, l, p, ...) is ignored here (vt and vn: LoadObjAttributes
+// below reads them, for the caller's tables; the scene stays flat). Two comment directives set
 // what OBJ cannot express: `# srt camera ex ey ez lx ly lz ux uy uz vfov_deg` and
 // `# srt background r g b`. Without a camera directive the camera looks along +z at the
 // centre of the bounding box from where the box's bounding sphere fills a 60-degree view.
@@ -337,7 +340,116 @@ Scene LoadObj(const std::string& path) {
     return s;
 }
 
+// One `/`-separated attribute index of a face corner (`what`: "texture" or "normal"), resolved
+// against the `have` values read so far; -1 for an empty field.
+long long ObjAttributeIndex(const std::string& path, std::size_t lineno, const std::string& tok, const char*& at,
+                            const char* what, long long have) {
+    if (*at == '\0' || *at == '/') {
+        return -1;
+    }
+    char* end = nullptr;
+    const long long i = std::strtoll(at, &end, 10);
+    if (end == at || (*end != '\0' && *end != '/')) {
+        ObjError(path, lineno, std::string("bad ") + what + " index in '" + tok + "'");
+    }
+    at = end;
+    const long long r = i > 0 ? i - 1 : have + i;  // 1-based, or relative when negative
+    if (i == 0 || r < 0 || r >= have) {
+        ObjError(path, lineno, std::string(what) + " index " + std::to_string(i) + " out of range (" +
+                                   std::to_string(have) + " " + what + "s so far)");
+    }
+    return r;
+}
+
 }  // namespace
+
+void LoadObjAttributes(const std::string& path, std::vector<float>& normals, std::vector<float>& uvs, bool have[2]) {
+    if (!EndsWithObj(path)) {
+        throw std::runtime_error("Error reading scene file: " + path + ": not a Wavefront OBJ file");
+    }
+    const Scene s = LoadObj(path);  // (every check of the scene itself; the vertices, for the default normals)
+    std::ifstream f(path);
+    std::vector<float> vn, vt;  // 3 per normal, 2 per texture coordinate
+    normals.clear();
+    uvs.clear();
+    have[0] = have[1] = false;
+    std::string line;
+    std::size_t lineno = 0;
+    while (std::getline(f, line)) {
+        ++lineno;
+        if (!line.empty() && line.back() == '\r') {
+            line.pop_back();
+        }
+        std::istringstream in(line);
+        std::string key;
+        if (!(in >> key)) {
+            continue;
+        }
+        if (key == "vn") {
+            float v[3];
+            if (!ReadFloats(in, v, 3)) {
+                ObjError(path, lineno, "normal needs 3 coordinates");
+            }
+            vn.insert(vn.end(), v, v + 3);
+        } else if (key == "vt") {
+            float v[2] = {0.f, 0.f};
+            if (!ReadFloats(in, v, 1)) {
+                ObjError(path, lineno, "texture coordinate needs at least 1 number");
+            }
+            float second;
+            if (ReadFloats(in, &second, 1)) {  // (v is optional: 0)
+                v[1] = second;
+            }
+            vt.insert(vt.end(), v, v + 2);
+        } else if (key == "f") {
+            std::vector<long long> ti, ni;
+            std::string tok;
+            while (in >> tok) {  // (the position indices: LoadObj has checked them)
+                const char* at = tok.c_str();
+                while (*at != '\0' && *at != '/') {
+                    ++at;
+                }
+                long long t = -1, n = -1;
+                if (*at == '/') {
+                    ++at;
+                    t = ObjAttributeIndex(path, lineno, tok, at, "texture", static_cast<long long>(vt.size() / 2));
+                    if (*at == '/') {
+                        ++at;
+                        n = ObjAttributeIndex(path, lineno, tok, at, "normal", static_cast<long long>(vn.size() / 3));
+                    }
+                }
+                ti.push_back(t);
+                ni.push_back(n);
+            }
+            for (std::size_t k = 1; k + 1 < ti.size(); ++k) {  // LoadObj's fan: (v0, vk, vk+1)
+                const std::size_t c[3] = {0, k, k + 1};
+                const std::size_t tri = normals.size() / 9;
+                if (9 * (tri + 1) > s.vertices.size()) {
+                    throw std::runtime_error("Error reading scene file: " + path + ": changed while it was read");
+                }
+                const float4 flat = ShadingNormal(s.vertices.data() + 9 * tri);
+                for (std::size_t v : c) {
+                    if (ni[v] >= 0) {
+                        normals.insert(normals.end(), vn.begin() + 3 * ni[v], vn.begin() + 3 * ni[v] + 3);
+                        have[0] = true;
+                    } else {
+                        const float n3[3] = {flat.x, flat.y, flat.z};
+                        normals.insert(normals.end(), n3, n3 + 3);
+                    }
+                    if (ti[v] >= 0) {
+                        uvs.insert(uvs.end(), vt.begin() + 2 * ti[v], vt.begin() + 2 * ti[v] + 2);
+                        have[1] = true;
+                    } else {
+                        uvs.insert(uvs.end(), 2, 0.f);
+                    }
+                }
+            }
+        }
+    }
+    if (normals.size() != s.vertices.size()) {
+        throw std::runtime_error("Error reading scene file: " + path + ": changed while it was read");
+    }
+}
 
 Scene LoadScene(const std::string& path) {
     if (EndsWithObj(path)) {

@@ -54,6 +54,12 @@ struct Scene {
 Scene LoadScene(const std::string& path);
 void SaveScene(const Scene& scene, const std::string& path);
 
+// The corner normals (`vn`, N x 9) and texture coordinates (`vt`, N x 6) of the triangles LoadScene
+// gives for a Wavefront OBJ file, row for row (the same fan, the same order). A corner without `vn`
+// takes its triangle's shading normal (shading_normal.h), one without `vt` (0, 0); have[0] / have[1]:
+// whether any corner carried one. Bad indices throw with the line, as LoadScene's.
+void LoadObjAttributes(const std::string& path, std::vector<float>& normals, std::vector<float>& uvs, bool have[2]);
+
 // Deterministic generators (own PCG32; no <random> distributions, whose output is
 // implementation-defined). `size` is the soup half-extent s (0 = kind default).
 Scene MakeScene(int kind, std::uint64_t triangles, std::uint64_t seed, float size);

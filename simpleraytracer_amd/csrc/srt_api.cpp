@@ -25,6 +25,8 @@
 #include "srt_query.h"
 #include "srt_render.h"
 #include "srt_samples.h"
+#include "srt_surface.h"
+#include "surface_math.h"
 #include "tile_lookup.h"
 
 namespace {
@@ -1621,6 +1623,210 @@ RTM_API int rtmOrderHost(const float* vertices, unsigned long long n, const floa
             throw std::runtime_error("Bad argument: vertices is NULL");
         }
         srt::OrderHost(vertices, n, camera, order, normals);
+    });
+}
+
+// Vertex attributes (include/srt_surface.h): the rtv family.
+static_assert(RTV_WRAP_CLAMP == srt::kSurfaceWrapClamp && RTV_FILTER_NEAREST == srt::kSurfaceFilterNearest &&
+                  RTV_MODULATE == srt::kSurfaceModulate && RTV_MAX_TEXTURE == srt::kSurfaceMaxTexture &&
+                  RTV_MAX_CHANNELS == srt::kSurfaceMaxChannels,
+              "include/srt_surface.h constants");
+
+namespace {
+
+rtv_surface CheckedSurface(const rtv_surface* s) {
+    if (s == nullptr) {
+        throw std::runtime_error("Bad argument: surface is NULL");
+    }
+    if (s->struct_size != sizeof(rtv_surface)) {
+        throw std::runtime_error("rtv_surface.struct_size is " + std::to_string(s->struct_size) + ", expected " +
+                                 std::to_string(sizeof(rtv_surface)));
+    }
+    if ((s->flags & ~srt::kSurfaceFlags) != 0u) {
+        throw std::runtime_error("rtv_surface.flags is " + std::to_string(s->flags) +
+                                 ": only RTV_WRAP_CLAMP, RTV_FILTER_NEAREST and RTV_MODULATE are known");
+    }
+    if (s->texture != nullptr) {
+        if (s->uvs == nullptr) {
+            throw std::runtime_error("rtv_surface.texture is set but rtv_surface.uvs is NULL: a texture needs uvs");
+        }
+        if (s->tex_width < 1 || s->tex_width > RTV_MAX_TEXTURE) {
+            throw std::runtime_error("rtv_surface.tex_width must be 1 to " + std::to_string(RTV_MAX_TEXTURE) + ", got " +
+                                     std::to_string(s->tex_width));
+        }
+        if (s->tex_height < 1 || s->tex_height > RTV_MAX_TEXTURE) {
+            throw std::runtime_error("rtv_surface.tex_height must be 1 to " + std::to_string(RTV_MAX_TEXTURE) +
+                                     ", got " + std::to_string(s->tex_height));
+        }
+    }
+    return *s;
+}
+
+rtv_outputs CheckedSurfaceOutputs(const rtv_outputs* o) {
+    if (o == nullptr) {
+        throw std::runtime_error("Bad argument: outputs is NULL");
+    }
+    if (o->struct_size != sizeof(rtv_outputs)) {
+        throw std::runtime_error("rtv_outputs.struct_size is " + std::to_string(o->struct_size) + ", expected " +
+                                 std::to_string(sizeof(rtv_outputs)));
+    }
+    return *o;
+}
+
+bool NoSurfacePlane(const rtv_outputs& o) {
+    return o.normal == nullptr && o.albedo == nullptr && o.rgba == nullptr && o.uv == nullptr;
+}
+
+void CheckChannels(size_t channels) {
+    if (channels < 1 || channels > RTV_MAX_CHANNELS) {
+        throw std::runtime_error("Bad argument: channels must be 1 to " + std::to_string(RTV_MAX_CHANNELS) + ", got " +
+                                 std::to_string(channels));
+    }
+}
+
+void NotNull(const void* p, const char* name) {
+    if (p == nullptr) {
+        throw std::runtime_error(std::string("Bad buffer argument: ") + name + " is NULL");
+    }
+}
+
+srt::SurfaceArgs SurfacePlanes(const rtv_surface& s, const rtv_outputs& o) {
+    srt::SurfaceArgs a{};
+    a.normals = s.normals;
+    a.uvs = s.uvs;
+    a.texture = s.texture;
+    a.tex_width = s.tex_width;
+    a.tex_height = s.tex_height;
+    a.flags = s.flags;
+    a.normal = o.normal;
+    a.albedo = o.albedo;
+    a.rgba = o.rgba;
+    a.uv = o.uv;
+    return a;
+}
+
+void SurfaceAsync(srt_device_scene scene, bool points, const float* d_where, const char* where_name, const int* d_ids,
+                  size_t row_begin, size_t count, const rtv_surface* surface, const rtv_outputs* outputs, void* stream) {
+    if (scene == nullptr) {
+        throw std::runtime_error("Bad scene handle");
+    }
+    const rtv_surface s = CheckedSurface(surface);
+    const rtv_outputs o = CheckedSurfaceOutputs(outputs);
+    if (count != 0 && !NoSurfacePlane(o)) {
+        NotNull(d_where, where_name);
+        NotNull(d_ids, "d_ids");
+    }
+    srt::DeviceScene* d = FromHandle(scene);
+    Bind bind(d->device());
+    d->Surface(points, d_where, d_ids, row_begin, count, SurfacePlanes(s, o), static_cast<hipStream_t>(stream));
+}
+
+void InterpolateAsync(srt_device_scene scene, bool points, const float* d_where, const char* where_name,
+                      const int* d_ids, size_t row_begin, size_t count, const float* d_table, size_t channels,
+                      float* d_out, void* stream) {
+    if (scene == nullptr) {
+        throw std::runtime_error("Bad scene handle");
+    }
+    CheckChannels(channels);
+    srt::DeviceScene* d = FromHandle(scene);
+    if (count != 0) {
+        NotNull(d_where, where_name);
+        NotNull(d_ids, "d_ids");
+        NotNull(d_out, "d_out");
+        if (d->triangles() != 0) {
+            NotNull(d_table, "d_table");
+        }
+    }
+    Bind bind(d->device());
+    d->Interpolate(points, d_where, d_ids, row_begin, count, d_table, channels, d_out, static_cast<hipStream_t>(stream));
+}
+
+}  // namespace
+
+RTV_API int rtvSurfaceFrameAsync(srt_device_scene scene, const float* d_offsets, const int* d_ids, size_t row_begin,
+                                 size_t row_count, const rtv_surface* surface, const rtv_outputs* outputs,
+                                 void* stream) {
+    return Guarded(
+        [&] { SurfaceAsync(scene, false, d_offsets, "d_offsets", d_ids, row_begin, row_count, surface, outputs, stream); });
+}
+
+RTV_API int rtvSurfacePointsAsync(srt_device_scene scene, const float* d_positions, const int* d_ids, size_t count,
+                                  const rtv_surface* surface, const rtv_outputs* outputs, void* stream) {
+    return Guarded([&] { SurfaceAsync(scene, true, d_positions, "d_positions", d_ids, 0, count, surface, outputs, stream); });
+}
+
+RTV_API int rtvInterpolateFrameAsync(srt_device_scene scene, const float* d_offsets, const int* d_ids,
+                                     size_t row_begin, size_t row_count, const float* d_table, size_t channels,
+                                     float* d_out, void* stream) {
+    return Guarded([&] {
+        InterpolateAsync(scene, false, d_offsets, "d_offsets", d_ids, row_begin, row_count, d_table, channels, d_out,
+                         stream);
+    });
+}
+
+RTV_API int rtvInterpolatePointsAsync(srt_device_scene scene, const float* d_positions, const int* d_ids, size_t count,
+                                      const float* d_table, size_t channels, float* d_out, void* stream) {
+    return Guarded([&] {
+        InterpolateAsync(scene, true, d_positions, "d_positions", d_ids, 0, count, d_table, channels, d_out, stream);
+    });
+}
+
+RTV_API int rtvSurfaceHost(const char* scene_path, size_t width, size_t height, const float* positions, const int* ids,
+                           size_t count, const rtv_surface* surface, const rtv_outputs* outputs) {
+    return Guarded([&] {
+        const rtv_surface s = CheckedSurface(surface);
+        const rtv_outputs o = CheckedSurfaceOutputs(outputs);
+        if (scene_path == nullptr || width == 0 || height == 0) {
+            throw std::runtime_error("Bad argument");
+        }
+        if (count != 0 && !NoSurfacePlane(o)) {
+            NotNull(positions, "positions");
+            NotNull(ids, "ids");
+        }
+        const srt::Scene scene = srt::LoadScene(scene_path);
+        srt::HostSurface(scene, width, height, positions, ids, count, s.normals, s.uvs, s.texture, s.tex_width,
+                         s.tex_height, s.flags, o.normal, o.albedo, o.rgba, o.uv);
+    });
+}
+
+RTV_API int rtvInterpolateHost(const char* scene_path, size_t width, size_t height, const float* positions,
+                               const int* ids, size_t count, const float* table, size_t channels, float* out) {
+    return Guarded([&] {
+        CheckChannels(channels);
+        if (scene_path == nullptr || width == 0 || height == 0) {
+            throw std::runtime_error("Bad argument");
+        }
+        const srt::Scene scene = srt::LoadScene(scene_path);
+        if (count != 0) {
+            NotNull(positions, "positions");
+            NotNull(ids, "ids");
+            NotNull(out, "out");
+            if (scene.triangle_count() != 0) {
+                NotNull(table, "table");
+            }
+        }
+        srt::HostInterpolate(scene, width, height, positions, ids, count, table, channels, out);
+    });
+}
+
+RTV_API int rtvObjAttributesHost(const char* path, float* normals, float* uvs, int have[2]) {
+    return Guarded([&] {
+        if (path == nullptr) {
+            throw std::runtime_error("Bad argument: path is NULL");
+        }
+        std::vector<float> n, t;
+        bool any[2];
+        srt::LoadObjAttributes(path, n, t, any);
+        if (normals != nullptr) {
+            std::copy(n.begin(), n.end(), normals);
+        }
+        if (uvs != nullptr) {
+            std::copy(t.begin(), t.end(), uvs);
+        }
+        if (have != nullptr) {
+            have[0] = any[0] ? 1 : 0;
+            have[1] = any[1] ? 1 : 0;
+        }
     });
 }
 

@@ -1,8 +1,8 @@
 """Scene files, the device-level render stages (include/srt_render.h), point queries
 (include/srt_query.h), G-buffer outputs (include/srt_gbuffer.h), multi-sample frames
 (include/srt_samples.h), spot-light shadow masks (include/srt_light.h), omni-light shadow masks
-(include/srt_omni.h), direct lighting (include/srt_lighting.h; the lights: lighting.py) and dynamic
-scenes (include/srt_motion.h).
+(include/srt_omni.h), direct lighting (include/srt_lighting.h; the lights: lighting.py), dynamic
+scenes (include/srt_motion.h) and vertex attributes (include/srt_surface.h).
 
 ``DeviceScene`` keeps a scene resident on one GPU and launches the two stages on a caller's
 HIP stream with caller-owned device buffers (torch tensors or raw pointers):
@@ -18,6 +18,7 @@ HIP stream with caller-owned device buffers (torch tensors or raw pointers):
     scene.omni_shadow(omni, offsets, ids, mask, face, stream=s)  # which pixels a point light (an OmniLight) reaches
     scene.light(lights, offsets, ids, rgba, ambient, stream=s)   # the lit picture under several lights (also render_lit())
     scene.set_camera(camera, stream=s)                           # move the camera in place (also set_vertices(), OmniLight.set_origin())
+    scene.surface_frame(offsets, ids, Surface(normals, uvs, texture), rgba=out)  # smooth, textured (also surface(), interpolate())
 
 This is the path bench.py times (inputs resident in HBM) and the one-process-per-GPU
 band renderer uses; ``runner.render`` is the host-image ml* path.
@@ -28,7 +29,7 @@ import ctypes
 import os
 
 from . import _native
-from ._native import (RTK_MAX_LAYERS, RTM_KEEP_ORDER, RTM_REORDER, RTS_MAX_SAMPLES, SRT_MAX_BATCH, SRT_SCENE_CORNELL, SRT_SCENE_SOUP, SRT_SCENE_TRIANGLE, SRT_TRACE_BVH,
+from ._native import (RTK_MAX_LAYERS, RTM_KEEP_ORDER, RTM_REORDER, RTS_MAX_SAMPLES, RTV_MAX_CHANNELS, SRT_MAX_BATCH, SRT_SCENE_CORNELL, SRT_SCENE_SOUP, SRT_SCENE_TRIANGLE, SRT_TRACE_BVH,
                       SRT_TRACE_CULL, SRT_TRACE_LDS, SRT_TRACE_SCALAR)
 
 SCENE_KINDS = {"triangle": SRT_SCENE_TRIANGLE, "cornell": SRT_SCENE_CORNELL, "soup": SRT_SCENE_SOUP}
@@ -366,6 +367,116 @@ def order_host(vertices, camera):
     return order, normals
 
 
+class Surface:
+    """What a surface is made of (``rtv_surface``, include/srt_surface.h): per-triangle corner
+    normals (triangles, 3, 3), corner uvs (triangles, 3, 2) and a texture (TH, TW, 4), float32, each
+    optional (a texture needs uvs), indexed by the triangle's index in the scene file. wrap
+    "repeat" | "clamp", filter "bilinear" | "nearest"; modulate: the texel times the scene's albedo
+    of the triangle. Device tensors for DeviceScene.surface_frame() / surface(), numpy arrays for
+    surface_host(); the holder keeps them alive and copies nothing."""
+
+    WRAPS = {"repeat": 0, "clamp": _native.RTV_WRAP_CLAMP}
+    FILTERS = {"bilinear": 0, "nearest": _native.RTV_FILTER_NEAREST}
+
+    def __init__(self, normals=None, uvs=None, texture=None, wrap: str = "repeat", filter: str = "bilinear",
+                 modulate: bool = False):
+        if wrap not in self.WRAPS:
+            raise ValueError(f"wrap must be one of {sorted(self.WRAPS)}, got {wrap!r}")
+        if filter not in self.FILTERS:
+            raise ValueError(f"filter must be one of {sorted(self.FILTERS)}, got {filter!r}")
+        if texture is not None and uvs is None:
+            raise ValueError("a texture needs uvs")
+        self.normals, self.uvs, self.texture = normals, uvs, texture
+        self.wrap, self.filter, self.modulate = wrap, filter, bool(modulate)
+
+    @property
+    def flags(self) -> int:
+        return self.WRAPS[self.wrap] | self.FILTERS[self.filter] | (_native.RTV_MODULATE if self.modulate else 0)
+
+    def _struct(self, address):
+        th, tw = (int(self.texture.shape[0]), int(self.texture.shape[1])) if self.texture is not None else (0, 0)
+        return _native.RtvSurface(ctypes.sizeof(_native.RtvSurface), address(self.normals), address(self.uvs),
+                                  address(self.texture), tw, th, self.flags)
+
+
+def _host_elements(positions, ids):
+    import numpy as np
+
+    pos = np.ascontiguousarray(positions, np.float32)
+    idv = np.ascontiguousarray(ids, np.int32)
+    if pos.ndim != 2 or pos.shape[1] != 2:
+        raise ValueError(f"positions must be (count, 2), got {pos.shape}")
+    if idv.shape != (pos.shape[0],):
+        raise ValueError(f"ids must be {(pos.shape[0],)}, got {idv.shape}")
+    return pos, idv
+
+
+def surface_host(path: str, width: int, height: int, positions, ids, surface: Surface):
+    """Vertex attributes on the host (rtvSurfaceHost: the library's canonical math, no device):
+    positions (count, 2) float32, ids (count,) int32 and a Surface of numpy arrays -> (normal
+    (count, 4), albedo (count, 4), rgba (count, 4), uv (count, 2)), float32 numpy arrays."""
+    import numpy as np
+
+    pos, idv = _host_elements(positions, ids)
+    count = pos.shape[0]
+    n = scene_triangles(path)
+    held = {}
+    for name, tail in (("normals", (3, 3)), ("uvs", (3, 2))):
+        buf = getattr(surface, name)
+        if buf is not None:
+            a = np.ascontiguousarray(buf, np.float32)
+            if a.shape not in ((n,) + tail, (n, tail[0] * tail[1])):
+                raise ValueError(f"{name} must be {(n,) + tail}, got {a.shape}")
+            held[name] = a
+    if surface.texture is not None:
+        a = np.ascontiguousarray(surface.texture, np.float32)
+        if a.ndim != 3 or a.shape[2] != 4:
+            raise ValueError(f"texture must be (TH, TW, 4), got {a.shape}")
+        held["texture"] = a
+    host = Surface(held.get("normals"), held.get("uvs"), held.get("texture"), surface.wrap, surface.filter,
+                   surface.modulate)
+    normal = np.empty((count, 4), np.float32)
+    albedo = np.empty((count, 4), np.float32)
+    rgba = np.empty((count, 4), np.float32)
+    uv = np.empty((count, 2), np.float32)
+    s = host._struct(lambda a: 0 if a is None else a.ctypes.data)
+    out = _native.RtvOutputs(ctypes.sizeof(_native.RtvOutputs), normal.ctypes.data, albedo.ctypes.data,
+                             rgba.ctypes.data, uv.ctypes.data)
+    _check(_native.lib().rtvSurfaceHost(os.fsencode(path), width, height, pos.ctypes.data, idv.ctypes.data, count,
+                                        ctypes.byref(s), ctypes.byref(out)))
+    return normal, albedo, rgba, uv
+
+
+def interpolate_host(path: str, width: int, height: int, positions, ids, table):
+    """One corner table interpolated on the host (rtvInterpolateHost): table (triangles, 3, C)
+    float32, 1 <= C <= 4 -> out (count, C) float32."""
+    import numpy as np
+
+    pos, idv = _host_elements(positions, ids)
+    tab = np.ascontiguousarray(table, np.float32)
+    n = scene_triangles(path)
+    if tab.ndim != 3 or tab.shape[:2] != (n, 3) or not 1 <= tab.shape[2] <= RTV_MAX_CHANNELS:
+        raise ValueError(f"table must be ({n}, 3, C) with 1 <= C <= {RTV_MAX_CHANNELS}, got {tab.shape}")
+    out = np.empty((pos.shape[0], tab.shape[2]), np.float32)
+    _check(_native.lib().rtvInterpolateHost(os.fsencode(path), width, height, pos.ctypes.data, idv.ctypes.data,
+                                            pos.shape[0], tab.ctypes.data, tab.shape[2], out.ctypes.data))
+    return out
+
+
+def obj_attributes(path: str):
+    """The corner normals and texture coordinates of a Wavefront OBJ file (rtvObjAttributesHost), row
+    i for triangle i of read_scene(path): (normals (n, 3, 3), uvs (n, 3, 2), have_normals,
+    have_uvs). A corner without `vn` takes its triangle's shading normal, one without `vt` (0, 0)."""
+    import numpy as np
+
+    n = scene_triangles(path)
+    normals = np.empty((n, 3, 3), np.float32)
+    uvs = np.empty((n, 3, 2), np.float32)
+    have = (ctypes.c_int * 2)()
+    _check(_native.lib().rtvObjAttributesHost(os.fsencode(path), normals.ctypes.data, uvs.ctypes.data, have))
+    return normals, uvs, bool(have[0]), bool(have[1])
+
+
 def _ptr(x) -> int:
     if x is None:
         return 0
@@ -663,6 +774,14 @@ class DeviceScene:
         """G-buffer at arbitrary image positions: positions (count, 2) float32 and ids (count,)
         int32 -- query()'s input and output -- -> any of depth (count,), bary (count, 2), normal
         (count, 4), albedo (count, 4), as gbuffer()'s."""
+        count = self._elements(positions, ids)
+        out = self._outputs((("depth", depth, ()), ("bary", bary, (2,)), ("normal", normal, (4,)),
+                             ("albedo", albedo, (4,))), (count,))
+        _check(self._lib.rtgPointsAsync(self.handle, _ptr(positions), _ptr(ids), count, ctypes.byref(out),
+                                        _stream(stream)))
+
+    def _elements(self, positions, ids):
+        """count of a (positions (count, 2) float32, ids (count,) int32) pair, checked as attributes() does."""
         count = None
         for name, buf, tail, dtype in (("positions", positions, (2,), "f32"), ("ids", ids, (), "i32")):
             if hasattr(buf, "shape"):
@@ -674,10 +793,94 @@ class DeviceScene:
             self._check_tensor(name, buf, dtype)
         if count is None:
             raise ValueError("positions must have a shape (count, 2): raw pointers carry no count")
-        out = self._outputs((("depth", depth, ()), ("bary", bary, (2,)), ("normal", normal, (4,)),
-                             ("albedo", albedo, (4,))), (count,))
-        _check(self._lib.rtgPointsAsync(self.handle, _ptr(positions), _ptr(ids), count, ctypes.byref(out),
-                                        _stream(stream)))
+        return count
+
+    def _surface(self, surface, planes, lead):
+        """(rtv_surface, rtv_outputs) of a Surface and the planes normal / albedo / rgba / uv (None:
+        not written), the tables checked against this scene and each plane to be `lead` + its tail."""
+        if not isinstance(surface, Surface):
+            raise ValueError(f"surface must be a Surface, got {type(surface).__name__}")
+        n = self.triangles
+        for name, buf, tail in (("normals", surface.normals, (3, 3)), ("uvs", surface.uvs, (3, 2))):
+            if buf is None:
+                continue
+            flat = (n, tail[0] * tail[1])
+            if hasattr(buf, "shape") and tuple(buf.shape) not in ((n,) + tail, flat):
+                raise ValueError(f"{name} must be {(n,) + tail} or {flat}, got {tuple(buf.shape)}")
+            self._check_tensor(name, buf, "f32")
+        if surface.texture is not None:
+            shape = tuple(surface.texture.shape) if hasattr(surface.texture, "shape") else None
+            if shape is None or len(shape) != 3 or shape[2] != 4:
+                raise ValueError(f"texture must be (TH, TW, 4), got {shape}")
+            self._check_tensor("texture", surface.texture, "f32")
+        out = _native.RtvOutputs(ctypes.sizeof(_native.RtvOutputs), 0, 0, 0, 0)
+        for name, buf, tail in planes:
+            if buf is None:
+                continue
+            if hasattr(buf, "shape") and tuple(buf.shape) != lead + tail:
+                raise ValueError(f"{name} must be {lead + tail}, got {tuple(buf.shape)}")
+            self._check_tensor(name, buf, "f32")
+            setattr(out, name, _ptr(buf))
+        return surface._struct(_ptr), out
+
+    def _table(self, table, out, lead):
+        """channels of a corner table (triangles, 3, C) or (triangles, 3 C) with out `lead` + (C,)."""
+        if not hasattr(out, "shape") or len(out.shape) != len(lead) + 1 or tuple(out.shape[:-1]) != lead:
+            raise ValueError(f"out must be {lead + ('C',)}, got {tuple(getattr(out, 'shape', ()))}")
+        channels = int(out.shape[-1])
+        if not 1 <= channels <= RTV_MAX_CHANNELS:
+            raise ValueError(f"out must have 1 to {RTV_MAX_CHANNELS} channels, got {channels}")
+        want = ((self.triangles, 3, channels), (self.triangles, 3 * channels))
+        if hasattr(table, "shape") and tuple(table.shape) not in want:
+            raise ValueError(f"table must be {want[0]} or {want[1]}, got {tuple(table.shape)}")
+        self._check_tensor("table", table, "f32")
+        self._check_tensor("out", out, "f32")
+        return channels
+
+    def surface_frame(self, offsets, ids, surface, normal=None, albedo=None, rgba=None, uv=None, row_begin: int = 0,
+                      row_count: int | None = None, stream=None):
+        """What the surface looks like at the prepared frame's rows, from hit ids (include/srt_surface.h):
+        offsets (rows, W, 2) float32, ids (rows, W) int32 and a Surface of device tables -> any of
+        normal (rows, W, 4) = (smooth unit normal towards the eye, shading cosine), albedo (rows, W,
+        4) = (textured r, g, b, float(id)), rgba (rows, W, 4) = (albedo.rgb * cosine, float(id)), uv
+        (rows, W, 2), float32 device buffers; a plane left None is not written."""
+        if row_count is None:
+            row_count = self.height - row_begin
+        self._check_buffer("offsets", offsets, row_count, 2, "f32")
+        self._check_buffer("ids", ids, row_count, 0, "i32")
+        s, out = self._surface(surface, (("normal", normal, (4,)), ("albedo", albedo, (4,)), ("rgba", rgba, (4,)),
+                                         ("uv", uv, (2,))), (row_count, self.width))
+        _check(self._lib.rtvSurfaceFrameAsync(self.handle, _ptr(offsets), _ptr(ids), row_begin, row_count,
+                                              ctypes.byref(s), ctypes.byref(out), _stream(stream)))
+
+    def surface(self, positions, ids, surface, normal=None, albedo=None, rgba=None, uv=None, stream=None):
+        """surface_frame() at arbitrary image positions: positions (count, 2) float32 and ids (count,)
+        int32 -- query()'s input and output -- -> any of normal, albedo, rgba (count, 4), uv (count, 2)."""
+        count = self._elements(positions, ids)
+        s, out = self._surface(surface, (("normal", normal, (4,)), ("albedo", albedo, (4,)), ("rgba", rgba, (4,)),
+                                         ("uv", uv, (2,))), (count,))
+        _check(self._lib.rtvSurfacePointsAsync(self.handle, _ptr(positions), _ptr(ids), count, ctypes.byref(s),
+                                               ctypes.byref(out), _stream(stream)))
+
+    def interpolate_frame(self, offsets, ids, table, out, row_begin: int = 0, row_count: int | None = None,
+                          stream=None):
+        """One per-corner table carried to the prepared frame's rows (rtvInterpolateFrameAsync): table
+        (triangles, 3, C) float32, 1 <= C <= 4, -> out (rows, W, C) float32, the three corner values
+        of each pixel's triangle under its perspective-correct weights; 0 where the id is no triangle."""
+        if row_count is None:
+            row_count = self.height - row_begin
+        self._check_buffer("offsets", offsets, row_count, 2, "f32")
+        self._check_buffer("ids", ids, row_count, 0, "i32")
+        channels = self._table(table, out, (row_count, self.width))
+        _check(self._lib.rtvInterpolateFrameAsync(self.handle, _ptr(offsets), _ptr(ids), row_begin, row_count,
+                                                  _ptr(table), channels, _ptr(out), _stream(stream)))
+
+    def interpolate(self, positions, ids, table, out, stream=None):
+        """interpolate_frame() at arbitrary image positions: positions (count, 2), ids (count,) -> out (count, C)."""
+        count = self._elements(positions, ids)
+        channels = self._table(table, out, (count,))
+        _check(self._lib.rtvInterpolatePointsAsync(self.handle, _ptr(positions), _ptr(ids), count, _ptr(table),
+                                                   channels, _ptr(out), _stream(stream)))
 
     def shadow(self, light, offsets, ids, mask, rgba=None, bias: float = 0.0, dim: float = 0.0, row_begin: int = 0,
                row_count: int | None = None, stream=None):
