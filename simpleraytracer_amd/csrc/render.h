@@ -334,6 +334,16 @@ struct CullSetup {
     // kMaxEmptyGroup (read per launch: not part of what is built).
     bool sweep;
     unsigned list_descs, empty_descs, empty_group;
+    // Per tile, non-zero exactly when the plan's descriptors of the tile are statically empty
+    // (kItemEmpty without kItemFull: what a sweep block fills by). Written by LaunchStreamPlan with
+    // every build of the plan. facts_fill (read per launch, like empty_group; ignored without sweep):
+    // the tile-facts launch of a frame stores the misses of the tiles that are empty by this map and
+    // valid in the frame, and the sweep blocks store none: they only trace the invalid ones.
+    unsigned* empty_map;
+    bool facts_fill;
+    // Which of the two facts kernels a launch runs (read per launch; render.hip LaunchSharedStages):
+    // the lean one-wave-per-tile kernel, or the block kernel. facts_fill implies the lean one.
+    bool lean_facts;
 };
 // The empty sweep: with setup.sweep the trace grid is the list descriptors, one block each, and one
 // sweep block per empty_group statically empty descriptors (render.hip TraceCullKernel), instead of

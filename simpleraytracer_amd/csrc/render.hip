@@ -80,7 +80,7 @@ struct TileInfo {
     unsigned usable;    // box within the screen-box range (else the tile streams every record)
 };
 
-// Per-tile facts of one frame on the shared setup (render.h CullSetup; TileInfoKernel<.., true>),
+// Per-tile facts of one frame on the shared setup (render.h CullSetup; TileFactsKernel),
 // 16 B: what a trace block still needs from its own frame's offsets. The tile box is not among
 // them: the shared lists were binned against the analytic box, which contains the tile's rays
 // exactly when every offset of the tile lies in [0, 1] (kFactInRange).
@@ -135,6 +135,7 @@ struct TraceParams {
     const unsigned* __restrict__ large_list;  // ids of records binned to every tile
     const unsigned* __restrict__ range_tag;   // = gen: some sample offset of this frame lies outside [0, 1]
     const CullRecord* __restrict__ stream;    // shared setup's record stream (render.h; TraceCullKernel<.., STREAM>)
+    const unsigned* __restrict__ empty_map;   // shared setup: per tile, non-zero = statically empty (render.h CullSetup)
     unsigned gen;                              // frame number of the scene (never 0)
     unsigned fused;                            // bins from the analytic tile bounds (BinParams::fused)
     unsigned plan_only;  // the work list is the slot's plan (no order launch for this frame): read the bins
@@ -142,6 +143,7 @@ struct TraceParams {
     unsigned list_descs;   // shared setup: the plan's descriptors that are not statically empty (they come first)
     unsigned empty_descs;  // shared setup: its statically empty descriptors (they follow)
     unsigned empty_group;  // shared setup: empty descriptors per sweep block (TraceCullKernel); 0: one block each
+    unsigned facts_fill;   // shared setup, sweep on: the facts launch stores the valid empty tiles' misses (TileFactsKernel)
     unsigned exp;                                // diagnostic build: experiment bits (env SRT_EXP), 0 in the product
     float wf;
     float hf;
@@ -2313,7 +2315,8 @@ __device__ void WaveScanOrdered(unsigned* a, int n, bool reverse, int lane) {
 #endif
 constexpr int kInfoTiles = SRT_INFO_TILES;
 // FACTS: a frame on the shared setup -- the tile's TileFacts (with its own in-range flag) into
-// p.tile_facts instead of the TileInfo, and no frame-wide range tag.
+// p.tile_facts instead of the TileInfo, and no frame-wide range tag. One of the shared path's two
+// facts kernels: the one for launches whose frames each bring their own offsets (LaunchSharedStages).
 template <bool FACTS>
 __device__ __forceinline__ void TileInfoBlock(const BinParams& p, int bx, int by) {
     constexpr int kWaves = kBinThreads / kWave;
@@ -3002,6 +3005,9 @@ __global__ __launch_bounds__(kBinThreads) void PrepareBinKernel(const Frames bat
 // descriptors and writes its share of the end marks with no global atomic, and the trace blocks
 // reset the bin counts they consume. (Per-bucket global cursors plus a last-block reset, this
 // kernel's first multi-block form: 11.0 us one frame in flight, three dependent atomic round trips.)
+// On the shared setup the kItemEmpty flag it writes is also what the setup's empty map is made of
+// (EmptyMapKernel, after StreamPlanKernel has ordered the plan): one entry per tile, read by the
+// frames' facts launch when it fills the empty tiles itself (TileFactsKernel, SRT_EMPTY_FILL=facts).
 constexpr int kOrderBlock = 256;
 constexpr int kOrderTilesPerThread = 8;  // tiles' loads in flight per thread (one pass at 1080p: 2040 tiles)
 #ifndef SRT_ORDER_COPIES
@@ -3289,27 +3295,135 @@ struct TraceRecords<true> {
 // every record as on the indexed path. No list entry is read.
 // The miss value of every pixel of one tile part (kBlockRows rows from band row row0 of tile column
 // tx), stored by the block's 256 threads: wave w rows row0 + w R .. + R - 1, lane = column.
-__device__ __forceinline__ void StoreMissPart(const TraceParams& p, int tx, int row0, int lane, int wave) {
-    constexpr int R = kCullR;
+// StoreMissRows: one wave's share, ROWS rows from band row y0 (lane = column); the facts launch's
+// fill (TileFactsKernel) stores a whole tile with it, kTileRows rows by one wave: the same bytes.
+template <int ROWS>
+__device__ __forceinline__ void StoreMissRows(const TraceParams& p, int tx, int y0, int lane) {
     const int xe = tx * kWave + lane;
     if (p.out_packed != nullptr) {
 #pragma unroll
-        for (int r = 0; r < R; ++r) {
-            const int y = row0 + wave * R + r;
+        for (int r = 0; r < ROWS; ++r) {
+            const int y = y0 + r;
             if (y < p.row_count) {
                 StorePackedIds(p, tx, xe, y, -1);
             }
         }
     } else if (xe < p.width) {
 #pragma unroll
-        for (int r = 0; r < R; ++r) {
-            const int y = row0 + wave * R + r;
+        for (int r = 0; r < ROWS; ++r) {
+            const int y = y0 + r;
             if (y < p.row_count) {
                 StorePixel(p, xe, y, 0.f, 0.f, -1);
             }
         }
     }
 }
+__device__ __forceinline__ void StoreMissPart(const TraceParams& p, int tx, int row0, int lane, int wave) {
+    StoreMissRows<kCullR>(p, tx, row0 + wave * kCullR, lane);
+}
+// The offset entry of a tile in the packed ids (render.h PackedIds): the tile's sample offset when
+// every ray of the tile has it, else NaNs. One lane stores it, once per tile.
+__device__ __forceinline__ void StorePackedTileOffset(const TraceParams& p, int tx, int ty, bool regular, float ox,
+                                                      float oy) {
+    const float qn = __builtin_nanf("");
+    *reinterpret_cast<float2*>(PackedTileOffset(p.out_packed, p, ty * kTileRows, tx)) =
+        regular ? make_float2(ox, oy) : make_float2(qn, qn);
+}
+
+// The tile facts of a frame on the shared setup (LaunchSharedStages), and with p.facts_fill the fill
+// of its statically empty tiles. One wave per tile, 64-thread blocks, at most 32 VGPRs and no LDS:
+// six trace blocks per CU (80 VGPRs a lane, 6 x 80 = 480 of a SIMD's 512) leave 32 registers and two
+// wave slots per SIMD, so these waves can be resident beside the other queue's trace instead of
+// waiting for whole block slots. The TileFacts are TileInfoBlock<true>'s, bit
+// for bit: the same positions (clamped rows and columns: duplicates of real pixels), the division
+// after the reduction, NaN dropped by fminf / fmaxf; min and max do not depend on the order. A tile
+// is 8 KB of offsets, 32 registers a lane at once, so the loads go in kRounds = 4 rounds of 8
+// registers, a loop the compiler must not unroll (unrolled, it issues every round's loads first: 47
+// VGPRs; two rounds: 34; four: 26. An amdgpu_num_vgpr(32) bound is dropped by the compiler here, as
+// less than what 8 waves per SIMD can use, so the loop is what bounds the registers).
+// The fill: a tile the setup's map calls statically empty (StreamPlanKernel's descriptors:
+// kItemEmpty without kItemFull) and whose facts are valid in this frame (kFactUsable |
+// kFactInRange) gets the miss value of every pixel here, the stores its sweep block made
+// (StoreMissRows, the tile's packed offset entry); the sweep block then skips it (TraceCullKernel).
+// The map entry is a scalar load issued with the first offsets, so the fill waits for nothing new.
+template <class Frames>
+__global__ __launch_bounds__(kWave) void TileFactsKernel(const Frames batch) {
+    const TraceParams& p = batch[blockIdx.z];
+    const int lane = threadIdx.x;
+    const int bx = blockIdx.x, ty = blockIdx.y;  // (the grid is the frame's tiles: x0 < width, y0 < row_count)
+    const unsigned tile = static_cast<unsigned>(ty) * static_cast<unsigned>(p.tiles_x) + static_cast<unsigned>(bx);
+    const int x0 = bx * kWave, y0 = ty * kTileRows;
+    const int width = p.width, last_row = p.row_count - 1;
+    const float2* __restrict__ offsets = p.offsets;
+    const unsigned empty = p.facts_fill != 0u ? p.empty_map[tile] : 0u;
+    const float2 o0 = offsets[static_cast<size_t>(y0) * width + x0];
+    Box box{__builtin_inff(), -__builtin_inff(), __builtin_inff(), -__builtin_inff()};  // of the sums
+    bool regular = true, in_range = true;
+    auto take = [&](int x, int yy, float2 o) {
+        const float sx = static_cast<float>(x) + o.x;
+        const float sy = static_cast<float>(FrameRow(p.row_begin, p.row_interleave, yy)) + o.y;
+        box = Box{fminf(box.xlo, sx), fmaxf(box.xhi, sx), fminf(box.ylo, sy), fmaxf(box.yhi, sy)};
+        regular = regular && __float_as_uint(o.x) == __float_as_uint(o0.x) && __float_as_uint(o.y) == __float_as_uint(o0.y);
+        in_range = in_range && o.x >= 0.f && o.x <= 1.f && o.y >= 0.f && o.y <= 1.f;  // NaN: false
+    };
+    constexpr int kRounds = 4;
+    if (x0 + kWave <= width && (width & 1) == 0 && (reinterpret_cast<uintptr_t>(offsets) & 15u) == 0) {
+        // Whole-width tile, 16-B aligned rows: lane = a column pair of one of two rows, 16 B per load.
+        constexpr int kPer = kTileRows / 2 / kRounds;
+        const int xa = x0 + 2 * (lane & (kWave / 2 - 1)), half = lane / (kWave / 2);
+#pragma nounroll
+        for (int r = 0; r < kRounds; ++r) {
+            float4 o[kPer];
+#pragma unroll
+            for (int k = 0; k < kPer; ++k) {
+                const int yy = min(y0 + (r * kPer + k) * 2 + half, last_row);
+                o[k] = *reinterpret_cast<const float4*>(offsets + static_cast<size_t>(yy) * width + xa);
+            }
+#pragma unroll
+            for (int k = 0; k < kPer; ++k) {
+                const int yy = min(y0 + (r * kPer + k) * 2 + half, last_row);
+                take(xa, yy, make_float2(o[k].x, o[k].y));
+                take(xa + 1, yy, make_float2(o[k].z, o[k].w));
+            }
+        }
+    } else {  // a tile at the frame's right edge, an odd width or an 8-B aligned pointer: 8-B loads, clamped columns
+        constexpr int kPer = kTileRows / kRounds;
+        const int xx = min(x0 + lane, width - 1);
+#pragma nounroll
+        for (int r = 0; r < kRounds; ++r) {
+            float2 o[kPer];
+#pragma unroll
+            for (int k = 0; k < kPer; ++k) {
+                o[k] = offsets[static_cast<size_t>(min(y0 + r * kPer + k, last_row)) * width + xx];
+            }
+#pragma unroll
+            for (int k = 0; k < kPer; ++k) {
+                take(xx, min(y0 + r * kPer + k, last_row), o[k]);
+            }
+        }
+    }
+    box = WaveReduceBox(box);
+    const bool tile_regular = __all(regular), tile_in_range = __all(in_range);
+    box = Box{box.xlo / p.wf, box.xhi / p.wf, box.ylo / p.hf, box.yhi / p.hf};  // the rays' (fx, fy) box
+    const unsigned flags = (tile_regular ? kFactRegular : 0u) | (ScreenBoxUsable(box) ? kFactUsable : 0u) |
+                           (tile_in_range ? kFactInRange : 0u);
+    if (lane == 0) {
+        TileFacts tf;
+        tf.ox = o0.x;
+        tf.oy = o0.y;
+        tf.flags = flags;
+        tf.pad = 0u;
+        const_cast<TileFacts*>(p.tile_facts)[tile] = tf;  // (the frame slot's own: no trace of it is running)
+    }
+    constexpr unsigned kValid = kFactUsable | kFactInRange;
+    if (empty != 0u && (flags & kValid) == kValid) {  // (wave-uniform: a scalar load, ballots, a reduced box)
+        if (p.out_packed != nullptr && lane == 0) {
+            StorePackedTileOffset(p, bx, ty, tile_regular, o0.x, o0.y);
+        }
+        StoreMissRows<kTileRows>(p, bx, y0, lane);
+    }
+}
+static_assert(sizeof(FrameArgs<TraceParams>) < 4096, "kMaxBatch frames' TraceParams as kernel arguments: under 4 KB");
 
 template <class Frames, bool RC = false, bool SHARED = false, bool STREAM = false>
 __global__ __launch_bounds__(kCullThreads, SRT_TRACE_OCC) void TraceCullKernel(const Frames batch) {
@@ -3390,7 +3504,10 @@ __global__ __launch_bounds__(kCullThreads, SRT_TRACE_OCC) void TraceCullKernel(c
                     my_oy = tf.oy;
                 }
             }
-            const unsigned long long filled = __ballot(fill);
+            // p.facts_fill: the frame's facts launch has stored these tiles' misses from the same two
+            // conditions (TileFactsKernel: the setup's empty map, the tile's facts), so the block
+            // stores nothing for them and only traces `todo`: every pixel keeps exactly one writer.
+            const unsigned long long filled = p.facts_fill != 0u ? 0ull : __ballot(fill);
             todo = __ballot(static_cast<unsigned>(s_lane) < cnt && !fill);
             swept = static_cast<unsigned>(__popcll(filled));
             d_traced = static_cast<unsigned>(__popcll(todo));
@@ -3409,9 +3526,7 @@ __global__ __launch_bounds__(kCullThreads, SRT_TRACE_OCC) void TraceCullKernel(c
                     const float fox = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(my_ox), k));
                     const float foy = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(my_oy), k));
                     if (threadIdx.x == 0) {
-                        const float qn = __builtin_nanf("");
-                        *reinterpret_cast<float2*>(PackedTileOffset(p.out_packed, p, ty * kTileRows, tx)) =
-                            (ff & kFactRegular) != 0u ? make_float2(fox, foy) : make_float2(qn, qn);
+                        StorePackedTileOffset(p, tx, ty, (ff & kFactRegular) != 0u, fox, foy);
                     }
                 }
                 StoreMissPart(p, tx, row0, s_lane, s_wave);
@@ -3569,9 +3684,7 @@ __global__ __launch_bounds__(kCullThreads, SRT_TRACE_OCC) void TraceCullKernel(c
     if (p.out_packed != nullptr && threadIdx.x == 0 && chunk == 0u && item % kParts == 0u) {
         // The tile's sample offset in the packed ids when every ray of the tile has it (the deferred
         // shading then reads no per-pixel offsets for the tile), else NaNs (render.h PackedIds).
-        const float qn = __builtin_nanf("");
-        *reinterpret_cast<float2*>(PackedTileOffset(p.out_packed, p, ty * kTileRows, tx)) =
-            (flags & kItemRegular) != 0u ? make_float2(ox, oy) : make_float2(qn, qn);
+        StorePackedTileOffset(p, tx, ty, (flags & kItemRegular) != 0u, ox, oy);
     }
     const int tid = threadIdx.x;
     const int lane = tid & (kWave - 1);
@@ -5556,7 +5669,8 @@ hipError_t LaunchCullFrames(const CullFrame* frames, std::size_t count, std::uin
 
 namespace {
 struct SetupSizes {
-    std::size_t counts, range_tag, work_count, stream_count, info, screen_boxes, qboxes, cull, lists, large, work, work_tmp;
+    std::size_t counts, range_tag, work_count, stream_count, info, screen_boxes, qboxes, cull, lists, large, work, work_tmp,
+        empty_map;
 };
 SetupSizes CullSetupSizes(std::uint64_t n, std::size_t width, std::size_t height, unsigned descs) {
     const std::size_t tiles = CullTiles(width, height), n_pad = PaddedTriangleCount(n);
@@ -5574,6 +5688,7 @@ SetupSizes CullSetupSizes(std::uint64_t n, std::size_t width, std::size_t height
     z.large = al(n_pad * 4);
     z.work = al(static_cast<std::size_t>(descs) * 2 * sizeof(uint4));
     z.work_tmp = z.work;  // StreamPlanKernel's partition
+    z.empty_map = al(tiles * sizeof(unsigned));
     return z;
 }
 }  // namespace
@@ -5581,7 +5696,7 @@ SetupSizes CullSetupSizes(std::uint64_t n, std::size_t width, std::size_t height
 std::size_t CullSetupBytes(std::uint64_t n, std::size_t width, std::size_t height, unsigned descs) {
     const SetupSizes z = CullSetupSizes(n, width, height, descs);
     return z.counts + z.range_tag + z.work_count + z.stream_count + z.info + z.screen_boxes + z.qboxes + z.cull +
-           z.lists + z.large + z.work + z.work_tmp;
+           z.lists + z.large + z.work + z.work_tmp + z.empty_map;
 }
 
 CullSetup CullSetupLayout(void* base, std::uint64_t n, std::size_t width, std::size_t height, unsigned descs,
@@ -5609,6 +5724,7 @@ CullSetup CullSetupLayout(void* base, std::uint64_t n, std::size_t width, std::s
     s.large_list = reinterpret_cast<unsigned*>(take(z.large));
     s.work = take(z.work);
     s.work_tmp = take(z.work_tmp);
+    s.empty_map = reinterpret_cast<unsigned*>(take(z.empty_map));
     s.tiles = CullTiles(width, height);
     s.capacity = CullBinCapacity(n, s.tiles);
     s.descs = descs;
@@ -5809,6 +5925,23 @@ __global__ __launch_bounds__(kPlanBlock) void StreamPlanKernel(uint4* work, uint
     }
 }
 
+// The setup's empty map (render.h CullSetup::empty_map), from the finished plan: one thread per
+// descriptor marks its tile when the descriptor is statically empty -- kItemEmpty without kItemFull,
+// the condition a sweep block fills by. A tile's descriptors share their flags and an empty part is
+// never split (StreamPlanKernel), so one entry per tile says it for all of them; the map was zeroed
+// on the same stream before.
+__global__ __launch_bounds__(kPackBlock) void EmptyMapKernel(const uint4* __restrict__ work, unsigned descs,
+                                                             unsigned* __restrict__ map, unsigned tiles) {
+    const unsigned d = blockIdx.x * kPackBlock + threadIdx.x;
+    if (d >= descs) {
+        return;
+    }
+    const uint4 w0 = work[2 * d];
+    if (w0.x != kWorkEnd && (w0.w & (kItemFull | kItemEmpty)) == kItemEmpty && w0.x / kParts < tiles) {
+        map[w0.x / kParts] = 1u;
+    }
+}
+
 // Block d copies descriptor d's records (a tile's first part only) into its stream range; the pad
 // record of an odd range is a copy of the range's first (no trace reads it).
 __global__ __launch_bounds__(kPackBlock) void PackStreamKernel(const uint4* __restrict__ work,
@@ -5841,6 +5974,16 @@ unsigned SharedTraceBlocks(unsigned descs, unsigned list_descs, unsigned empty_d
 hipError_t LaunchStreamPlan(const CullSetup& s, hipStream_t stream) {
     hipLaunchKernelGGL(StreamPlanKernel, dim3(1), dim3(kPlanBlock), 0, stream, static_cast<uint4*>(s.work),
                        static_cast<uint4*>(s.work_tmp), s.descs, s.sweep, s.stream_count);
+    // The empty map of the plan as it now stands: with every build, stream or not, sweep or not.
+    const unsigned tiles = static_cast<unsigned>(s.tiles);
+    const hipError_t zeroed = hipMemsetAsync(s.empty_map, 0, static_cast<std::size_t>(tiles) * sizeof(unsigned), stream);
+    if (zeroed != hipSuccess) {
+        return zeroed;
+    }
+    if (s.descs != 0u) {
+        hipLaunchKernelGGL(EmptyMapKernel, dim3((s.descs + kPackBlock - 1) / kPackBlock), dim3(kPackBlock), 0, stream,
+                           static_cast<const uint4*>(s.work), s.descs, s.empty_map, tiles);
+    }
     return hipGetLastError();
 }
 
@@ -5855,13 +5998,23 @@ hipError_t LaunchStreamPack(const CullSetup& s, void* records, hipStream_t strea
 }
 
 namespace {
-// The two launches of a frame set on the shared setup: tile facts, trace.
+// The two launches of a frame set on the shared setup: tile facts, trace. The facts kernel is one of
+// two that write the same bits. lean: TileFactsKernel, one wave per tile on the frames' TraceParams
+// (with TraceParams::facts_fill also the fill of the statically empty tiles). It fits beside the
+// other queue's trace and is faster where the launch's offsets are reused from cache. Otherwise
+// TileInfoKernel<.., true>, a 256-thread block per two tiles on the frames' BinParams, which has the
+// whole tile's loads in flight at once and is what a launch reading its offsets from HBM wants
+// (profiles/facts_fill/README.md: the rotating-inputs and single-frame legs decided).
 template <class TB, class BB>
-void LaunchSharedStages(const TB& tb, const BB& bb, unsigned z, unsigned gx, unsigned gy, bool recompute,
+void LaunchSharedStages(const TB& tb, const BB& bb, bool lean, unsigned z, unsigned gx, unsigned gy, bool recompute,
                         bool streamed, unsigned descs, hipStream_t stream, const StageEvents& ev) {
     // (descs: the trace grid -- the plan's room, or SharedTraceBlocks with the empty sweep)
-    Launch(TileInfoKernel<BB, true>, dim3(gx, (gy + kInfoTiles - 1) / kInfoTiles, z), dim3(kBinThreads), stream,
-           ev.bin_begin, ev.bin_end, bb);
+    if (lean) {
+        Launch(TileFactsKernel<TB>, dim3(gx, gy, z), dim3(kWave), stream, ev.bin_begin, ev.bin_end, tb);
+    } else {
+        Launch(TileInfoKernel<BB, true>, dim3(gx, (gy + kInfoTiles - 1) / kInfoTiles, z), dim3(kBinThreads), stream,
+               ev.bin_begin, ev.bin_end, bb);
+    }
     if (recompute) {
         Launch(TraceCullKernel<TB, true, true>, dim3(descs, 1, z), dim3(kWave * kCullWaves), stream, ev.begin, ev.end, tb);
     } else if (streamed) {
@@ -5904,6 +6057,8 @@ hipError_t LaunchSharedCullFrames(const CullFrame* frames, std::size_t count, co
     if (use_table) {
         std::memset(host + lay.prep, 0, lay.bin - lay.prep);  // (no record pass: uploaded, never read)
     }
+    // The facts fill is the lean kernel's; without it the caller's choice (CullSetup::lean_facts).
+    const bool lean = setup.lean_facts || (group != 0u && setup.facts_fill);
     const EdgeLayout e = SetupRecords(setup);
     for (std::size_t i = 0; i < count; ++i) {
         const CullFrame& f = frames[i];
@@ -5931,7 +6086,9 @@ hipError_t LaunchSharedCullFrames(const CullFrame* frames, std::size_t count, co
         p.list_descs = setup.list_descs;
         p.empty_descs = setup.empty_descs;
         p.empty_group = group;
-        BinParams& b = bp[i];
+        p.empty_map = setup.empty_map;
+        p.facts_fill = group != 0u && setup.facts_fill ? 1u : 0u;  // (ignored with the sweep off)
+        BinParams& b = bp[i];  // (the block facts kernel's view of the frame)
         b = BinParams{};
         b.offsets = p.offsets;
         b.tile_facts = static_cast<TileFacts*>(f.bins->tile_info);
@@ -5955,7 +6112,7 @@ hipError_t LaunchSharedCullFrames(const CullFrame* frames, std::size_t count, co
     blocks = group != 0u ? std::max(setup.list_descs, 1u) : blocks;
 #endif
     if (!use_table) {
-        LaunchSharedStages(tb, bb, z, gx, gy, setup.recompute, streamed, blocks, stream, ev);
+        LaunchSharedStages(tb, bb, lean, z, gx, gy, setup.recompute, streamed, blocks, stream, ev);
         return hipGetLastError();
     }
     if (table->host_device != nullptr) {
@@ -5977,7 +6134,7 @@ hipError_t LaunchSharedCullFrames(const CullFrame* frames, std::size_t count, co
     unsigned char* dev = static_cast<unsigned char*>(table->device);
     const BinTable bt{(ConstantPtr<BinParams>)(dev + lay.bin)};
     const TraceTable tt{(ConstantPtr<TraceParams>)(dev + lay.trace)};
-    LaunchSharedStages(tt, bt, z, gx, gy, setup.recompute, streamed, blocks, stream, ev);
+    LaunchSharedStages(tt, bt, lean, z, gx, gy, setup.recompute, streamed, blocks, stream, ev);
     return hipGetLastError();
 }
 

@@ -866,6 +866,34 @@ unsigned EmptyGroupFromEnv() {
     return static_cast<unsigned>(v);
 }
 
+// SRT_EMPTY_FILL = sweep (default) | facts, read per call: who stores the misses of the statically
+// empty tiles whose offsets are valid in the frame -- the trace's sweep blocks, or the frame's
+// tile-facts launch (render.h CullSetup::facts_fill; measured slower on the headline, kept for
+// measurements: profiles/facts_fill/README.md). A launch parameter, not part of what is built;
+// without the sweep (SRT_EMPTY_SWEEP=0) one block per empty descriptor fills, whatever this says.
+bool EmptyFillFromEnv() {
+    const char* e = std::getenv("SRT_EMPTY_FILL");
+    const std::string v = e == nullptr || *e == '\0' ? "sweep" : e;
+    if (v != "facts" && v != "sweep") {
+        throw std::runtime_error("SRT_EMPTY_FILL must be facts or sweep, got '" + v + "'");
+    }
+    return v == "facts";
+}
+
+// SRT_FACTS_KERNEL = auto (default) | lean | block, read per call: the facts kernel of a shared-setup
+// launch (render.h CullSetup::lean_facts). auto: lean when some frames of the launch share an offsets
+// buffer -- a sample pattern reused across frames stays in cache, where the lean kernel beside the
+// other queue's trace is the faster one --, block when every frame brings its own (a single frame,
+// rotating inputs: read from memory once, where the block kernel is). -1: auto.
+int FactsKernelFromEnv() {
+    const char* e = std::getenv("SRT_FACTS_KERNEL");
+    const std::string v = e == nullptr || *e == '\0' ? "auto" : e;
+    if (v != "auto" && v != "lean" && v != "block") {
+        throw std::runtime_error("SRT_FACTS_KERNEL must be auto, lean or block, got '" + v + "'");
+    }
+    return v == "auto" ? -1 : v == "lean" ? 1 : 0;
+}
+
 // SRT_TRACE_STREAM_CAP (tests only): the longest record stream, in records, instead of
 // kStreamCapRecords -- forces the indexed fallback at small sizes, as SRT_CULL_BIN_CAP forces list overflow.
 std::size_t StreamCapFromEnv() {
@@ -924,10 +952,12 @@ void DeviceScene::LogSetupStats() const {
     }
     std::fprintf(stderr,
                  "srt setup: scene %p builds %llu shared_frames %llu per_frame_frames %llu stream_frames %llu "
-                 "stream_records %llu empty_descs %llu sweep_blocks %llu\n",
+                 "stream_records %llu empty_descs %llu sweep_blocks %llu facts_fill_frames %llu "
+                 "lean_facts_frames %llu\n",
                  static_cast<const void*>(this), m_setup_stats.builds, m_setup_stats.shared_frames,
                  m_setup_stats.per_frame_frames, m_setup_stats.stream_frames, m_setup_stats.stream_records,
-                 m_setup_stats.empty_descs, m_setup_stats.sweep_blocks);
+                 m_setup_stats.empty_descs, m_setup_stats.sweep_blocks, m_setup_stats.facts_fill_frames,
+                 m_setup_stats.lean_facts_frames);
     std::fflush(stderr);
 }
 
@@ -953,7 +983,17 @@ void DeviceScene::TraceShared(const float* const* d_offsets, float* const* d_rgb
         cf[f].band = BandArgs{d_offsets[f], d_rgba != nullptr ? d_rgba[f] : nullptr, m_width, m_height, 0, m_height,
                               d_ids != nullptr ? d_ids[f] : nullptr, 1, id_planes, rgba_frame_rows};
     }
-    const CullSetup setup = EnsureSetup(bins[0].descs, stream);
+    CullSetup setup = EnsureSetup(bins[0].descs, stream);
+    {
+        const int want = FactsKernelFromEnv();
+        bool reused = false;  // some frames of the launch read the same offsets buffer
+        for (std::size_t f = 1; f < frames && !reused; ++f) {
+            for (std::size_t g = 0; g < f && !reused; ++g) {
+                reused = d_offsets[f] == d_offsets[g];
+            }
+        }
+        setup.lean_facts = want < 0 ? reused : want == 1;
+    }
     // (the last trace's grid: sweep blocks per frame, 0 with the sweep off)
     m_setup_stats.sweep_blocks =
         setup.sweep ? SharedTraceBlocks(setup.descs, setup.list_descs, setup.empty_descs, setup.empty_group) - setup.list_descs
@@ -971,6 +1011,8 @@ void DeviceScene::TraceShared(const float* const* d_offsets, float* const* d_rgb
     }
     m_setup_stats.shared_frames += frames;
     m_setup_stats.stream_frames += setup.stream != nullptr ? frames : 0;
+    m_setup_stats.facts_fill_frames += setup.sweep && setup.facts_fill ? frames : 0;
+    m_setup_stats.lean_facts_frames += setup.lean_facts || (setup.sweep && setup.facts_fill) ? frames : 0;
     LogSetupStats();
     RecordOrder(stream);
 }
@@ -998,6 +1040,7 @@ CullSetup DeviceScene::EnsureSetup(unsigned descs, hipStream_t stream) const {
     const bool want_stream = TraceStreamFromEnv() && !recompute;
     setup.sweep = EmptySweepFromEnv();
     setup.empty_group = EmptyGroupFromEnv();
+    setup.facts_fill = EmptyFillFromEnv();
     const SetupKey key{m_width,         m_height,    setup.capacity, setup.descs,
                        setup.min_chunk, setup.recompute, want_stream,    want_stream ? StreamCapFromEnv() : 0,
                        setup.sweep};

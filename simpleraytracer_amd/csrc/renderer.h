@@ -252,6 +252,12 @@ public:
         unsigned long long stream_records = 0;
         unsigned long long empty_descs = 0;   // statically empty descriptors of the standing setup's plan
         unsigned long long sweep_blocks = 0;  // sweep blocks per frame of the last shared trace (0: sweep off)
+        // Of shared_frames, those whose tile-facts launch was asked to fill the statically empty
+        // tiles (env SRT_EMPTY_FILL=facts, with the sweep on; the default is sweep: 0).
+        unsigned long long facts_fill_frames = 0;
+        // Of shared_frames, those whose facts launch was the lean kernel (env SRT_FACTS_KERNEL; auto:
+        // launches in which frames share an offsets buffer).
+        unsigned long long lean_facts_frames = 0;
     };
     SetupStats setup_stats() const { return m_setup_stats; }
 
