@@ -21,7 +21,7 @@ OBJS := $(BUILD)/render.o $(BUILD)/spatial.o $(BUILD)/renderer.o $(BUILD)/engine
 
 HEADERS := $(wildcard $(CSRC)/*.h) include/model_runner.h include/srt_render.h include/srt_query.h include/srt_gbuffer.h \
            include/srt_samples.h include/srt_light.h include/srt_layers.h include/srt_omni.h \
-           include/srt_lighting.h include/srt_motion.h include/srt_surface.h
+           include/srt_lighting.h include/srt_motion.h include/srt_surface.h include/srt_material.h
 
 # Diagnostic build (per-block cull phase counters, srtDiagRead): never the product library.
 DIAG_BUILD := build/diag

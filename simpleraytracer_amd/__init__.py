@@ -10,11 +10,11 @@ Layers:
 """
 from .device import (MAX_BATCH, DeviceScene, OmniLight, SrtError, Surface, convert_scene, read_scene, scene_frame,  # noqa: F401
                      scene_triangles, write_scene)
-from .lighting import PointLight, PointLightHost, SpotLight, SpotLightHost  # noqa: F401
+from .lighting import Material, PointLight, PointLightHost, SpotLight, SpotLightHost  # noqa: F401
 from .runner import Context, Image, MLError, Model, default_offsets, render  # noqa: F401
 
 __all__ = [
     "Context", "Image", "Model", "MLError", "render", "default_offsets",
     "DeviceScene", "OmniLight", "SrtError", "Surface", "MAX_BATCH", "write_scene", "scene_triangles", "scene_frame", "read_scene", "convert_scene",
-    "SpotLight", "PointLight", "SpotLightHost", "PointLightHost",
+    "SpotLight", "PointLight", "SpotLightHost", "PointLightHost", "Material",
 ]

@@ -3,6 +3,7 @@
 #include "gbuffer_math.h"
 #include "layers_math.h"
 #include "lighting_math.h"
+#include "material_math.h"
 #include "omni_math.h"
 #include "samples_math.h"
 #include "screen_box.h"
@@ -267,6 +268,71 @@ void HostGBuffer(const Scene& scene, std::size_t width, std::size_t height, cons
     });
 }
 
+namespace {
+
+void CheckSurfaceTables(const HostSurfaceTables& s) {
+    if ((s.flags & ~kSurfaceFlags) != 0u) {
+        throw std::runtime_error("Host surface: unknown flags");
+    }
+    if (s.texture != nullptr && (s.uvs == nullptr || s.tex_width < 1 || s.tex_width > kSurfaceMaxTexture ||
+                                 s.tex_height < 1 || s.tex_height > kSurfaceMaxTexture)) {
+        throw std::runtime_error("Host surface: a texture needs uvs and 1 to 16384 texels per side");
+    }
+}
+
+// What the surface of triangle i looks like at (fx, fy), r being its record under frame f: the normal
+// plane on[4], the albedo plane's colour oa[3] and the uv (surface_math.h; HostSurface, HostLitSurface).
+void SurfaceLook(const Scene& scene, const Frame& f, const HostSurfaceTables& s, std::size_t i, const Rec& r, float fx,
+                 float fy, float on[4], float oa[3], float ouv[2]) {
+    const bool clamp = (s.flags & kSurfaceWrapClamp) != 0u, nearest = (s.flags & kSurfaceFilterNearest) != 0u;
+    const bool modulate = (s.flags & kSurfaceModulate) != 0u;
+    const int tw = static_cast<int>(s.tex_width), th = static_cast<int>(s.tex_height);
+    const SurfaceWeights bw = SurfaceBary(r.c, fx, fy);
+    const float* a = scene.albedo.data() + 3 * i;
+    if (s.normals != nullptr) {
+        const float* cn = s.normals + 9 * i;
+        const SurfaceNormal sn = SurfaceSmoothNormal(SurfaceMix(bw, cn[0], cn[3], cn[6]), SurfaceMix(bw, cn[1], cn[4], cn[7]),
+                                                     SurfaceMix(bw, cn[2], cn[5], cn[8]), f.base, f.du, f.dv, fx, fy);
+        const float v[4] = {sn.x, sn.y, sn.z, sn.cosv};
+        std::copy(v, v + 4, on);
+    } else {
+        const GBufferTexel g = GBufferHit(r.c, r.vol, f.base, f.du, f.dv, fx, fy, static_cast<int>(i), r.n[0], r.n[1],
+                                          r.n[2], r.n[3], a[0], a[1], a[2]);
+        const float v[4] = {g.nx, g.ny, g.nz, g.cosv};
+        std::copy(v, v + 4, on);
+    }
+    ouv[0] = ouv[1] = 0.f;
+    if (s.uvs != nullptr) {
+        const float* ct = s.uvs + 6 * i;
+        ouv[0] = SurfaceMix(bw, ct[0], ct[2], ct[4]);
+        ouv[1] = SurfaceMix(bw, ct[1], ct[3], ct[5]);
+    }
+    std::copy(a, a + 3, oa);
+    if (s.texture != nullptr) {
+        float tex[3];
+        if (nearest) {
+            const int ti = SurfaceNearest(SurfaceWrap(ouv[0], clamp), tw);
+            const int tj = SurfaceNearest(SurfaceWrap(ouv[1], clamp), th);
+            const float* t = s.texture + 4 * (static_cast<std::size_t>(tj) * s.tex_width + static_cast<std::size_t>(ti));
+            std::copy(t, t + 3, tex);
+        } else {
+            const SurfaceTaps sx = SurfaceBilinear(SurfaceWrap(ouv[0], clamp), tw, clamp);
+            const SurfaceTaps sy = SurfaceBilinear(SurfaceWrap(ouv[1], clamp), th, clamp);
+            const float* top = s.texture + 4 * static_cast<std::size_t>(sy.i0) * s.tex_width;
+            const float* bot = s.texture + 4 * static_cast<std::size_t>(sy.i1) * s.tex_width;
+            for (int c = 0; c < 3; ++c) {
+                tex[c] = SurfaceLerp(SurfaceLerp(top[4 * sx.i0 + c], top[4 * sx.i1 + c], sx.a),
+                                     SurfaceLerp(bot[4 * sx.i0 + c], bot[4 * sx.i1 + c], sx.a), sy.a);
+            }
+        }
+        for (int c = 0; c < 3; ++c) {
+            oa[c] = modulate ? tex[c] * a[c] : tex[c];
+        }
+    }
+}
+
+}  // namespace
+
 void HostSurface(const Scene& scene, std::size_t width, std::size_t height, const float* positions, const int* ids,
                  std::size_t count, const float* normals, const float* uvs, const float* texture,
                  std::size_t tex_width, std::size_t tex_height, unsigned flags, float* normal, float* albedo,
@@ -274,21 +340,13 @@ void HostSurface(const Scene& scene, std::size_t width, std::size_t height, cons
     if (width == 0 || height == 0) {
         throw std::runtime_error("Host surface: frame dimensions must be non-zero");
     }
-    if ((flags & ~kSurfaceFlags) != 0u) {
-        throw std::runtime_error("Host surface: unknown flags");
-    }
-    if (texture != nullptr && (uvs == nullptr || tex_width < 1 || tex_width > kSurfaceMaxTexture || tex_height < 1 ||
-                               tex_height > kSurfaceMaxTexture)) {
-        throw std::runtime_error("Host surface: a texture needs uvs and 1 to 16384 texels per side");
-    }
+    const HostSurfaceTables tables{normals, uvs, texture, tex_width, tex_height, flags};
+    CheckSurfaceTables(tables);
     if (normal == nullptr && albedo == nullptr && rgba == nullptr && uv == nullptr) {
         return;  // (no plane: nothing is read either)
     }
     const Frame f = MakeFrame(scene.camera, width, height);
     const std::size_t n = scene.triangle_count();
-    const bool clamp = (flags & kSurfaceWrapClamp) != 0u, nearest = (flags & kSurfaceFilterNearest) != 0u;
-    const bool modulate = (flags & kSurfaceModulate) != 0u;
-    const int tw = static_cast<int>(tex_width), th = static_cast<int>(tex_height);
     ParallelFor(count, 256, [&](std::size_t q) {
         const int id = ids[q];
         float on[4] = {0.f, 0.f, 0.f, 1.f};
@@ -296,50 +354,8 @@ void HostSurface(const Scene& scene, std::size_t width, std::size_t height, cons
         float ouv[2] = {0.f, 0.f};
         if (id >= 0 && static_cast<std::size_t>(id) < n) {
             const std::size_t i = static_cast<std::size_t>(id);
-            const float fx = positions[2 * q], fy = positions[2 * q + 1];
             const Rec r = MakeRecord(scene.vertices.data() + 9 * i, f);
-            const SurfaceWeights bw = SurfaceBary(r.c, fx, fy);
-            const float* a = scene.albedo.data() + 3 * i;
-            if (normals != nullptr) {
-                const float* cn = normals + 9 * i;
-                const SurfaceNormal s = SurfaceSmoothNormal(SurfaceMix(bw, cn[0], cn[3], cn[6]),
-                                                            SurfaceMix(bw, cn[1], cn[4], cn[7]),
-                                                            SurfaceMix(bw, cn[2], cn[5], cn[8]), f.base, f.du, f.dv, fx, fy);
-                const float v[4] = {s.x, s.y, s.z, s.cosv};
-                std::copy(v, v + 4, on);
-            } else {
-                const GBufferTexel g = GBufferHit(r.c, r.vol, f.base, f.du, f.dv, fx, fy, id, r.n[0], r.n[1], r.n[2],
-                                                  r.n[3], a[0], a[1], a[2]);
-                const float v[4] = {g.nx, g.ny, g.nz, g.cosv};
-                std::copy(v, v + 4, on);
-            }
-            if (uvs != nullptr) {
-                const float* ct = uvs + 6 * i;
-                ouv[0] = SurfaceMix(bw, ct[0], ct[2], ct[4]);
-                ouv[1] = SurfaceMix(bw, ct[1], ct[3], ct[5]);
-            }
-            std::copy(a, a + 3, oa);
-            if (texture != nullptr) {
-                float tex[3];
-                if (nearest) {
-                    const int ti = SurfaceNearest(SurfaceWrap(ouv[0], clamp), tw);
-                    const int tj = SurfaceNearest(SurfaceWrap(ouv[1], clamp), th);
-                    const float* t = texture + 4 * (static_cast<std::size_t>(tj) * tex_width + static_cast<std::size_t>(ti));
-                    std::copy(t, t + 3, tex);
-                } else {
-                    const SurfaceTaps sx = SurfaceBilinear(SurfaceWrap(ouv[0], clamp), tw, clamp);
-                    const SurfaceTaps sy = SurfaceBilinear(SurfaceWrap(ouv[1], clamp), th, clamp);
-                    const float* top = texture + 4 * static_cast<std::size_t>(sy.i0) * tex_width;
-                    const float* bot = texture + 4 * static_cast<std::size_t>(sy.i1) * tex_width;
-                    for (int c = 0; c < 3; ++c) {
-                        tex[c] = SurfaceLerp(SurfaceLerp(top[4 * sx.i0 + c], top[4 * sx.i1 + c], sx.a),
-                                             SurfaceLerp(bot[4 * sx.i0 + c], bot[4 * sx.i1 + c], sx.a), sy.a);
-                    }
-                }
-                for (int c = 0; c < 3; ++c) {
-                    oa[c] = modulate ? tex[c] * a[c] : tex[c];
-                }
-            }
+            SurfaceLook(scene, f, tables, i, r, positions[2 * q], positions[2 * q + 1], on, oa, ouv);
             oa[3] = static_cast<float>(id);
         }
         if (normal != nullptr) {
@@ -677,9 +693,18 @@ void HostOmniShadow(const Scene& scene, std::size_t width, std::size_t height, c
     });
 }
 
-void HostLighting(const Scene& scene, std::size_t width, std::size_t height, const HostLight* lights, std::size_t count,
-                  const float ambient[3], const float* offsets, const int* ids, std::size_t row_begin,
-                  std::size_t row_count, float* rgba, unsigned char* classes) {
+void HostLitSurface(const Scene& scene, std::size_t width, std::size_t height, const HostLight* lights, std::size_t count,
+                    const float ambient[3], const HostSurfaceTables* surface, const HostMaterial* material,
+                    const float* offsets, const int* ids, std::size_t row_begin, std::size_t row_count, float* rgba,
+                    unsigned char* classes) {
+    if (surface != nullptr) {
+        CheckSurfaceTables(*surface);
+    }
+    if (material != nullptr && (material->shininess_log2 < 0 || material->shininess_log2 > kMaterialMaxShininessLog2)) {
+        throw std::runtime_error("Host lighting: shininess_log2 outside 0 .. 12");
+    }
+    const HostSurfaceTables tables = surface != nullptr ? *surface : HostSurfaceTables{};
+    const bool smooth = tables.normals != nullptr;
     if (width == 0 || height == 0) {
         throw std::runtime_error("Host lighting: frame dimensions must be non-zero");
     }
@@ -734,7 +759,9 @@ void HostLighting(const Scene& scene, std::size_t width, std::size_t height, con
         float d[3], p[3];
         LightingPoint(f.origin, f.base, f.du, f.dv, fx, fy, t, d, p);
         const float nn = ShadowDot(r.n, r.n), nd = ShadowDot(r.n, d);
-        float e[3] = {ambient[0], ambient[1], ambient[2]};
+        float on[4], oa[3], ouv[2];
+        SurfaceLook(scene, f, tables, static_cast<std::size_t>(id), r, fx, fy, on, oa, ouv);
+        float e[3] = {ambient[0], ambient[1], ambient[2]}, sp[3] = {0.f, 0.f, 0.f};
         for (std::size_t l = 0; l < count; ++l) {
             const HostLight& in = lights[l];
             const float* origin = frames[first[l]].frame.origin;
@@ -743,16 +770,16 @@ void HostLighting(const Scene& scene, std::size_t width, std::size_t height, con
                 q[k] = p[k] - origin[k];
             }
             const LightFrame& lf = frames[first[l] + (in.point ? static_cast<std::size_t>(OmniFace(q)) : 0)];
-            const ShadowPoint sp = ShadowProjectOffset(q, lf.rows, in.bias);
+            const ShadowPoint at = ShadowProjectOffset(q, lf.rows, in.bias);
             unsigned char cls = kShadowOutside;
-            if (sp.inside) {
+            if (at.inside) {
                 float best = inf;
                 int lid = -1;
                 for (std::size_t k = 0; k < n; ++k) {  // ascending ids: strict < keeps the lowest on ties
                     const float* c = lf.recs[k].c;
-                    const float eA = std::fma(sp.gy, c[2], std::fma(sp.gx, c[1], c[0]));
-                    const float eB = std::fma(sp.gy, c[5], std::fma(sp.gx, c[4], c[3]));
-                    const float eC = std::fma(sp.gy, c[8], std::fma(sp.gx, c[7], c[6]));
+                    const float eA = std::fma(at.gy, c[2], std::fma(at.gx, c[1], c[0]));
+                    const float eB = std::fma(at.gy, c[5], std::fma(at.gx, c[4], c[3]));
+                    const float eC = std::fma(at.gy, c[8], std::fma(at.gx, c[7], c[6]));
                     if (eA >= 0.f && eB >= 0.f && eC >= 0.f) {
                         const float det = (eA + eB) + eC;
                         if (det > 0.f) {
@@ -764,26 +791,39 @@ void HostLighting(const Scene& scene, std::size_t width, std::size_t height, con
                         }
                     }
                 }
-                cls = ShadowClass(id, lid, best, sp.thr);
+                cls = ShadowClass(id, lid, best, at.thr);
             }
             if (classes != nullptr) {
                 classes[l * plane + i] = cls;
             }
             const float nl = ShadowDot(r.n, q);
             if (cls == kShadowLit && LightingFacing(nl, nd)) {
-                const float w = LightingWeight(nl, nn, ShadowDot(q, q), in.falloff);
+                const float qq = ShadowDot(q, q);
+                const float w = smooth ? MaterialDiffuse(on, q, qq, in.falloff) : LightingWeight(nl, nn, qq, in.falloff);
                 for (int k = 0; k < 3; ++k) {
                     e[k] = e[k] + in.color[k] * w;
                 }
+                if (material != nullptr && w > 0.f) {
+                    const float ws = MaterialSpecular(on, q, qq, d, material->shininess_log2, in.falloff);
+                    for (int k = 0; k < 3; ++k) {
+                        sp[k] = sp[k] + in.color[k] * ws;
+                    }
+                }
             }
         }
-        const float* a = scene.albedo.data() + 3 * static_cast<std::size_t>(id);
-        out[0] = a[0] * e[0];
-        out[1] = a[1] * e[1];
-        out[2] = a[2] * e[2];
+        for (int k = 0; k < 3; ++k) {
+            out[k] = material != nullptr ? oa[k] * e[k] + material->specular[k] * sp[k] : oa[k] * e[k];
+        }
         out[3] = static_cast<float>(id);
         std::copy(out, out + 4, rgba + 4 * i);
     });
+}
+
+void HostLighting(const Scene& scene, std::size_t width, std::size_t height, const HostLight* lights, std::size_t count,
+                  const float ambient[3], const float* offsets, const int* ids, std::size_t row_begin,
+                  std::size_t row_count, float* rgba, unsigned char* classes) {
+    HostLitSurface(scene, width, height, lights, count, ambient, nullptr, nullptr, offsets, ids, row_begin, row_count, rgba,
+                   classes);
 }
 
 bool CpuBackendSelected() {

@@ -111,6 +111,25 @@ void HostLighting(const Scene& scene, std::size_t width, std::size_t height, con
                   const float ambient[3], const float* offsets, const int* ids, std::size_t row_begin,
                   std::size_t row_count, float* rgba, unsigned char* classes);
 
+// Lit surfaces (material_math.h; the host answer of render.h LaunchLitSurface): HostLighting with the
+// pixel's normal and albedo taken from HostSurface's tables (`surface`; null: none, the shading
+// table's) and, with a `material`, a Blinn-Phong term. Without both it is HostLighting, bit for bit.
+struct HostSurfaceTables {  // HostSurface's inputs: host arrays, each null for none
+    const float* normals;
+    const float* uvs;
+    const float* texture;
+    std::size_t tex_width, tex_height;
+    unsigned flags;
+};
+struct HostMaterial {
+    float specular[3];
+    int shininess_log2;  // 0 .. kMaterialMaxShininessLog2
+};
+void HostLitSurface(const Scene& scene, std::size_t width, std::size_t height, const HostLight* lights, std::size_t count,
+                    const float ambient[3], const HostSurfaceTables* surface, const HostMaterial* material,
+                    const float* offsets, const int* ids, std::size_t row_begin, std::size_t row_count, float* rgba,
+                    unsigned char* classes);
+
 // The light frame's projection rows (px, py, pz) as HostShadow and LaunchShadow compute them.
 void HostShadowRows(const Camera& light_camera, std::size_t light_width, std::size_t light_height, float rows[9]);
 

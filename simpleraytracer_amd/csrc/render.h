@@ -523,6 +523,27 @@ hipError_t LaunchLighting(const float* d_vertices, const float* d_shade, std::ui
                           const float background[3], const LightingLight* lights, std::size_t count,
                           const LightingArgs& args, hipStream_t stream);
 
+// Lit surfaces (render.hip LitSurfaceKernel; material_math.h; DESIGN.md section 2 "Lit surfaces"):
+// LaunchLighting with the pixel's normal and albedo taken from LaunchSurface's tables instead of the
+// shading table, and with a material a Blinn-Phong term: the textured, smooth-shaded, shadowed frame
+// in one launch. Classes, and which lights contribute, are LaunchLighting's; with no table and no
+// material so is the pixel, bit for bit.
+struct LitSurface {
+    // The surface as SurfaceArgs' (device; null: none).
+    const float* normals;
+    const float* uvs;
+    const float* texture;
+    std::size_t tex_width;
+    std::size_t tex_height;
+    unsigned flags;
+    bool material;  // specular, shininess_log2 hold one
+    float specular[3];
+    int shininess_log2;  // 0 .. kMaterialMaxShininessLog2: the exponent is 2^shininess_log2
+};
+hipError_t LaunchLitSurface(const float* d_vertices, const float* d_shade, std::uint64_t n, const Frame& frame,
+                            const float background[3], const LightingLight* lights, std::size_t count,
+                            const LightingArgs& args, const LitSurface& surface, hipStream_t stream);
+
 // G-buffer (render.hip GBufferKernel): the surface attributes of (image position, triangle id)
 // pairs of the frame -- depth, barycentrics, normal + shading cosine, albedo + id (gbuffer_math.h;
 // DESIGN.md section 2 "Surface attributes") -- from hit ids, a deferred pass like LaunchShade with

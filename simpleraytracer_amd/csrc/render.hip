@@ -7,6 +7,7 @@
 #include "gbuffer_math.h"
 #include "layers_math.h"
 #include "lighting_math.h"
+#include "material_math.h"
 #include "samples_math.h"
 #include "screen_box.h"
 #include "omni_math.h"
@@ -4457,7 +4458,8 @@ struct ViewPixel {
     bool surface;
     float t;
 };
-__device__ __forceinline__ ViewPixel ViewPixelAt(const ViewBand& v, unsigned pixel) {
+// The pixel without its depth (t = 0): what needs no gather by id.
+__device__ __forceinline__ ViewPixel ViewPixelWhere(const ViewBand& v, unsigned pixel) {
     ViewPixel px;
     px.code = v.ids[pixel];
     const float2 o = v.offsets[pixel];
@@ -4466,6 +4468,10 @@ __device__ __forceinline__ ViewPixel ViewPixelAt(const ViewBand& v, unsigned pix
     px.fy = (static_cast<float>(v.row_begin + y) + o.y) / v.hf;
     px.surface = static_cast<unsigned>(px.code) < v.n;
     px.t = 0.f;
+    return px;
+}
+__device__ __forceinline__ ViewPixel ViewPixelAt(const ViewBand& v, unsigned pixel) {
+    ViewPixel px = ViewPixelWhere(v, pixel);
     if (px.surface) {
         const float* at = v.vertices + 9ull * static_cast<unsigned>(px.code);
         float vx[9], c[9], vol;
@@ -4791,6 +4797,30 @@ struct LightingParams {
 static_assert(sizeof(LightingLightParams) == 40 && sizeof(LightingParams) == 3160 && sizeof(LightingParams) < 4096,
               "the light frames and the light table travel in the kernel-argument segment (< 4 KB)");
 
+// Light lt's class of the surface point P of triangle `code` (geometric normal N, nd = N.d), with
+// off = P - the light's origin, nl = N.off and whether the light and the eye face the same side.
+template <bool RC>
+__device__ __forceinline__ unsigned char LightClassAt(const LightingParams& q, const LightingLightParams& lt,
+                                                      const float P[3], const float N[3], float nd, int code,
+                                                      unsigned lane, float off[3], float& nl, bool& facing) {
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        off[k] = P[k] - lt.origin[k];
+    }
+    nl = ShadowDot(N, off);
+    facing = LightingFacing(nl, nd);
+    unsigned char cls = kShadowOutside;
+    if (facing || q.classes != nullptr) {  // (a light that is not facing adds nothing)
+        const unsigned fi = lt.first + (lt.point != 0u ? static_cast<unsigned>(OmniFace(off)) : 0u);
+        const LightFrame& f = q.frame[fi];
+        const ShadowPoint sp = ShadowProjectOffset(off, f.rows, lt.bias);
+        if (sp.inside) {
+            cls = OccludedAt<RC, kLightingLanes, kLightingAhead>(f, q.view.n, code, sp, lane);
+        }
+    }
+    return cls;
+}
+
 template <bool RC>
 __global__ __launch_bounds__(kLightingThreads) void LightingKernel(const LightingParams q) {
     const unsigned lane = threadIdx.x & (kLightingLanes - 1);
@@ -4820,22 +4850,9 @@ __global__ __launch_bounds__(kLightingThreads) void LightingKernel(const Lightin
         const LightingLightParams& lt = q.light[l];
         unsigned char cls = kShadowNoSurface;
         if (surface) {
-            float off[3];
-#pragma unroll
-            for (int k = 0; k < 3; ++k) {
-                off[k] = P[k] - lt.origin[k];
-            }
-            const float nl = ShadowDot(N, off);
-            const bool facing = LightingFacing(nl, nd);
-            cls = kShadowOutside;
-            if (facing || q.classes != nullptr) {  // (a light that is not facing adds nothing)
-                const unsigned fi = lt.first + (lt.point != 0u ? static_cast<unsigned>(OmniFace(off)) : 0u);
-                const LightFrame& f = q.frame[fi];
-                const ShadowPoint sp = ShadowProjectOffset(off, f.rows, lt.bias);
-                if (sp.inside) {
-                    cls = OccludedAt<RC, kLightingLanes, kLightingAhead>(f, v.n, code, sp, lane);
-                }
-            }
+            float off[3], nl;
+            bool facing;
+            cls = LightClassAt<RC>(q, lt, P, N, nd, code, lane, off, nl, facing);
             if (cls == kShadowLit && facing) {
                 const float w = LightingWeight(nl, nn, ShadowDot(off, off), lt.falloff);
                 e0 = e0 + lt.color[0] * w;
@@ -4851,6 +4868,205 @@ __global__ __launch_bounds__(kLightingThreads) void LightingKernel(const Lightin
         F4 out{v.bg[0], v.bg[1], v.bg[2], -1.f};
         if (surface) {
             out = F4{al[0] * e0, al[1] * e1, al[2] * e2, static_cast<float>(code)};
+        }
+        StoreNontemporal(q.rgba + pixel, out);
+    }
+}
+
+// ---------------------------------------------------------------------------------------
+// Lit surfaces (render.h LaunchLitSurface; material_math.h; DESIGN.md section 5 "Lit surfaces"):
+// LightingKernel with the pixel's normal and albedo from SurfaceKernel's tables and, with a material,
+// a Blinn-Phong term -- the textured, smooth-shaded, shadowed pixel in one launch. Launch shape,
+// light frames and light table are LightingKernel's (LightingParams travels whole, the surface and
+// the material behind it); LightClassAt gives every light's class from geometry alone, so the class
+// planes are LightingKernel's whatever the surface.
+// The pixel's by-id gathers are issued together before anything is computed from them: the vertex
+// row (36 B: the depth and the weights), the shading-table row (32 B: the geometric normal and the
+// scene's albedo), and behind uniform branches on what the call holds the normals row (36 B) and
+// the uvs row (24 B). From them the weights and the uv, and with a texture the texel taps (four
+// float4, one with the nearest filter) -- the second dependent chain, issued before the light loop
+// and first read after it, so that its latency sits under the scans; the smooth normal is needed in
+// the loop. Every lane of the pixel's group gathers and computes the same (one address per pixel and
+// load: the group's loads are one request, and the arithmetic is the wave's either way); lane 0
+// stores. An id outside the scene gathers nothing. No LDS, no atomics, no scratch.
+// ---------------------------------------------------------------------------------------
+#ifndef SRT_LITSURFACE_GATHER
+#define SRT_LITSURFACE_GATHER 0
+#endif
+// Who reads the normals row, the uvs row and the texels. 0: every lane of the pixel's group, the same
+// addresses (the product). Measurement builds (profiles/lit_surface/): 1: lane 0 alone, the others
+// carry zeros they never store; 2: the rows one float per lane, handed over with cross-lane moves.
+constexpr int kLitSurfaceGather = SRT_LITSURFACE_GATHER;
+static_assert(kLitSurfaceGather != 2 || kLightingLanes >= 9, "a normals row is nine floats");
+struct LitSurfaceParams {
+    LightingParams lit;
+    const float* __restrict__ normals;
+    const float* __restrict__ uvs;
+    const float4* __restrict__ texture;
+    int tw, th;
+    unsigned flags;
+    unsigned material;  // 1: specular, shininess hold one
+    int shininess;      // log2 of the exponent
+    float specular[3];
+};
+static_assert(sizeof(LitSurfaceParams) == sizeof(LightingParams) + 56 && sizeof(LitSurfaceParams) < 4096,
+              "the light frames, the light table and the surface travel in the kernel-argument segment (< 4 KB)");
+
+template <bool RC>
+__global__ __launch_bounds__(kLightingThreads) void LitSurfaceKernel(const LitSurfaceParams s) {
+    const LightingParams& q = s.lit;
+    const unsigned lane = threadIdx.x & (kLightingLanes - 1);
+    const unsigned pixel = blockIdx.x * kLightingBlock + threadIdx.x / kLightingLanes;
+    if (pixel >= q.view.pixels) {
+        return;
+    }
+    const ViewBand& v = q.view;
+    const ViewPixel px = ViewPixelWhere(v, pixel);
+    const bool surface = px.surface;
+    const int code = px.code;
+    // What the call holds (uniform).
+    const bool smooth = s.normals != nullptr;
+    const bool textured = s.texture != nullptr;
+    const bool shiny = s.material != 0u;
+    const bool modulate = (s.flags & kSurfaceModulate) != 0u;
+    const bool clamp = (s.flags & kSurfaceWrapClamp) != 0u;
+    const bool nearest = (s.flags & kSurfaceFilterNearest) != 0u;
+    // The pixel's facts, once for all lights.
+    float d[3] = {0.f, 0.f, 0.f}, P[3] = {0.f, 0.f, 0.f}, N[3] = {0.f, 0.f, 0.f}, al[3] = {0.f, 0.f, 0.f};
+    float u[3] = {0.f, 0.f, 0.f};
+    float nn = 0.f, nd = 0.f, ta = 0.f, tb = 0.f;
+    float4 t00{}, t01{}, t10{}, t11{};
+    const bool gathers = kLitSurfaceGather != 1 || lane == 0u;  // whether this lane reads the surface's rows and texels
+    if (surface) {
+        const unsigned id = static_cast<unsigned>(code);
+        float vx[9], cn[9], ct[6];
+        {
+            const float* at = v.vertices + 9ull * id;
+#pragma unroll
+            for (int j = 0; j < 9; ++j) {
+                vx[j] = at[j];
+                cn[j] = 0.f;
+            }
+        }
+        const float4* sr = v.shade + 2ull * id;
+        const float4 nr = sr[0], ar = sr[1];
+#pragma unroll
+        for (int j = 0; j < 6; ++j) {
+            ct[j] = 0.f;
+        }
+        if constexpr (kLitSurfaceGather == 2) {  // one float per lane and row, handed over within the group
+            const float mn = smooth && lane < 9u ? s.normals[9ull * id + lane] : 0.f;
+            const float mt = textured && lane < 6u ? s.uvs[6ull * id + lane] : 0.f;
+#pragma unroll
+            for (int j = 0; j < 9; ++j) {
+                cn[j] = __shfl(mn, j, kLightingLanes);
+            }
+#pragma unroll
+            for (int j = 0; j < 6; ++j) {
+                ct[j] = __shfl(mt, j, kLightingLanes);
+            }
+        } else {
+            if (smooth && gathers) {
+                const float* at = s.normals + 9ull * id;
+#pragma unroll
+                for (int j = 0; j < 9; ++j) {
+                    cn[j] = at[j];
+                }
+            }
+            if (textured && gathers) {
+                const float* at = s.uvs + 6ull * id;
+#pragma unroll
+                for (int j = 0; j < 6; ++j) {
+                    ct[j] = at[j];
+                }
+            }
+        }
+        float c[9], vol;
+        ComputeEdges(v.eye, v.base, v.du, v.dv, vx, true, c, vol);
+        const float t = ShadowDepth(c, vol, px.fx, px.fy);  // (ViewPixelAt's)
+        const SurfaceWeights bw = smooth || textured ? SurfaceBary(c, px.fx, px.fy) : SurfaceWeights{0.f, 0.f, 0.f};
+        if (textured && (gathers || kLitSurfaceGather == 2)) {
+            const float tu = SurfaceMix(bw, ct[0], ct[2], ct[4]), tv = SurfaceMix(bw, ct[1], ct[3], ct[5]);
+            if (nearest) {
+                const int i = SurfaceNearest(SurfaceWrap(tu, clamp), s.tw);
+                const int j = SurfaceNearest(SurfaceWrap(tv, clamp), s.th);
+                t00 = s.texture[static_cast<size_t>(j) * static_cast<unsigned>(s.tw) + static_cast<unsigned>(i)];
+            } else {
+                const SurfaceTaps sx = SurfaceBilinear(SurfaceWrap(tu, clamp), s.tw, clamp);
+                const SurfaceTaps sy = SurfaceBilinear(SurfaceWrap(tv, clamp), s.th, clamp);
+                const float4* top = s.texture + static_cast<size_t>(sy.i0) * static_cast<unsigned>(s.tw);
+                const float4* bot = s.texture + static_cast<size_t>(sy.i1) * static_cast<unsigned>(s.tw);
+                t00 = top[sx.i0];
+                t01 = top[sx.i1];
+                t10 = bot[sx.i0];
+                t11 = bot[sx.i1];
+                ta = sx.a;
+                tb = sy.a;
+            }
+        }
+        LightingPoint(v.eye, v.base, v.du, v.dv, px.fx, px.fy, t, d, P);
+        N[0] = nr.x, N[1] = nr.y, N[2] = nr.z;
+        al[0] = ar.x, al[1] = ar.y, al[2] = ar.z;
+        nn = ShadowDot(N, N);
+        nd = ShadowDot(N, d);
+        if (smooth) {
+            const SurfaceNormal sn =
+                SurfaceSmoothNormal(SurfaceMix(bw, cn[0], cn[3], cn[6]), SurfaceMix(bw, cn[1], cn[4], cn[7]),
+                                    SurfaceMix(bw, cn[2], cn[5], cn[8]), v.base, v.du, v.dv, px.fx, px.fy);
+            u[0] = sn.x, u[1] = sn.y, u[2] = sn.z;
+        } else if (shiny) {  // (the G-buffer's normal plane, SurfaceKernel's fallback: it needs no edge record)
+            const float none[9] = {};
+            const GBufferTexel g = GBufferHit(none, 0.f, v.base, v.du, v.dv, px.fx, px.fy, code, nr.x, nr.y, nr.z, nr.w,
+                                              ar.x, ar.y, ar.z);
+            u[0] = g.nx, u[1] = g.ny, u[2] = g.nz;
+        }
+    }
+    float e0 = q.ambient[0], e1 = q.ambient[1], e2 = q.ambient[2];
+    float s0 = 0.f, s1 = 0.f, s2 = 0.f;
+    for (unsigned l = 0u; l < q.count; ++l) {
+        const LightingLightParams& lt = q.light[l];
+        unsigned char cls = kShadowNoSurface;
+        if (surface) {
+            float off[3], nl;
+            bool facing;
+            cls = LightClassAt<RC>(q, lt, P, N, nd, code, lane, off, nl, facing);
+            if (cls == kShadowLit && facing) {
+                const float qq = ShadowDot(off, off);
+                const float w = smooth ? MaterialDiffuse(u, off, qq, lt.falloff) : LightingWeight(nl, nn, qq, lt.falloff);
+                e0 = e0 + lt.color[0] * w;
+                e1 = e1 + lt.color[1] * w;
+                e2 = e2 + lt.color[2] * w;
+                if (shiny && w > 0.f) {
+                    const float ws = MaterialSpecular(u, off, qq, d, s.shininess, lt.falloff);
+                    s0 = s0 + lt.color[0] * ws;
+                    s1 = s1 + lt.color[1] * ws;
+                    s2 = s2 + lt.color[2] * ws;
+                }
+            }
+        }
+        if (lane == 0u && q.classes != nullptr) {
+            q.classes[static_cast<size_t>(l) * v.pixels + pixel] = cls;
+        }
+    }
+    if (lane == 0u) {
+        F4 out{v.bg[0], v.bg[1], v.bg[2], -1.f};
+        if (surface) {
+            float r = al[0], g = al[1], b = al[2];
+            if (textured) {
+                float tr = t00.x, tg = t00.y, tbl = t00.z;
+                if (!nearest) {
+                    tr = SurfaceLerp(SurfaceLerp(t00.x, t01.x, ta), SurfaceLerp(t10.x, t11.x, ta), tb);
+                    tg = SurfaceLerp(SurfaceLerp(t00.y, t01.y, ta), SurfaceLerp(t10.y, t11.y, ta), tb);
+                    tbl = SurfaceLerp(SurfaceLerp(t00.z, t01.z, ta), SurfaceLerp(t10.z, t11.z, ta), tb);
+                }
+                r = modulate ? tr * r : tr;
+                g = modulate ? tg * g : tg;
+                b = modulate ? tbl * b : tbl;
+            }
+            out = F4{r * e0, g * e1, b * e2, static_cast<float>(code)};
+            if (shiny) {
+                out = F4{out.x + s.specular[0] * s0, out.y + s.specular[1] * s1, out.z + s.specular[2] * s2, out.w};
+            }
         }
         StoreNontemporal(q.rgba + pixel, out);
     }
@@ -6439,25 +6655,23 @@ hipError_t LaunchOmniShadow(const float* d_vertices, const float* d_shade, std::
                           kOmniThreads, stream, q);
 }
 
-hipError_t LaunchLighting(const float* d_vertices, const float* d_shade, std::uint64_t n, const Frame& frame,
-                          const float background[3], const LightingLight* lights, std::size_t count,
-                          const LightingArgs& args, hipStream_t stream) {
-    if (args.width == 0 || args.row_count == 0) {
-        return hipSuccess;
-    }
-    LightingParams q{};
+// The band, the light frames and the light table of a lighting launch (LaunchLighting,
+// LaunchLitSurface). False: arguments the launchers refuse; else `recompute` is the record source.
+static bool FillLighting(LightingParams& q, const float* d_vertices, const float* d_shade, std::uint64_t n,
+                         const Frame& frame, const float background[3], const LightingLight* lights, std::size_t count,
+                         const LightingArgs& args, bool& recompute) {
     if (args.rgba == nullptr || count > static_cast<std::size_t>(kLightingMaxLights) || (count != 0 && lights == nullptr) ||
         !FillViewBand(q.view, d_vertices, d_shade, n, frame, background, args, kLightingBlock)) {
-        return hipErrorInvalidValue;
+        return false;
     }
-    bool recompute = false;
+    recompute = false;
     unsigned frames = 0u;
     for (std::size_t i = 0; i < count; ++i) {
         const LightingLight& in = lights[i];
         const unsigned faces = in.point ? static_cast<unsigned>(kOmniFaces) : 1u;
         if (in.frames == nullptr || frames + faces > static_cast<unsigned>(kLightingMaxFrames) || !(in.bias >= 0.f) ||
             !std::isfinite(in.bias) || !(in.falloff >= 0.f) || !std::isfinite(in.falloff)) {
-            return hipErrorInvalidValue;
+            return false;
         }
         LightingLightParams& lt = q.light[i];
         lt.first = frames;
@@ -6472,7 +6686,7 @@ hipError_t LaunchLighting(const float* d_vertices, const float* d_shade, std::ui
             bool rc = false;
             if (!SameLight(in.frames[k], in.frames[0]) || !FillLightFrame(q.frame[frames], in.frames[k], n, rc) ||
                 (frames != 0u && rc != recompute)) {
-                return hipErrorInvalidValue;  // (the last: one record source per launch)
+                return false;  // (the last: one record source per launch)
             }
             recompute = rc;
         }
@@ -6483,8 +6697,56 @@ hipError_t LaunchLighting(const float* d_vertices, const float* d_shade, std::ui
     for (int k = 0; k < 3; ++k) {
         q.ambient[k] = args.ambient[k];
     }
+    return true;
+}
+
+hipError_t LaunchLighting(const float* d_vertices, const float* d_shade, std::uint64_t n, const Frame& frame,
+                          const float background[3], const LightingLight* lights, std::size_t count,
+                          const LightingArgs& args, hipStream_t stream) {
+    if (args.width == 0 || args.row_count == 0) {
+        return hipSuccess;
+    }
+    LightingParams q{};
+    bool recompute = false;
+    if (!FillLighting(q, d_vertices, d_shade, n, frame, background, lights, count, args, recompute)) {
+        return hipErrorInvalidValue;
+    }
     return LaunchBySource(recompute, LightingKernel<true>, LightingKernel<false>, ViewBandGrid(q.view, kLightingBlock),
                           kLightingThreads, stream, q);
+}
+
+hipError_t LaunchLitSurface(const float* d_vertices, const float* d_shade, std::uint64_t n, const Frame& frame,
+                            const float background[3], const LightingLight* lights, std::size_t count,
+                            const LightingArgs& args, const LitSurface& surface, hipStream_t stream) {
+    if (args.width == 0 || args.row_count == 0) {
+        return hipSuccess;
+    }
+    LitSurfaceParams s{};
+    bool recompute = false;
+    const bool texture_ok = surface.texture == nullptr ||
+                            (surface.uvs != nullptr && surface.tex_width >= 1 && surface.tex_width <= kSurfaceMaxTexture &&
+                             surface.tex_height >= 1 && surface.tex_height <= kSurfaceMaxTexture);
+    const bool material_ok =
+        !surface.material ||
+        (surface.shininess_log2 >= 0 && surface.shininess_log2 <= kMaterialMaxShininessLog2 &&
+         std::isfinite(surface.specular[0]) && std::isfinite(surface.specular[1]) && std::isfinite(surface.specular[2]));
+    if (!texture_ok || !material_ok || (surface.flags & ~kSurfaceFlags) != 0u ||
+        !FillLighting(s.lit, d_vertices, d_shade, n, frame, background, lights, count, args, recompute)) {
+        return hipErrorInvalidValue;
+    }
+    s.normals = surface.normals;
+    s.uvs = surface.uvs;
+    s.texture = reinterpret_cast<const float4*>(surface.texture);
+    s.tw = surface.texture != nullptr ? static_cast<int>(surface.tex_width) : 1;
+    s.th = surface.texture != nullptr ? static_cast<int>(surface.tex_height) : 1;
+    s.flags = surface.flags;
+    s.material = surface.material ? 1u : 0u;
+    s.shininess = surface.material ? surface.shininess_log2 : 0;
+    for (int k = 0; k < 3; ++k) {
+        s.specular[k] = surface.material ? surface.specular[k] : 0.f;
+    }
+    return LaunchBySource(recompute, LitSurfaceKernel<true>, LitSurfaceKernel<false>,
+                          ViewBandGrid(s.lit.view, kLightingBlock), kLightingThreads, stream, s);
 }
 
 hipError_t LaunchGBuffer(const float* d_vertices, const float* d_shade, std::uint64_t n, const Frame& frame,

@@ -1326,6 +1326,18 @@ void DeviceScene::CheckLights(const LightTerms* lights, std::size_t count, const
 void DeviceScene::Lighting(const Light* lights, std::size_t count, const float ambient[3], const float* d_offsets,
                            const int* d_ids, std::size_t row_begin, std::size_t row_count, float* d_rgba,
                            unsigned char* d_classes, hipStream_t stream) const {
+    LightingWith(nullptr, lights, count, ambient, d_offsets, d_ids, row_begin, row_count, d_rgba, d_classes, stream);
+}
+
+void DeviceScene::LitSurface(const Light* lights, std::size_t count, const float ambient[3], const srt::LitSurface& surface,
+                             const float* d_offsets, const int* d_ids, std::size_t row_begin, std::size_t row_count,
+                             float* d_rgba, unsigned char* d_classes, hipStream_t stream) const {
+    LightingWith(&surface, lights, count, ambient, d_offsets, d_ids, row_begin, row_count, d_rgba, d_classes, stream);
+}
+
+void DeviceScene::LightingWith(const srt::LitSurface* surface, const Light* lights, std::size_t count,
+                               const float ambient[3], const float* d_offsets, const int* d_ids, std::size_t row_begin,
+                               std::size_t row_count, float* d_rgba, unsigned char* d_classes, hipStream_t stream) const {
     if (m_width == 0) {
         throw std::runtime_error("Lighting: Prepare() has not been called on the view scene");
     }
@@ -1379,7 +1391,12 @@ void DeviceScene::Lighting(const Light* lights, std::size_t count, const float a
     }
     const LightingArgs args{d_offsets, d_ids,  m_width,  m_height, row_begin, row_count, {ambient[0], ambient[1], ambient[2]},
                             d_rgba,    d_classes};
-    HipCheck(LaunchLighting(m_vertices, m_shade, m_n, m_frame, m_background, ll, count, args, stream), "lighting launch");
+    if (surface != nullptr) {
+        HipCheck(LaunchLitSurface(m_vertices, m_shade, m_n, m_frame, m_background, ll, count, args, *surface, stream),
+                 "lit surface launch");
+    } else {
+        HipCheck(LaunchLighting(m_vertices, m_shade, m_n, m_frame, m_background, ll, count, args, stream), "lighting launch");
+    }
     RecordOrder(stream);
     for (std::size_t l = 0; l < count; ++l) {
         for (std::size_t k = 0; k < (lights[l].point ? 6u : 1u); ++k) {

@@ -23,6 +23,7 @@ struct ShadowLight;  // render.h
 struct StageEvents;  // render.h
 struct OrderScratch;  // render.h
 struct SurfaceArgs;   // render.h
+struct LitSurface;    // render.h
 
 // Throws std::runtime_error("HIP error: <what>: <reason>") on failure.
 void HipCheck(hipError_t err, const char* what);
@@ -174,6 +175,12 @@ public:
     void Lighting(const Light* lights, std::size_t count, const float ambient[3], const float* d_offsets,
                   const int* d_ids, std::size_t row_begin, std::size_t row_count, float* d_rgba,
                   unsigned char* d_classes, hipStream_t stream) const;
+    // Lit surfaces (render.h LaunchLitSurface): Lighting with the pixel's normal and albedo from the
+    // caller's device tables in `surface` and, if it holds one, a material. Every rule of Lighting
+    // applies; the caller has checked the surface and the material (render.h LitSurface).
+    void LitSurface(const Light* lights, std::size_t count, const float ambient[3], const srt::LitSurface& surface,
+                    const float* d_offsets, const int* d_ids, std::size_t row_begin, std::size_t row_count,
+                    float* d_rgba, unsigned char* d_classes, hipStream_t stream) const;
 
     // G-buffer: the surface attributes (render.h GBufferArgs: depth, bary, normal, albedo; a null
     // plane is not written) of hit ids on the prepared frame. points: `count` positions d_where
@@ -339,6 +346,10 @@ private:
         const char* its_scene;   // "the light scene" or "the light's scene": whose triangles are counted
     };
     void CheckLightScene(const DeviceScene& f, const DeviceScene& first, const LightWords& w) const;
+    // Lighting (surface == nullptr) and LitSurface: the same checks, ordering and setups, one launch.
+    void LightingWith(const srt::LitSurface* surface, const Light* lights, std::size_t count, const float ambient[3],
+                      const float* d_offsets, const int* d_ids, std::size_t row_begin, std::size_t row_count,
+                      float* d_rgba, unsigned char* d_classes, hipStream_t stream) const;
     // This scene as a light frame of `view`'s launch on `stream`: ordered after its previous call,
     // its query setup (re)built into `setup` if it has one.
     ShadowLight AsLightFrame(const DeviceScene& view, CullSetup& setup, hipStream_t stream) const;

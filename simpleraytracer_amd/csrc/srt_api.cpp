@@ -12,6 +12,7 @@
 #include "cpu_render.h"
 #include "engine.h"
 #include "lighting_math.h"
+#include "material_math.h"
 #include "omni_math.h"
 #include "render.h"
 #include "renderer.h"
@@ -20,6 +21,7 @@
 #include "srt_layers.h"
 #include "srt_light.h"
 #include "srt_lighting.h"
+#include "srt_material.h"
 #include "srt_motion.h"
 #include "srt_omni.h"
 #include "srt_query.h"
@@ -1380,9 +1382,12 @@ RTO_API int rtoFaceOfHost(const float q[3]) {
 static_assert(RTD_MAX_LIGHTS == srt::kLightingMaxLights && RTD_MAX_FRAMES == srt::kLightingMaxFrames,
               "include/srt_lighting.h and lighting_math.h agree");
 
-RTD_API int rtdLightAsync(srt_device_scene view, const rtd_light* lights, size_t count, const float ambient[3],
-                          const float* d_offsets, const int* d_ids, size_t row_begin, size_t row_count,
-                          float* d_rgba, unsigned char* d_classes, void* stream) {
+namespace {
+
+// rtdLightAsync, and with a `surface` (checked by the caller) rtpLightSurfaceAsync.
+int LightAsync(srt_device_scene view, const rtd_light* lights, size_t count, const float ambient[3],
+               const srt::LitSurface* surface, const float* d_offsets, const int* d_ids, size_t row_begin,
+               size_t row_count, float* d_rgba, unsigned char* d_classes, void* stream) {
     return Guarded([&] {
         if (view == nullptr) {
             throw std::runtime_error("Bad scene handle: view is NULL");
@@ -1427,14 +1432,21 @@ RTD_API int rtdLightAsync(srt_device_scene view, const rtd_light* lights, size_t
         }
         srt::DeviceScene* s = FromHandle(view);
         Bind bind(s->device());
-        s->Lighting(in.data(), count, ambient, d_offsets, d_ids, row_begin, row_count, d_rgba, d_classes,
-                    static_cast<hipStream_t>(stream));
+        if (surface != nullptr) {
+            s->LitSurface(in.data(), count, ambient, *surface, d_offsets, d_ids, row_begin, row_count, d_rgba, d_classes,
+                          static_cast<hipStream_t>(stream));
+        } else {
+            s->Lighting(in.data(), count, ambient, d_offsets, d_ids, row_begin, row_count, d_rgba, d_classes,
+                        static_cast<hipStream_t>(stream));
+        }
     });
 }
 
-RTD_API int rtdLightHost(const char* scene_path, size_t width, size_t height, const rtd_light_host* lights, size_t count,
-                         const float ambient[3], const float* offsets, const int* ids, size_t row_begin, size_t row_count,
-                         float* rgba, unsigned char* classes) {
+// rtdLightHost, and with `surface` / `material` (checked by the caller) rtpLightSurfaceHost.
+int LightHost(const char* scene_path, size_t width, size_t height, const rtd_light_host* lights, size_t count,
+              const float ambient[3], const srt::HostSurfaceTables* surface, const srt::HostMaterial* material,
+              const float* offsets, const int* ids, size_t row_begin, size_t row_count, float* rgba,
+              unsigned char* classes) {
     return Guarded([&] {
         if (scene_path == nullptr) {
             throw std::runtime_error("Bad argument: scene_path is NULL");
@@ -1508,9 +1520,25 @@ RTD_API int rtdLightHost(const char* scene_path, size_t width, size_t height, co
             throw std::runtime_error("Bad buffer argument: rgba is NULL");
         }
         const srt::Scene scene = srt::LoadScene(scene_path);
-        srt::HostLighting(scene, width, height, in.data(), count, ambient, offsets, ids, row_begin, row_count, rgba,
-                          classes);
+        srt::HostLitSurface(scene, width, height, in.data(), count, ambient, surface, material, offsets, ids, row_begin,
+                            row_count, rgba, classes);
     });
+}
+
+}  // namespace
+
+RTD_API int rtdLightAsync(srt_device_scene view, const rtd_light* lights, size_t count, const float ambient[3],
+                          const float* d_offsets, const int* d_ids, size_t row_begin, size_t row_count,
+                          float* d_rgba, unsigned char* d_classes, void* stream) {
+    return LightAsync(view, lights, count, ambient, nullptr, d_offsets, d_ids, row_begin, row_count, d_rgba, d_classes,
+                      stream);
+}
+
+RTD_API int rtdLightHost(const char* scene_path, size_t width, size_t height, const rtd_light_host* lights, size_t count,
+                         const float ambient[3], const float* offsets, const int* ids, size_t row_begin, size_t row_count,
+                         float* rgba, unsigned char* classes) {
+    return LightHost(scene_path, width, height, lights, count, ambient, nullptr, nullptr, offsets, ids, row_begin,
+                     row_count, rgba, classes);
 }
 
 // Dynamic scenes (include/srt_motion.h): the rtm family. Checks in the order flags, camera / origin,
@@ -1828,6 +1856,73 @@ RTV_API int rtvObjAttributesHost(const char* path, float* normals, float* uvs, i
             have[1] = any[1] ? 1 : 0;
         }
     });
+}
+
+// Lit surfaces (include/srt_material.h): the rtp family -- the rtd calls on an rtv surface. The
+// surface and the material are checked here, before the lights; the rest is LightAsync / LightHost.
+static_assert(RTP_MAX_SHININESS_LOG2 == srt::kMaterialMaxShininessLog2, "include/srt_material.h and material_math.h agree");
+
+namespace {
+
+// The surface (NULL: none) and the material (NULL: none) of an rtp call, as render.h's LitSurface.
+srt::LitSurface CheckedLitSurface(const rtv_surface* surface, const rtp_material* material) {
+    srt::LitSurface out{};
+    if (surface != nullptr) {
+        const rtv_surface s = CheckedSurface(surface);
+        out.normals = s.normals;
+        out.uvs = s.uvs;
+        out.texture = s.texture;
+        out.tex_width = s.tex_width;
+        out.tex_height = s.tex_height;
+        out.flags = s.flags;
+    }
+    if (material != nullptr) {
+        if (material->struct_size != sizeof(rtp_material)) {
+            throw std::runtime_error("rtp_material.struct_size is " + std::to_string(material->struct_size) +
+                                     ", expected " + std::to_string(sizeof(rtp_material)));
+        }
+        for (int k = 0; k < 3; ++k) {
+            if (!std::isfinite(material->specular[k])) {
+                throw std::runtime_error("rtp_material.specular value " + std::to_string(k) + " is not finite");
+            }
+            out.specular[k] = material->specular[k];
+        }
+        if (material->shininess_log2 < 0 || material->shininess_log2 > RTP_MAX_SHININESS_LOG2) {
+            throw std::runtime_error("rtp_material.shininess_log2 must be 0 to " + std::to_string(RTP_MAX_SHININESS_LOG2) +
+                                     ", got " + std::to_string(material->shininess_log2));
+        }
+        out.material = true;
+        out.shininess_log2 = material->shininess_log2;
+    }
+    return out;
+}
+
+}  // namespace
+
+RTP_API int rtpLightSurfaceAsync(srt_device_scene view, const rtd_light* lights, size_t count, const float ambient[3],
+                                 const rtv_surface* surface, const rtp_material* material, const float* d_offsets,
+                                 const int* d_ids, size_t row_begin, size_t row_count, float* d_rgba,
+                                 unsigned char* d_classes, void* stream) {
+    srt::LitSurface lit{};
+    if (Guarded([&] { lit = CheckedLitSurface(surface, material); }) != 0) {
+        return -1;
+    }
+    return LightAsync(view, lights, count, ambient, &lit, d_offsets, d_ids, row_begin, row_count, d_rgba, d_classes,
+                      stream);
+}
+
+RTP_API int rtpLightSurfaceHost(const char* scene_path, size_t width, size_t height, const rtd_light_host* lights,
+                                size_t count, const float ambient[3], const rtv_surface* surface,
+                                const rtp_material* material, const float* offsets, const int* ids, size_t row_begin,
+                                size_t row_count, float* rgba, unsigned char* classes) {
+    srt::LitSurface lit{};
+    if (Guarded([&] { lit = CheckedLitSurface(surface, material); }) != 0) {
+        return -1;
+    }
+    const srt::HostSurfaceTables tables{lit.normals, lit.uvs, lit.texture, lit.tex_width, lit.tex_height, lit.flags};
+    const srt::HostMaterial mat{{lit.specular[0], lit.specular[1], lit.specular[2]}, lit.shininess_log2};
+    return LightHost(scene_path, width, height, lights, count, ambient, &tables, lit.material ? &mat : nullptr, offsets,
+                     ids, row_begin, row_count, rgba, classes);
 }
 
 #ifdef SRT_DIAG

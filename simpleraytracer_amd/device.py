@@ -419,6 +419,23 @@ def surface_host(path: str, width: int, height: int, positions, ids, surface: Su
 
     pos, idv = _host_elements(positions, ids)
     count = pos.shape[0]
+    host = _host_surface(path, surface)
+    normal = np.empty((count, 4), np.float32)
+    albedo = np.empty((count, 4), np.float32)
+    rgba = np.empty((count, 4), np.float32)
+    uv = np.empty((count, 2), np.float32)
+    s = host._struct(lambda a: 0 if a is None else a.ctypes.data)
+    out = _native.RtvOutputs(ctypes.sizeof(_native.RtvOutputs), normal.ctypes.data, albedo.ctypes.data,
+                             rgba.ctypes.data, uv.ctypes.data)
+    _check(_native.lib().rtvSurfaceHost(os.fsencode(path), width, height, pos.ctypes.data, idv.ctypes.data, count,
+                                        ctypes.byref(s), ctypes.byref(out)))
+    return normal, albedo, rgba, uv
+
+
+def _host_surface(path: str, surface: Surface) -> Surface:
+    """`surface` with its tables as contiguous float32 numpy arrays, checked against path's triangles."""
+    import numpy as np
+
     n = scene_triangles(path)
     held = {}
     for name, tail in (("normals", (3, 3)), ("uvs", (3, 2))):
@@ -433,18 +450,41 @@ def surface_host(path: str, width: int, height: int, positions, ids, surface: Su
         if a.ndim != 3 or a.shape[2] != 4:
             raise ValueError(f"texture must be (TH, TW, 4), got {a.shape}")
         held["texture"] = a
-    host = Surface(held.get("normals"), held.get("uvs"), held.get("texture"), surface.wrap, surface.filter,
+    return Surface(held.get("normals"), held.get("uvs"), held.get("texture"), surface.wrap, surface.filter,
                    surface.modulate)
-    normal = np.empty((count, 4), np.float32)
-    albedo = np.empty((count, 4), np.float32)
-    rgba = np.empty((count, 4), np.float32)
-    uv = np.empty((count, 2), np.float32)
-    s = host._struct(lambda a: 0 if a is None else a.ctypes.data)
-    out = _native.RtvOutputs(ctypes.sizeof(_native.RtvOutputs), normal.ctypes.data, albedo.ctypes.data,
-                             rgba.ctypes.data, uv.ctypes.data)
-    _check(_native.lib().rtvSurfaceHost(os.fsencode(path), width, height, pos.ctypes.data, idv.ctypes.data, count,
-                                        ctypes.byref(s), ctypes.byref(out)))
-    return normal, albedo, rgba, uv
+
+
+def lit_surface_host(path: str, width: int, height: int, lights, ambient, offsets, ids, surface, material=None,
+                     row_begin: int = 0, row_count: int | None = None):
+    """Lit surfaces on the host (rtpLightSurfaceHost: the library's canonical math, no device):
+    lighting_host() on the surface a Surface of numpy arrays describes (None: none) with a
+    lighting.Material (None: no highlight) -> (rgba (rows, W, 4) float32, classes (len(lights),
+    rows, W) uint8). Without both it is lighting_host(), bit for bit."""
+    import numpy as np
+
+    from . import lighting
+
+    if row_count is None:
+        row_count = height - row_begin
+    off = np.ascontiguousarray(offsets, np.float32)
+    idv = np.ascontiguousarray(ids, np.int32)
+    if off.shape != (row_count, width, 2):
+        raise ValueError(f"offsets must be {(row_count, width, 2)}, got {off.shape}")
+    if idv.shape != (row_count, width):
+        raise ValueError(f"ids must be {(row_count, width)}, got {idv.shape}")
+    if surface is not None and not isinstance(surface, Surface):
+        raise ValueError(f"surface must be a Surface or None, got {type(surface).__name__}")
+    host = _host_surface(path, surface) if surface is not None else None
+    s = ctypes.byref(host._struct(lambda a: 0 if a is None else a.ctypes.data)) if host is not None else None
+    arr, count = lighting.pack_host(lights)
+    rgba = np.empty((row_count, width, 4), np.float32)
+    classes = np.empty((count, row_count, width), np.uint8)
+    _check(_native.lib().rtpLightSurfaceHost(os.fsencode(path), width, height,
+                                             ctypes.addressof(arr) if arr is not None else None, count,
+                                             lighting.ambient3(ambient), s, lighting.material_ref(material),
+                                             off.ctypes.data, idv.ctypes.data, row_begin, row_count, rgba.ctypes.data,
+                                             classes.ctypes.data))
+    return rgba, classes
 
 
 def interpolate_host(path: str, width: int, height: int, positions, ids, table):
@@ -1040,6 +1080,39 @@ class DeviceScene:
         available), then light() from them, both on `stream`."""
         self.trace_ids(offsets, ids, variant=variant, stream=stream)
         self.light(lights, offsets, ids, rgba, ambient=ambient, classes=classes, stream=stream)
+
+    def light_surface(self, lights, offsets, ids, surface, rgba, ambient=(0.0, 0.0, 0.0), material=None, classes=None,
+                      row_begin: int = 0, row_count: int | None = None, stream=None):
+        """The textured, smooth-shaded, shadowed rows of the prepared frame (include/srt_material.h):
+        light() on the surface a Surface of device tables describes (None: none) -- its smooth normal
+        under the lights, its textured albedo -- with a lighting.Material (None: no highlight) adding
+        a Blinn-Phong term. lights, offsets, ids, rgba, ambient, classes as light()'s; the classes
+        are light()'s whatever the surface, and without surface and material so is rgba. One launch."""
+        from . import lighting
+
+        if row_count is None:
+            row_count = self.height - row_begin
+        self._check_buffer("offsets", offsets, row_count, 2, "f32")
+        self._check_buffer("ids", ids, row_count, 0, "i32")
+        self._check_buffer("rgba", rgba, row_count, 4, "f32")
+        s = ctypes.byref(self._surface(surface, (), ())[0]) if surface is not None else None
+        arr, count = lighting.pack_device(lights)
+        if classes is not None:
+            if hasattr(classes, "shape") and tuple(classes.shape) != (count, row_count, self.width):
+                raise ValueError(f"classes must be {(count, row_count, self.width)}, got {tuple(classes.shape)}")
+            self._check_tensor("classes", classes, "u8")
+        _check(self._lib.rtpLightSurfaceAsync(self.handle, ctypes.addressof(arr) if arr is not None else None, count,
+                                              lighting.ambient3(ambient), s, lighting.material_ref(material),
+                                              _ptr(offsets), _ptr(ids), row_begin, row_count, _ptr(rgba), _ptr(classes),
+                                              _stream(stream)))
+
+    def render_lit_surface(self, lights, offsets, ids, surface, rgba, ambient=(0.0, 0.0, 0.0), material=None,
+                           classes=None, variant: str = "cull", stream=None):
+        """The lit surface of the whole prepared frame: trace_ids() into ids ((H, W) int32; they stay
+        available), then light_surface() from them, both on `stream`."""
+        self.trace_ids(offsets, ids, variant=variant, stream=stream)
+        self.light_surface(lights, offsets, ids, surface, rgba, ambient=ambient, material=material, classes=classes,
+                           stream=stream)
 
     def close(self):
         if self.handle:

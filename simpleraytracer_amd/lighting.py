@@ -1,5 +1,7 @@
 """The lights of the direct-lighting calls (include/srt_lighting.h): what DeviceScene.light(),
-DeviceScene.render_lit() and device.lighting_host() take.
+DeviceScene.render_lit() and device.lighting_host() take -- and, with a device.Surface and a
+Material, DeviceScene.light_surface(), render_lit_surface() and device.lit_surface_host()
+(include/srt_material.h).
 
     key = SpotLight(DeviceScene(path, 0, camera=cam), color=(1.0, 0.9, 0.8), falloff=9.0, bias=2 ** -10)
     bulb = PointLight(OmniLight(path, 0, origin), color=(0.3, 0.3, 1.0), falloff=4.0)
@@ -20,7 +22,7 @@ from dataclasses import dataclass
 from typing import Any, Sequence
 
 from . import _native
-from ._native import RTD_MAX_FRAMES, RTD_MAX_LIGHTS  # noqa: F401
+from ._native import RTD_MAX_FRAMES, RTD_MAX_LIGHTS, RTP_MAX_SHININESS_LOG2  # noqa: F401
 
 
 def _three(name: str, values) -> tuple:
@@ -90,6 +92,30 @@ class PointLightHost:
         out.kind = 1
         out.origin[:] = _three("origin", self.origin)
         out.face_size = self.face_size
+
+
+@dataclass
+class Material:
+    """The highlight of a lit surface (``rtp_material``, include/srt_material.h): a Blinn-Phong term
+    of colour `specular` with the exponent 2 ** shininess_log2 (0 .. 12)."""
+
+    specular: Sequence[float] = (0.0, 0.0, 0.0)
+    shininess_log2: int = 0
+
+    def _struct(self) -> _native.RtpMaterial:
+        out = _native.RtpMaterial(ctypes.sizeof(_native.RtpMaterial))
+        out.specular[:] = _three("specular", self.specular)
+        out.shininess_log2 = int(self.shininess_log2)
+        return out
+
+
+def material_ref(material):
+    """The `material` argument of the rtp calls: a pointer to its struct, or None."""
+    if material is None:
+        return None
+    if not isinstance(material, Material):
+        raise TypeError(f"material must be a Material, got {type(material).__name__}")
+    return ctypes.byref(material._struct())
 
 
 def _pack(lights, struct, kinds):

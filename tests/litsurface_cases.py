@@ -1,0 +1,148 @@
+"""Shared cases of the lit-surface tests (test_litsurface_host.py, test_gpu_litsurface.py): the numpy
+float32 restatement of DESIGN.md section 2 "Lit surfaces", composed from what the suite already
+trusts -- lighting_cases for P, d, N, the class planes and `facing`, surface_cases for the restated
+normal and albedo planes and for tables() / texture(). Only the accumulation is new. Expected values
+come from the oracle and numpy, never from the library. Not a test module.
+
+As in surface_cases, numpy restates the pixel bit for bit only where a normals table is given: the
+fallback normal is rtg's fma arithmetic. Without a normals table and without a material the pixel
+needs no normal at all (the diffuse weight is "Lighting"'s) and is restated; with a material and no
+normals table the device is compared with the host instead.
+"""
+from __future__ import annotations
+
+import functools
+from types import SimpleNamespace
+
+import numpy as np
+
+import lighting_cases as lc
+import surface_cases as sv
+from oracle import srt_oracle as oracle
+
+f32 = np.float32
+W, H = lc.W, lc.H
+AMBIENT = lc.AMBIENT
+SPECULAR = (0.9, 0.7, 0.5)
+SHININESS = (0, 5, 12)
+TEXTURE = (3, 5)  # (TH, TW)
+SENTINELS = (-1, None, 2 ** 31 - 1, -2 ** 31)  # None: the scene's triangle count
+
+
+def positions(offsets) -> np.ndarray:
+    """The image position of every pixel of the W x H frame, (H W, 2) float32: the oracle's expression."""
+    off = np.asarray(offsets, f32)
+    pos = np.empty((H, W, 2), f32)
+    for r in range(H):
+        for x in range(W):
+            pos[r, x] = oracle.pixel_position(x, r, float(off[r, x, 0]), float(off[r, x, 1]), W, H)
+    return pos.reshape(-1, 2)
+
+
+@functools.lru_cache(maxsize=None)
+def edges(name: str) -> SimpleNamespace:
+    """surface_cases.edge_values of the case's frame: one pair per pixel, in row order (read-only)."""
+    c = lc.case(name)
+    return sv.edge_values(c.view, W, H, positions(c.offsets), np.asarray(c.ids).reshape(-1))
+
+
+@functools.lru_cache(maxsize=None)
+def tables(name: str, seed: int = 7) -> SimpleNamespace:
+    """surface_cases.tables for the case's scene, the planted uvs on triangles the frame hits."""
+    c = lc.case(name)
+    return sv.tables(c.n, seed, hit_ids=np.asarray(c.ids).reshape(-1))
+
+
+def clamp01(c):
+    """c > 0 ? (c < 1 ? c : 1) : 0; NaN gives 0."""
+    return np.where(c > 0, np.where(c < 1, c, f32(1)), f32(0)).astype(f32)
+
+
+def falloff(c, qq, light):
+    return c * (f32(light.falloff) / qq) if light.falloff > 0 else c
+
+
+def restate(name: str, normals=None, uvs=None, tex=None, wrap="repeat", filter="bilinear", modulate=False,
+            material=None, lights=None, ambient=AMBIENT) -> np.ndarray:
+    """The definition for the whole frame: (H, W, 4) float32. material: (specular, shininess_log2) or None."""
+    assert material is None or normals is not None, "numpy does not restate the fallback normal"
+    c = lc.case(name)
+    fa = lc.facts(c.view)
+    ev = edges(name)
+    assert np.array_equal(ev.ids.reshape(H, W), fa.ids)
+    planes = sv.expected(ev, normals, uvs, tex, wrap, filter, modulate)
+    albedo = planes.albedo[:, :3].reshape(H, W, 3)
+    u = planes.normal[:, :3].reshape(H, W, 3) if normals is not None else None
+    lights = c.lights if lights is None else lights
+    e = np.broadcast_to(np.array(ambient, f32), (H, W, 3)).copy()
+    s_acc = np.zeros((H, W, 3), f32)
+    with np.errstate(all="ignore"):
+        for light in lights:
+            lt = lc.light_terms(name, light)
+            q = (fa.p - lc.light_origin(name, light)[None, None, :]).astype(f32)
+            qq = lc.dotv(q, q)
+            if u is None:
+                w = lt.w
+            else:
+                w = falloff(clamp01((f32(0) - lc.dotv(u, q)) / np.sqrt(qq)), qq, light)
+            assert w.dtype == f32
+            on = lt.contributes
+            for k in range(3):
+                e[..., k][on] = e[..., k][on] + f32(light.color[k]) * w[on]
+            if material is not None:
+                g = q / np.sqrt(qq)[..., None] + fa.d / np.sqrt(lc.dotv(fa.d, fa.d))[..., None]
+                s = clamp01((f32(0) - lc.dotv(u, g)) / np.sqrt(lc.dotv(g, g)))
+                for _ in range(material[1]):
+                    s = s * s
+                ws = falloff(s, qq, light)
+                assert ws.dtype == f32
+                shines = on & (w > 0)
+                for k in range(3):
+                    s_acc[..., k][shines] = s_acc[..., k][shines] + f32(light.color[k]) * ws[shines]
+        rgb = albedo * e
+        if material is not None:
+            rgb = rgb + np.array(material[0], f32) * s_acc
+    out = np.empty((H, W, 4), f32)
+    out[..., :3] = rgb
+    out[..., 3] = fa.ids.astype(f32)
+    out[~fa.surface] = np.append(fa.background, f32(-1))
+    return out
+
+
+def check_not_vacuous(name: str, normals, material):
+    """Counts of the restatement that keep a test from passing vacuously: the smooth weight differs
+    from the flat one on most contributing pixels, and the highlight is non-zero on many."""
+    flat = restate(name)
+    smooth = restate(name, normals=normals)
+    shiny = restate(name, normals=normals, material=material)
+    surface = lc.facts(lc.case(name).view).surface
+    differs = int((flat[..., :3] != smooth[..., :3]).any(-1).sum())
+    shines = int((shiny[..., :3] != smooth[..., :3]).any(-1).sum())
+    print(f"{name}: {int(surface.sum())} surface pixels, {differs} differ under the normals table, {shines} carry a highlight")
+    assert differs >= (W * H) // 20 and shines >= (W * H) // 100
+
+
+def host_surface(normals=None, uvs=None, tex=None, wrap="repeat", filter="bilinear", modulate=False):
+    from simpleraytracer_amd import Surface
+
+    return Surface(normals, uvs, tex, wrap, filter, modulate)
+
+
+def host_material(material):
+    from simpleraytracer_amd import Material
+
+    return None if material is None else Material(material[0], material[1])
+
+
+def sentinel_ids(name: str):
+    """The case's ids with the sentinels planted in row 5, and where."""
+    c = lc.case(name)
+    ids = np.array(c.ids)
+    values = np.array([c.n if v is None else v for v in SENTINELS], np.int64).astype(np.int32)
+    ids[5, :len(values)] = values
+    changed = np.zeros((H, W), bool)
+    changed[5, :len(values)] = True
+    return ids, changed
+
+
+same_bits = lc.same_bits
