@@ -12,6 +12,7 @@ view's facts and a light's class plane are computed once per session and shared 
 from __future__ import annotations
 
 import functools
+from pathlib import Path
 from types import SimpleNamespace
 
 import numpy as np
@@ -164,22 +165,22 @@ def dotv(a, b):
     return (a[..., 0] * b[..., 0] + a[..., 1] * b[..., 1]) + a[..., 2] * b[..., 2]
 
 
-@functools.lru_cache(maxsize=None)
-def facts(view_path: str) -> SimpleNamespace:
-    """Steps 2 to 4 of the definition for every pixel of the view's frame under the session's sample
-    offsets and the oracle's ids: surface, d, P, N, nn, nd, albedo (float32 arrays)."""
+def frame_facts(view_path: str, w: int, h: int, off, ids=None) -> SimpleNamespace:
+    """Steps 2 to 4 of the definition for every pixel of the file's w x h frame under the offsets
+    `off` and the hit ids `ids` (None: the oracle's own render of the frame): surface, d, P, N, nn,
+    nd, albedo (float32 arrays)."""
     s = oracle.OracleScene(view_path)
-    n, ev, fv = s.n, s.edges(W, H), s.frame(W, H)
+    n, ev, fv = s.n, s.edges(w, h), s.frame(w, h)
     v, alb, bg = s.vertices.astype(f32), s.albedo.astype(f32), s.background.astype(f32)
-    off = sc.random_offsets()
-    ids = s.render(W, H, off)[..., 3].astype(np.int32)
+    with np.errstate(all="ignore"):
+        ids = s.render(w, h, off)[..., 3].astype(np.int32) if ids is None else np.asarray(ids, np.int32)
     s.close()
     eye, base, du, dv = fv[0:3], fv[3:6], fv[6:9], fv[9:12]
     surface = (ids >= 0) & (ids < n)
-    fx, fy, t = np.zeros((H, W), f32), np.zeros((H, W), f32), np.zeros((H, W), f32)
-    for r in range(H):
-        for x in range(W):
-            px, py = oracle.pixel_position(x, r, float(off[r, x, 0]), float(off[r, x, 1]), W, H)
+    fx, fy, t = np.zeros((h, w), f32), np.zeros((h, w), f32), np.zeros((h, w), f32)
+    for r in range(h):
+        for x in range(w):
+            px, py = oracle.pixel_position(x, r, float(off[r, x, 0]), float(off[r, x, 1]), w, h)
             fx[r, x], fy[r, x] = px, py
             if surface[r, x]:
                 i = int(ids[r, x])
@@ -203,13 +204,18 @@ def facts(view_path: str) -> SimpleNamespace:
     return out
 
 
-def light_terms(name: str, light) -> SimpleNamespace:
-    """Steps 6.1, 6.3 to 6.6 of one light for every pixel: facing, contributing, the weight w."""
-    c = case(name)
-    fa = facts(c.view)
-    cls = light_classes(name, light)
+@functools.lru_cache(maxsize=None)
+def facts(view_path: str) -> SimpleNamespace:
+    """frame_facts of a case's view: the 160 x 96 frame under the session's sample offsets and the
+    oracle's ids."""
+    return frame_facts(view_path, W, H, sc.random_offsets())
+
+
+def terms(fa, cls, origin, light) -> SimpleNamespace:
+    """Steps 6.1, 6.3 to 6.6 of one light for every pixel of frame_facts' frame, from the light's class
+    plane and its float32 origin: q, qq, nl, facing, contributing, the weight w."""
     with np.errstate(all="ignore"):
-        q = (fa.p - light_origin(name, light)[None, None, :]).astype(f32)
+        q = (fa.p - np.asarray(origin, f32)[None, None, :]).astype(f32)
         nl = dotv(fa.normal, q)
         facing = ((nl < 0) & (fa.nd < 0)) | ((nl > 0) & (fa.nd > 0))
         contributes = fa.surface & (cls == sc.LIT) & facing
@@ -218,7 +224,28 @@ def light_terms(name: str, light) -> SimpleNamespace:
         cosl = np.where(cosine < 1, cosine, f32(1))
         w = cosl * (f32(light.falloff) / qq) if light.falloff > 0 else cosl
     assert w.dtype == f32
-    return SimpleNamespace(cls=cls, facing=facing, contributes=contributes, w=w)
+    return SimpleNamespace(cls=cls, q=q, qq=qq, nl=nl, facing=facing, contributes=contributes, w=w)
+
+
+def light_terms(name: str, light) -> SimpleNamespace:
+    """terms() of one light of a case."""
+    return terms(facts(case(name).view), light_classes(name, light), light_origin(name, light), light)
+
+
+def accumulate(fa, lights, per_light, ambient) -> np.ndarray:
+    """The definition's accumulation for the whole frame: per_light[l] is terms() of lights[l]."""
+    h, w = fa.ids.shape
+    e = np.broadcast_to(np.array(ambient, f32), (h, w, 3)).copy()
+    with np.errstate(all="ignore"):
+        for light, lt in zip(lights, per_light):
+            on = lt.contributes
+            for k in range(3):
+                e[..., k][on] = e[..., k][on] + f32(light.color[k]) * lt.w[on]  # (no + 0 for the others)
+        out = np.empty((h, w, 4), f32)
+        out[..., :3] = fa.albedo * e
+    out[..., 3] = fa.ids.astype(f32)
+    out[~fa.surface] = np.append(fa.background, f32(-1))
+    return out
 
 
 def restate_rgba(name: str, lights=None, ambient=AMBIENT) -> np.ndarray:
@@ -226,18 +253,72 @@ def restate_rgba(name: str, lights=None, ambient=AMBIENT) -> np.ndarray:
     c = case(name)
     fa = facts(c.view)
     lights = c.lights if lights is None else lights
-    e = np.broadcast_to(np.array(ambient, f32), (H, W, 3)).copy()
-    for light in lights:
-        lt = light_terms(name, light)
-        on = lt.contributes
-        for k in range(3):
-            e[..., k][on] = e[..., k][on] + f32(light.color[k]) * lt.w[on]  # (no + 0 for the others)
-    out = np.empty((H, W, 4), f32)
-    out[..., :3] = fa.albedo * e
-    out[..., 3] = fa.ids.astype(f32)
-    out[~fa.surface] = np.append(fa.background, f32(-1))
     assert np.array_equal(fa.ids, c.ids)
-    return out
+    return accumulate(fa, lights, [light_terms(name, light) for light in lights], ambient)
+
+
+# --- the same restatement for any scene file, frame, offsets and ids (scale_cases) ----------------
+
+@functools.lru_cache(maxsize=None)
+def scene_light_file(path: str, cam: tuple) -> str:
+    """The triangles of the scene file `path` under a spot light's camera."""
+    from scenefile import read_scene, write_custom_scene
+
+    _, bg, v, alb = read_scene(path)
+    out = sc._dir() / f"{Path(path).stem}_{_tag(cam)}.srt"
+    return write_custom_scene(out, v, alb, eye=cam[0:3], lookat=cam[3:6], up=cam[6:9], vfov=cam[9], background=bg)
+
+
+@functools.lru_cache(maxsize=None)
+def scene_point_case(path: str, origin: tuple) -> SimpleNamespace:
+    """What omni_cases.restate reads of a case, for the scene file `path` under a point light."""
+    from scenefile import read_scene, write_custom_scene
+
+    _, bg, v, alb = read_scene(path)
+    faces = []
+    for k in range(6):
+        cam = oc.face_camera(origin, k)
+        faces.append(write_custom_scene(sc._dir() / f"{Path(path).stem}_{_tag(origin)}_face{k}.srt", v, alb, eye=cam[0:3],
+                                        lookat=cam[3:6], up=cam[6:9], vfov=cam[9], background=bg))
+    return SimpleNamespace(view=path, faces=tuple(faces), origin=origin)
+
+
+def scene_light_facts(path: str, w: int, h: int, light, off, ids) -> SimpleNamespace:
+    """What a light's class plane follows from at any bias: shadow_cases.restate_facts (a spot light) or
+    omni_cases.restate (a point light) of the file's w x h frame."""
+    if light.kind == "point":
+        return oc.restate(scene_point_case(path, light.origin), light.face_size, off, ids, w=w, h=h)
+    return sc.restate_facts(path, scene_light_file(path, light.cam), w, h, light.wl, light.hl, off, ids)
+
+
+def scene_light_classes(light, light_facts, ids, bias=None) -> np.ndarray:
+    bias = light.bias if bias is None else bias
+    return (oc.mask_of if light.kind == "point" else sc.mask_of)(light_facts, ids, bias)
+
+
+def scene_light_origin(path: str, light) -> np.ndarray:
+    """light_origin for the scene file `path`."""
+    if light.kind == "point":
+        return np.array(light.origin, f32)
+    s = oracle.OracleScene(scene_light_file(path, light.cam))
+    o = s.frame(light.wl, light.hl)[0:3].copy()
+    s.close()
+    return o
+
+
+def restate_frame(path: str, w: int, h: int, lights, ambient, off, ids, fa=None, light_facts=None) -> SimpleNamespace:
+    """The definition for the w x h frame of the scene file `path` under `lights`, the sample offsets
+    `off` and the hit ids `ids`: the class planes (L, h, w), the RGBA (h, w, 4), and what they follow
+    from (fa: frame_facts; light_facts and terms: one entry per light), which a caller may hand back
+    in to spare their recomputation (they do not depend on colour, falloff or bias)."""
+    fa = frame_facts(path, w, h, off, ids) if fa is None else fa
+    if light_facts is None:
+        light_facts = [scene_light_facts(path, w, h, l, off, ids) for l in lights]
+    classes = [scene_light_classes(l, f, ids) for l, f in zip(lights, light_facts)]
+    per_light = [terms(fa, cls, scene_light_origin(path, l), l) for l, cls in zip(lights, classes)]
+    return SimpleNamespace(classes=np.stack(classes) if lights else np.empty((0, h, w), np.uint8),
+                           rgba=accumulate(fa, lights, per_light, ambient), fa=fa, light_facts=light_facts,
+                           terms=per_light)
 
 
 def expected_classes(name: str, lights=None) -> np.ndarray:
@@ -299,6 +380,9 @@ def host_lights(lights):
 
 def same_bits(name, got, want):
     sc.same_bits(name, got, want)
+
+
+same_bits_or_nan = sc.same_bits_or_nan
 
 
 def assert_same_classes(got, want):

@@ -62,25 +62,46 @@ def falloff(c, qq, light):
     return c * (f32(light.falloff) / qq) if light.falloff > 0 else c
 
 
+def highlight(fa, u, q, qq, shininess_log2: int) -> np.ndarray:
+    """s of the definition: the clamped cosine between u and the negated half vector, squared
+    shininess_log2 times."""
+    with np.errstate(all="ignore"):
+        g = q / np.sqrt(qq)[..., None] + fa.d / np.sqrt(lc.dotv(fa.d, fa.d))[..., None]
+        s = clamp01((f32(0) - lc.dotv(u, g)) / np.sqrt(lc.dotv(g, g)))
+        for _ in range(shininess_log2):
+            s = s * s
+    return s
+
+
 def restate(name: str, normals=None, uvs=None, tex=None, wrap="repeat", filter="bilinear", modulate=False,
             material=None, lights=None, ambient=AMBIENT) -> np.ndarray:
     """The definition for the whole frame: (H, W, 4) float32. material: (specular, shininess_log2) or None."""
-    assert material is None or normals is not None, "numpy does not restate the fallback normal"
     c = lc.case(name)
     fa = lc.facts(c.view)
     ev = edges(name)
-    assert np.array_equal(ev.ids.reshape(H, W), fa.ids)
-    planes = sv.expected(ev, normals, uvs, tex, wrap, filter, modulate)
-    albedo = planes.albedo[:, :3].reshape(H, W, 3)
-    u = planes.normal[:, :3].reshape(H, W, 3) if normals is not None else None
     lights = c.lights if lights is None else lights
-    e = np.broadcast_to(np.array(ambient, f32), (H, W, 3)).copy()
-    s_acc = np.zeros((H, W, 3), f32)
+    surface = SimpleNamespace(normals=normals, uvs=uvs, texture=tex, wrap=wrap, filter=filter, modulate=modulate)
+    return accumulate(fa, ev, lights, [lc.light_terms(name, light) for light in lights], ambient, surface, material)
+
+
+def accumulate(fa, ev, lights, per_light, ambient, surface=None, material=None) -> np.ndarray:
+    """The definition's accumulation for the whole frame of lighting_cases.frame_facts `fa`: ev is
+    surface_cases.edge_values of its pixels in row order, per_light[l] lighting_cases.terms of
+    lights[l], surface an object with normals, uvs, texture, wrap, filter and modulate (None: none)."""
+    rows, cols = fa.ids.shape
+    normals, uvs, tex = (None, None, None) if surface is None else (surface.normals, surface.uvs, surface.texture)
+    wrap, filter, modulate = ("repeat", "bilinear", False) if surface is None else (surface.wrap, surface.filter,
+                                                                                   surface.modulate)
+    assert material is None or normals is not None, "numpy does not restate the fallback normal"
+    assert np.array_equal(ev.ids.reshape(rows, cols), fa.ids)
+    planes = sv.expected(ev, normals, uvs, tex, wrap, filter, modulate)
+    albedo = planes.albedo[:, :3].reshape(rows, cols, 3)
+    u = planes.normal[:, :3].reshape(rows, cols, 3) if normals is not None else None
+    e = np.broadcast_to(np.array(ambient, f32), (rows, cols, 3)).copy()
+    s_acc = np.zeros((rows, cols, 3), f32)
     with np.errstate(all="ignore"):
-        for light in lights:
-            lt = lc.light_terms(name, light)
-            q = (fa.p - lc.light_origin(name, light)[None, None, :]).astype(f32)
-            qq = lc.dotv(q, q)
+        for light, lt in zip(lights, per_light):
+            q, qq = lt.q, lt.qq
             if u is None:
                 w = lt.w
             else:
@@ -90,11 +111,7 @@ def restate(name: str, normals=None, uvs=None, tex=None, wrap="repeat", filter="
             for k in range(3):
                 e[..., k][on] = e[..., k][on] + f32(light.color[k]) * w[on]
             if material is not None:
-                g = q / np.sqrt(qq)[..., None] + fa.d / np.sqrt(lc.dotv(fa.d, fa.d))[..., None]
-                s = clamp01((f32(0) - lc.dotv(u, g)) / np.sqrt(lc.dotv(g, g)))
-                for _ in range(material[1]):
-                    s = s * s
-                ws = falloff(s, qq, light)
+                ws = falloff(highlight(fa, u, q, qq, material[1]), qq, light)
                 assert ws.dtype == f32
                 shines = on & (w > 0)
                 for k in range(3):
@@ -102,11 +119,24 @@ def restate(name: str, normals=None, uvs=None, tex=None, wrap="repeat", filter="
         rgb = albedo * e
         if material is not None:
             rgb = rgb + np.array(material[0], f32) * s_acc
-    out = np.empty((H, W, 4), f32)
+    out = np.empty((rows, cols, 4), f32)
     out[..., :3] = rgb
     out[..., 3] = fa.ids.astype(f32)
     out[~fa.surface] = np.append(fa.background, f32(-1))
     return out
+
+
+def restate_frame(path: str, w: int, h: int, lights, ambient, off, ids, surface=None, material=None, lit=None,
+                  ev=None) -> np.ndarray:
+    """The definition for the w x h frame of the scene file `path` under `lights`, the sample offsets
+    `off` and the hit ids `ids`: (h, w, 4) float32. lit: lighting_cases.restate_frame of the same
+    arguments, ev: surface_cases.edge_values of the frame's pixels, where the caller has them."""
+    import layers_cases
+
+    lit = lc.restate_frame(path, w, h, lights, ambient, off, ids) if lit is None else lit
+    if ev is None:
+        ev = sv.edge_values(path, w, h, layers_cases.pixel_positions(w, h, off), np.asarray(ids).reshape(-1))
+    return accumulate(lit.fa, ev, lights, lit.terms, ambient, surface, material)
 
 
 def check_not_vacuous(name: str, normals, material):

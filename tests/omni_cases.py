@@ -90,13 +90,13 @@ def case(view: str) -> SimpleNamespace:
     return SimpleNamespace(name=view, view=path, faces=faces, origin=ORIGIN, n=len(v), offsets=off, ids=ids)
 
 
-def restate(c, face_size: int, offsets, ids, row_begin: int = 0) -> SimpleNamespace:
+def restate(c, face_size: int, offsets, ids, row_begin: int = 0, w: int = W, h: int = H) -> SimpleNamespace:
     """The definition up to the bias, pixel by pixel, for the band whose offsets and ids are given:
     face (255: no surface), outside (class 2), z, the face frame's closest hit (li, lt), the
-    frustum margin min(g, 1 - g) and whether the pixel is near a cube seam."""
+    frustum margin min(g, 1 - g) and whether the pixel is near a cube seam. The view frame is w x h."""
     sv = oracle.OracleScene(c.view)
     n = sv.n
-    ev, fv = sv.edges(W, H), sv.frame(W, H)
+    ev, fv = sv.edges(w, h), sv.frame(w, h)
     sv.close()
     el, rows_f, origin_f = [], [], []
     for k in range(6):
@@ -111,17 +111,17 @@ def restate(c, face_size: int, offsets, ids, row_begin: int = 0) -> SimpleNamesp
     lorigin = origin_f[0]
     eye, base, du, dv = fv[0:3], fv[3:6], fv[6:9], fv[9:12]
     rows = ids.shape[0]
-    out = SimpleNamespace(face=np.full((rows, W), NO_FACE, np.uint8), outside=np.zeros((rows, W), bool),
-                          z=np.zeros((rows, W), f32), li=np.full((rows, W), -1, np.int64),
-                          lt=np.full((rows, W), np.inf, f32), margin=np.full((rows, W), np.inf),
-                          seam=np.zeros((rows, W), bool))
+    out = SimpleNamespace(face=np.full((rows, w), NO_FACE, np.uint8), outside=np.zeros((rows, w), bool),
+                          z=np.zeros((rows, w), f32), li=np.full((rows, w), -1, np.int64),
+                          lt=np.full((rows, w), np.inf, f32), margin=np.full((rows, w), np.inf),
+                          seam=np.zeros((rows, w), bool))
     with np.errstate(all="ignore"):
         for r in range(rows):
-            for x in range(W):
+            for x in range(w):
                 i = int(ids[r, x])
                 if not 0 <= i < n:
                     continue
-                fx, fy = oracle.pixel_position(x, row_begin + r, float(offsets[r, x, 0]), float(offsets[r, x, 1]), W, H)
+                fx, fy = oracle.pixel_position(x, row_begin + r, float(offsets[r, x, 0]), float(offsets[r, x, 1]), w, h)
                 hit, t, _ = oracle.closest_hit(ev[i:i + 1], fx, fy)
                 assert hit == 0, f"pixel ({x}, {row_begin + r}): id {i} does not hit at its own position"
                 fx, fy, t = f32(fx), f32(fy), f32(t)

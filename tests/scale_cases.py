@@ -305,3 +305,213 @@ def assert_shadow_classes(mask):
     """The k = 0 mask holds shadowed, lit and outside-the-frustum pixels, 2 % of the frame each."""
     counts = [int((np.asarray(mask) == c).sum()) for c in range(3)]
     assert all(n >= 0.02 * np.asarray(mask).size for n in counts), f"degenerate light: class counts {counts}"
+
+
+# Lights, surfaces and materials (rto*, rtd*, rtv*, rtp*): what these families compute after the hit,
+# across scale and at the edges of float32.
+#
+# The rig of S times 2^k: the spot light above, a second one on the other side of S, and a point light
+# at the first one's eye, every position times 2^k; count_cases' colours and ambient. c of "Lighting"
+# is scale-free (nl ~ s^3, sqrt(nn) ~ s^2, sqrt(qq) ~ s, every factor a power of two); the falloffs are
+# (0, f1 4^k, f2 4^k), so that falloff / qq is too: the lit frame of S times 2^k has the bits of k = 0
+# while nn = N . N (s^4) stays a normal number. It does not at k = -30 (nn of S's small triangles is
+# subnormal, or 0) and at k = +30 (nn of the two covering triangles is +inf: c = 0, they go dark);
+# there the frame is compared at its own k only. The bias is relative (thr = z - b z), so the masks at
+# bias 0 are those of k = 0; the run with the bias RIG_BIAS 2^k is not scale-free and probes b z.
+#
+# The surface tables do not scale: weights, uv and the normal plane are scale-free. The magnitude
+# sweep multiplies the normals table by 2^m at k = 0, so that Ns . Ns of "Vertex attributes" is 0,
+# subnormal, ordinary, huge and +inf.
+#
+# The library refuses a point light's origin beyond |o_k| <= 2^16 (DESIGN.md section 2 "Omni shadow":
+# fl32(o + axis) must stay a direction), and the first spot light's eye is (3, 2, 1) 2^k: the rig holds
+# the point light up to k = 14, which therefore stands beside 16 among the large scales, and at k = 16
+# and 30 the tests assert the refusal and light the scene with the two spot lights.
+#
+# Counts obtained (CPU, numpy; conditions on the inputs, asserted with their thresholds by
+# test_scale_host.test_rig_guards and test_sweep_and_shininess_guards). 14 400 pixels, 7 534 of them hit:
+#   k = 0     light 0 (spot): 518 shadowed, 4 402 lit, 4 295 contributing (thresholds 100, 100)
+#             light 1 (spot): 195 shadowed, 2 249 lit, 2 061 contributing
+#             light 2 (point): 659 shadowed, 6 875 lit, 6 628 contributing
+#             4 669 hit pixels (62 %) under two or more lights (threshold: a fifth)
+#   k = -30   12 984 (lit pixel, light) pairs, nn nonzero subnormal in 1 398 (10.8 %; threshold 5 %);
+#             nn == 0 in 0: S yields none (its two degenerate triangles are never hit)
+#   k = +30   nn == +inf at 6 356 pixels (threshold 100): the covering triangles, dark but for the ambient
+#   normals table times 2^m: Ns . Ns is 0 at all 7 534 hit pixels for m = -75 (threshold 100), nonzero
+#             subnormal at all of them for m = -64 (threshold 5 %), ordinary for m = 0, finite for m = 63,
+#             +inf at 131 pixels for m = 64 (threshold 100)
+#   shininess_log2 = 12: s^4096 is a nonzero subnormal in 470 (pixel, light) pairs (threshold 16; table
+#             seeds 1 .. 79 give 1 to 1 089, seed 27 of test_gpu_surface.py gives 4); under the black
+#             texture 196 pixels hold a subnormal rgb value
+LIGHT2_EYE, LIGHT2_LOOK, LIGHT2_VFOV = (-3.0, 1.5, 0.5), (1.5, 0.5, 9.0), 50.0
+FACE = 64
+RIG_KS = (-30, -21, 0, 14, 16, 30)  # (the point light's origin is accepted up to k = 14: 3 x 2^14 <= 2^16)
+RIG_FALLOFF = (0.0, 16.0, 8.0)  # times 4^k
+RIG_BIAS = 0.25                 # times 2^k, in the biased run
+TABLE_SEED, TEXTURE_SEED, TEXTURE = 12, 11, (3, 5)  # (of seeds 1 .. 79 the table with the most subnormal highlights)
+SWEEP_MS = (-75, -64, 0, 63, 64)
+SPECULAR = (0.9, 0.7, 0.5)
+SHININESS = (0, 1, 12)
+
+
+def light2_camera(k: int = 0):
+    eye, look = scaled_camera(LIGHT2_EYE, LIGHT2_LOOK, k)
+    return (*[float(v) for v in eye], *[float(v) for v in look], *LIGHT_UP, LIGHT2_VFOV)
+
+
+def point_origin(k: int = 0):
+    return tuple(float(v) for v in scaled_camera(LIGHT_EYE, LIGHT_LOOK, k)[0])
+
+
+def point_allowed(k: int) -> bool:
+    """DESIGN.md section 2 "Omni shadow": a point light's origin is refused beyond |o_k| <= 2^16."""
+    return max(abs(v) for v in point_origin(k)) <= 65536.0
+
+
+def rig(k: int = 0, biased: bool = False, point: bool | None = None):
+    """The lights of S times 2^k (lighting_cases.spot / point): spot, spot and -- point=None: where
+    the library accepts its origin -- the point light."""
+    import count_cases as cc
+    import lighting_cases as lt
+
+    f = [float(np.ldexp(f32(v), 2 * k)) for v in RIG_FALLOFF]
+    bias = float(np.ldexp(f32(RIG_BIAS), k)) if biased else 0.0
+    lights = [lt.spot(light_camera(k), LIGHT_W, LIGHT_H, cc.LIGHT_COLORS[0], f[0], bias),
+              lt.spot(light2_camera(k), LIGHT_W, LIGHT_H, cc.LIGHT_COLORS[1], f[1], bias)]
+    if point_allowed(k) if point is None else point:
+        assert point_allowed(k), k
+        lights.append(lt.point(point_origin(k), FACE, cc.LIGHT_COLORS[2], f[2], bias))
+    return lights
+
+
+def ambient():
+    import count_cases as cc
+
+    return cc.AMBIENT
+
+
+@functools.lru_cache(maxsize=None)
+def _rig_facts(k: int):
+    """(frame_facts, [light facts]) of S times 2^k under rig(k): what every run at k shares."""
+    import lighting_cases as lt
+
+    c = case(s_name(k))
+    off, ids = offsets(W, H), frame_ids(c.name)
+    return (lt.frame_facts(c.path, W, H, off, ids),
+            [lt.scene_light_facts(c.path, W, H, light, off, ids) for light in rig(k)])
+
+
+@functools.lru_cache(maxsize=None)
+def lit(k: int, biased: bool = False, point: bool | None = None) -> SimpleNamespace:
+    """lighting_cases.restate_frame of S times 2^k under rig(k, biased, point): classes, rgba, fa,
+    terms (read-only, once per session)."""
+    import lighting_cases as lt
+
+    c = case(s_name(k))
+    fa, light_facts = _rig_facts(k)
+    lights = rig(k, biased, point)
+    out = lt.restate_frame(c.path, W, H, lights, ambient(), offsets(W, H), frame_ids(c.name), fa=fa,
+                           light_facts=light_facts[:len(lights)])
+    for a in (out.classes, out.rgba):
+        a.setflags(write=False)
+    return out
+
+
+@functools.lru_cache(maxsize=None)
+def pixel_edges(k: int) -> SimpleNamespace:
+    """surface_cases.edge_values of every pixel of the frame of S times 2^k, in row order."""
+    import surface_cases as sv
+
+    c = case(s_name(k))
+    return sv.edge_values(c.path, W, H, lc.pixel_positions(W, H, offsets(W, H)), frame_ids(c.name).reshape(-1))
+
+
+@functools.lru_cache(maxsize=None)
+def surface_tables() -> SimpleNamespace:
+    """surface_cases.tables for S (the planted uvs on triangles the frame hits) and a 3 x 5 texture."""
+    import surface_cases as sv
+
+    tb = sv.tables(len(s_geometry()[0]), TABLE_SEED, hit_ids=frame_ids(s_name(0)).reshape(-1))
+    tb.texture = sv.texture(*TEXTURE, TEXTURE_SEED)
+    return tb
+
+
+@functools.lru_cache(maxsize=None)
+def surface(m: int = 0, wrap: str = "repeat", filter: str = "bilinear"):
+    """The Surface of numpy tables: the normals table times 2^m (float32), uvs and the texture."""
+    from simpleraytracer_amd import Surface
+
+    tb = surface_tables()
+    with np.errstate(all="ignore"):
+        normals = (tb.normals * f32(2.0) ** m).astype(f32) if m else tb.normals
+    normals.setflags(write=False)
+    return Surface(normals, tb.uvs, tb.texture, wrap, filter)
+
+
+@functools.lru_cache(maxsize=None)
+def surface_planes(k: int, m: int = 0, wrap: str = "repeat", filter: str = "bilinear") -> SimpleNamespace:
+    """surface_cases.expected of the frame of S times 2^k under surface(m, wrap, filter)."""
+    import surface_cases as sv
+
+    s = surface(m, wrap, filter)
+    return sv.expected(pixel_edges(k), s.normals, s.uvs, s.texture, wrap, filter)
+
+
+@functools.lru_cache(maxsize=None)
+def black_surface():
+    """surface() with a black 1 x 1 texture: the albedo plane is 0, so a lit pixel is its highlight alone
+    (specular . S) and a subnormal S, which any albedo . E of ordinary size absorbs, reaches the output."""
+    from simpleraytracer_amd import Surface
+
+    tb = surface_tables()
+    black = np.zeros((1, 1, 4), f32)
+    black.setflags(write=False)
+    return Surface(tb.normals, tb.uvs, black)
+
+
+def lit_surface(k: int, m: int = 0, material=None, point: bool | None = None, black: bool = False) -> np.ndarray:
+    """litsurface_cases' restatement of S times 2^k under rig(k, point=point) and surface(m), or
+    black_surface(): (H, W, 4) float32."""
+    import litsurface_cases as pc
+
+    base = lit(k, False, point)
+    return pc.accumulate(base.fa, pixel_edges(k), rig(k, False, point), base.terms, ambient(),
+                         black_surface() if black else surface(m), material)
+
+
+def check_planes(what: str, got: dict, exp):
+    """The four planes of a surface call against surface_cases.expected, on the bits (a NaN for a NaN)."""
+    from shadow_cases import same_bits_or_nan
+
+    for name in ("uv", "albedo", "normal", "rgba"):
+        same_bits_or_nan(f"{what}: {name}", np.asarray(got[name]).reshape(-1, got[name].shape[-1]), getattr(exp, name))
+
+
+def table_nn(m: int) -> np.ndarray:
+    """dotp(Ns, Ns) of the hit pixels of the k = 0 frame under the normals table times 2^m."""
+    import surface_cases as sv
+
+    ev = pixel_edges(0)
+    ns = sv.interpolate(ev, surface(m).normals)
+    return sv.dotp(ns, ns)[ev.valid]
+
+
+def subnormal(a) -> np.ndarray:
+    """Nonzero and below the smallest normal float32."""
+    a = np.abs(np.asarray(a, f32))
+    return (a > 0) & (a < np.finfo(f32).tiny)
+
+
+def highlights(k: int, shininess_log2: int):
+    """(s, shines) per light: litsurface_cases.highlight under surface(0), and where it is added."""
+    import lighting_cases as lt
+    import litsurface_cases as pc
+
+    fa = lit(k).fa
+    u = surface_planes(k).normal[:, :3].reshape(H, W, 3)
+    out = []
+    with np.errstate(all="ignore"):
+        for light, t in zip(rig(k), lit(k).terms):
+            w = pc.falloff(pc.clamp01((f32(0) - lt.dotv(u, t.q)) / np.sqrt(t.qq)), t.qq, light)
+            out.append((pc.highlight(fa, u, t.q, t.qq, shininess_log2), t.contributes & (w > 0)))
+    return out

@@ -125,8 +125,10 @@ def dotp(a, b) -> np.float32:
     return f32(f32(f32(a[0] * b[0]) + f32(a[1] * b[1])) + f32(a[2] * b[2]))
 
 
-def restate(view: str, light: str, w: int, h: int, wl: int, hl: int, offsets, ids, bias: float, row_begin: int = 0):
-    """The definition, pixel by pixel: the mask of the band whose offsets and ids are given."""
+def restate_facts(view: str, light: str, w: int, h: int, wl: int, hl: int, offsets, ids, row_begin: int = 0):
+    """The definition up to the bias, pixel by pixel, for the band whose offsets and ids are given:
+    surface (the id lies inside the scene), outside (class 2), z and the light frame's closest hit
+    (li, lt)."""
     sv, sl = oracle.OracleScene(view), oracle.OracleScene(light)
     n = sv.n
     assert sl.n == n
@@ -137,15 +139,17 @@ def restate(view: str, light: str, w: int, h: int, wl: int, hl: int, offsets, id
     eye, base, du, dv = fv[0:3], fv[3:6], fv[6:9], fv[9:12]
     lorigin = fl[0:3]
     px, py, pz = projection_rows(fl)
-    b = f32(bias)
     rows = ids.shape[0]
-    mask = np.full((rows, w), NO_SURFACE, np.uint8)
+    out = SimpleNamespace(surface=np.zeros((rows, w), bool), outside=np.zeros((rows, w), bool),
+                          z=np.zeros((rows, w), f32), li=np.full((rows, w), -1, np.int64),
+                          lt=np.full((rows, w), np.inf, f32))
     with np.errstate(all="ignore"):
         for r in range(rows):
             for x in range(w):
                 i = int(ids[r, x])
                 if not 0 <= i < n:
                     continue
+                out.surface[r, x] = True
                 fx, fy = oracle.pixel_position(x, row_begin + r, float(offsets[r, x, 0]), float(offsets[r, x, 1]), w, h)
                 hit, t, _ = oracle.closest_hit(ev[i:i + 1], fx, fy)
                 assert hit == 0, f"pixel ({x}, {row_begin + r}): id {i} does not hit at its own position"
@@ -155,17 +159,36 @@ def restate(view: str, light: str, w: int, h: int, wl: int, hl: int, offsets, id
                 q = [f32(p[k] - lorigin[k]) for k in range(3)]
                 z = dotp(q, pz)
                 if not (z > 0 and z < np.inf):
-                    mask[r, x] = OUTSIDE
+                    out.outside[r, x] = True
                     continue
                 gx, gy = f32(dotp(q, px) / z), f32(dotp(q, py) / z)
                 if not (0 <= gx <= 1 and 0 <= gy <= 1):
-                    mask[r, x] = OUTSIDE
+                    out.outside[r, x] = True
                     continue
                 li, lt, _ = oracle.closest_hit(el, float(gx), float(gy))
-                lt = f32(lt) if li >= 0 else f32(np.inf)
-                thr = f32(z - f32(b * z))
-                mask[r, x] = LIT if (li == i or lt >= thr) else SHADOWED
+                out.z[r, x] = z
+                out.li[r, x] = li
+                out.lt[r, x] = f32(lt) if li >= 0 else f32(np.inf)
+    for a in vars(out).values():
+        a.setflags(write=False)
+    return out
+
+
+def mask_of(facts, ids, bias: float) -> np.ndarray:
+    """The last two steps for every pixel: thr = z - b z (two roundings), lit iff li == id or lt >= thr."""
+    b = f32(bias)
+    with np.errstate(all="ignore"):
+        thr = (facts.z - (b * facts.z).astype(f32)).astype(f32)
+    lit = (facts.li == ids) | (facts.lt >= thr)
+    mask = np.where(lit, LIT, SHADOWED).astype(np.uint8)
+    mask[facts.outside] = OUTSIDE
+    mask[~facts.surface] = NO_SURFACE
     return mask
+
+
+def restate(view: str, light: str, w: int, h: int, wl: int, hl: int, offsets, ids, bias: float, row_begin: int = 0):
+    """The definition, pixel by pixel: the mask of the band whose offsets and ids are given."""
+    return mask_of(restate_facts(view, light, w, h, wl, hl, offsets, ids, row_begin), ids, bias)
 
 
 @functools.lru_cache(maxsize=None)
@@ -195,6 +218,17 @@ def same_bits(name, got, want):
     assert g.shape == w.shape, f"{name}: shape {np.shape(got)} != {np.shape(want)}"
     bad = np.flatnonzero(g != w)
     assert bad.size == 0, f"{name}: {bad.size} values differ, first at {bad[0]}: {g[bad[0]]:#x} != {w[bad[0]]:#x}"
+
+
+def same_bits_or_nan(name, got, want):
+    """same_bits, except that where `want` holds a NaN `got` must hold a NaN of any sign and payload: a
+    generated NaN's bits are the platform's, not the definition's."""
+    g, w = np.ascontiguousarray(got, f32).reshape(-1), np.ascontiguousarray(want, f32).reshape(-1)
+    assert g.shape == w.shape, f"{name}: shape {np.shape(got)} != {np.shape(want)}"
+    nan = np.isnan(w)
+    bad = np.flatnonzero(np.where(nan, ~np.isnan(g), g.view(np.uint32) != w.view(np.uint32)))
+    assert bad.size == 0, (f"{name}: {bad.size} values differ, first at {bad[0]}: {g.view(np.uint32)[bad[0]]:#x} != "
+                           f"{w.view(np.uint32)[bad[0]]:#x}")
 
 
 def dimmed(shade_rgba, mask, dim: float) -> np.ndarray:

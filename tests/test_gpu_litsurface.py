@@ -89,6 +89,25 @@ def test_device_equals_the_host_and_the_restatement(gpu, monkeypatch, name):
     lc.assert_same_classes(classes, hclasses)
 
 
+@pytest.mark.parametrize("shininess_log2", [0, 1, 12])
+def test_every_shininess_equals_the_restatement_and_the_host(gpu, monkeypatch, shininess_log2):
+    """roomA under the normals table: no squaring, one, and twelve (s^4096: most highlights underflow)."""
+    default_env(monkeypatch)
+    name = "roomA"
+    c = lc.case(name)
+    tb = pc.tables(name)
+    s = full_surface(name)
+    material = (pc.SPECULAR, shininess_log2)
+    rig = SurfaceRig(c)
+    rgba, classes = rig.light_surface(s, material)
+    rig.close()
+    hrgba, hclasses = host(c, s, material)
+    lc.assert_same_classes(classes, lc.expected(name).classes)
+    lc.assert_same_classes(classes, hclasses)
+    pc.same_bits("rgba against the host's", rgba, hrgba)
+    pc.same_bits("rgba", rgba, pc.restate(name, tb.normals, tb.uvs, s.texture, material=material))
+
+
 def test_sixteen_light_frames(gpu, monkeypatch):
     default_env(monkeypatch)
     c = lc.case("full")
