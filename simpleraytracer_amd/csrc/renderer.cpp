@@ -12,6 +12,7 @@
 #include "comm.h"
 #include "engine.h"
 #include "lighting_math.h"
+#include "rays.h"
 #include "render.h"
 
 namespace srt {
@@ -173,6 +174,10 @@ DeviceScene::~DeviceScene() {
         FreeOrderScratch(*m_scratch);
         delete m_scratch;
     }
+    if (m_rays != nullptr) {
+        FreeRayTree(*m_rays);
+        delete m_rays;
+    }
     (void)hipFree(m_block_ext);
     (void)hipFree(m_setup);
     (void)hipFree(m_stream);
@@ -279,6 +284,7 @@ void DeviceScene::SetVertices(const float* d_vertices, bool reorder, hipStream_t
         AllocOrderScratch(*m_scratch, m_n, stream);  // (first use only)
     }
     OrderAfterPrevious(stream);
+    m_rays_stale = true;  // the world-space tree is a function of the vertices alone (rays.h)
     HipCheck(hipMemcpyAsync(m_vertices, d_vertices, m_n * 9 * sizeof(float), hipMemcpyDeviceToDevice, stream),
              "hipMemcpyAsync(vertices)");
     // (a failed enqueue below leaves the copy queued: the pose counts as changed either way)
@@ -291,6 +297,89 @@ void DeviceScene::SetVertices(const float* d_vertices, bool reorder, hipStream_t
     }
     RecordOrder(stream);
     PoseChanged(true);
+}
+
+// Ray queries (rays.h). The tree is keyed on the vertices only, so PoseChanged leaves it alone and
+// SetVertices marks it stale itself.
+const RayTree* DeviceScene::EnsureRayTree(hipStream_t stream) const {
+    const char* mode = std::getenv("SRT_RAYS");
+    if (m_n == 0 || (mode != nullptr && std::strcmp(mode, "brute") == 0)) {
+        return nullptr;
+    }
+    if (m_rays == nullptr) {
+        RayTree* tree = new RayTree{};
+        try {
+            AllocRayTree(*tree, m_n, stream);
+        } catch (...) {
+            delete tree;
+            throw;
+        }
+        m_rays = tree;
+        m_rays_stale = true;
+        ++m_ray_stats.allocations;
+    }
+    if (m_rays_stale) {
+        EnqueueRayTreeBuild(*m_rays, m_vertices, m_n, stream);
+        m_rays_stale = false;
+        ++m_ray_stats.builds;
+    }
+    return m_rays;
+}
+
+void DeviceScene::LogRayStats() const {
+    const char* e = std::getenv("SRT_SETUP_LOG");
+    if (e == nullptr || *e == '\0' || std::strcmp(e, "0") == 0) {
+        return;
+    }
+    std::fprintf(stderr, "srt rays: scene %p builds %llu allocations %llu\n", static_cast<const void*>(this),
+                 m_ray_stats.builds, m_ray_stats.allocations);
+    std::fflush(stderr);
+}
+
+void DeviceScene::BuildRays(hipStream_t stream) const {
+    OrderAfterPrevious(stream);
+    try {
+        (void)EnsureRayTree(stream);
+    } catch (...) {
+        m_rays_stale = true;
+        RecordOrder(stream);
+        throw;
+    }
+    RecordOrder(stream);
+    LogRayStats();
+}
+
+void DeviceScene::Closest(const float* d_rays, std::size_t count, int* d_ids, float* d_t, float* d_bary,
+                          hipStream_t stream) const {
+    if (count == 0) {
+        return;
+    }
+    OrderAfterPrevious(stream);
+    try {
+        const RayTree* tree = EnsureRayTree(stream);
+        LaunchRayClosest(tree, m_vertices, m_n, d_rays, count, d_ids, d_t, d_bary, stream);
+    } catch (...) {
+        RecordOrder(stream);
+        throw;
+    }
+    RecordOrder(stream);
+    LogRayStats();
+}
+
+void DeviceScene::Occluded(const float* d_rays, std::size_t count, unsigned char* d_out, hipStream_t stream) const {
+    if (count == 0) {
+        return;
+    }
+    OrderAfterPrevious(stream);
+    try {
+        const RayTree* tree = EnsureRayTree(stream);
+        LaunchRayOccluded(tree, m_vertices, m_n, d_rays, count, d_out, stream);
+    } catch (...) {
+        RecordOrder(stream);
+        throw;
+    }
+    RecordOrder(stream);
+    LogRayStats();
 }
 
 // The block extents of the prepared frame, once per Prepare (on the first binned trace's stream,

@@ -24,6 +24,7 @@ struct StageEvents;  // render.h
 struct OrderScratch;  // render.h
 struct SurfaceArgs;   // render.h
 struct LitSurface;    // render.h
+struct RayTree;       // rays.h
 
 // Throws std::runtime_error("HIP error: <what>: <reason>") on failure.
 void HipCheck(hipError_t err, const char* what);
@@ -224,6 +225,26 @@ public:
     void SetCamera(const Camera& camera, bool reorder, hipStream_t stream);
     void SetVertices(const float* d_vertices, bool reorder, hipStream_t stream);
 
+    // Ray queries (include/srt_rays.h; rays.h): the closest hit (d_ids, d_t and, non-null, d_bary:
+    // count x 2) or the occlusion byte (d_out) of `count` caller-supplied rays (d_rays: count x 8
+    // floats, 16-byte aligned), answered from the scene's world-space tree -- or, env SRT_RAYS=brute
+    // (read per call), by brute force over the vertices, which needs no tree. The tree depends on
+    // the vertices only: no Prepare is needed, a camera move leaves it alone, SetVertices marks it
+    // stale. It is built by the first call that needs it (or BuildRays), on that call's stream, and
+    // rebuilt in the same buffers by the first call after SetVertices: allocation at the first
+    // build only, no host synchronisation. Calls on the scene for the ordering rule.
+    void BuildRays(hipStream_t stream) const;
+    void Closest(const float* d_rays, std::size_t count, int* d_ids, float* d_t, float* d_bary,
+                 hipStream_t stream) const;
+    void Occluded(const float* d_rays, std::size_t count, unsigned char* d_out, hipStream_t stream) const;
+    // Builds of the tree so far and the builds that allocated (0 or 1). Env SRT_SETUP_LOG=1 prints
+    // them to stderr after every ray call ("srt rays: ...").
+    struct RayStats {
+        unsigned long long builds = 0;
+        unsigned long long allocations = 0;
+    };
+    RayStats ray_stats() const { return m_ray_stats; }
+
     std::size_t width() const { return m_width; }
     // The spatial order (device, triangles entries) and the time its build took at load (ms).
     const unsigned* order() const { return m_order; }
@@ -280,6 +301,13 @@ private:
     // Sort scratch of the reordering updates (render.h OrderScratch): sizes depend on the triangle
     // count only; allocated by the first such update, freed with the scene.
     OrderScratch* m_scratch = nullptr;
+    // The world-space tree of the ray queries (rays.h): null until the first build; stale after
+    // SetVertices until the next ray call rebuilds it in place.
+    mutable RayTree* m_rays = nullptr;
+    mutable bool m_rays_stale = true;
+    mutable RayStats m_ray_stats{};
+    const RayTree* EnsureRayTree(hipStream_t stream) const;  // (re)built on `stream` if need be; null: brute force
+    void LogRayStats() const;
     // The one place that knows what a pose (camera, vertices) shapes: every cache below that is a
     // function of it is dropped or marked for its lazy rebuild (renderer.cpp).
     void PoseChanged(bool vertices);

@@ -3,6 +3,7 @@
 
 #include <algorithm>
 #include <cmath>
+#include <cstdint>
 #include <cstring>
 #include <exception>
 #include <memory>
@@ -14,6 +15,8 @@
 #include "lighting_math.h"
 #include "material_math.h"
 #include "omni_math.h"
+#include "ray_math.h"
+#include "rays.h"
 #include "render.h"
 #include "renderer.h"
 #include "scene.h"
@@ -25,6 +28,7 @@
 #include "srt_motion.h"
 #include "srt_omni.h"
 #include "srt_query.h"
+#include "srt_rays.h"
 #include "srt_render.h"
 #include "srt_samples.h"
 #include "srt_surface.h"
@@ -1923,6 +1927,126 @@ RTP_API int rtpLightSurfaceHost(const char* scene_path, size_t width, size_t hei
     const srt::HostMaterial mat{{lit.specular[0], lit.specular[1], lit.specular[2]}, lit.shininess_log2};
     return LightHost(scene_path, width, height, lights, count, ambient, &tables, lit.material ? &mat : nullptr, offsets,
                      ids, row_begin, row_count, rgba, classes);
+}
+
+// Ray queries (include/srt_rays.h): the rtr family.
+static_assert(RTR_RAY_FLOATS * sizeof(float) == sizeof(srt::Ray), "include/srt_rays.h and ray_math.h agree");
+
+namespace {
+
+void CheckRays(const float* rays, const char* name, bool device) {
+    if (rays == nullptr) {
+        throw std::runtime_error(std::string("Bad buffer argument: ") + name + " is NULL");
+    }
+    if (device && reinterpret_cast<std::uintptr_t>(rays) % 16 != 0) {
+        throw std::runtime_error(std::string("Bad buffer argument: ") + name + " is not 16-byte aligned");
+    }
+}
+
+bool CheckedBoxClause(int flags) {
+    if ((flags & ~RTR_NO_BOX_CLAUSE) != 0) {
+        throw std::runtime_error("Unknown ray flags " + std::to_string(flags));
+    }
+    return (flags & RTR_NO_BOX_CLAUSE) == 0;
+}
+
+}  // namespace
+
+RTR_API int rtrBuildAsync(srt_device_scene scene, void* stream) {
+    return Guarded([&] {
+        if (scene == nullptr) {
+            throw std::runtime_error("Bad scene handle");
+        }
+        srt::DeviceScene* s = FromHandle(scene);
+        Bind bind(s->device());
+        s->BuildRays(static_cast<hipStream_t>(stream));
+    });
+}
+
+RTR_API int rtrClosestAsync(srt_device_scene scene, const float* d_rays, size_t count, int* d_ids, float* d_t,
+                            float* d_bary, void* stream) {
+    return Guarded([&] {
+        if (scene == nullptr) {
+            throw std::runtime_error("Bad scene handle");
+        }
+        if (count != 0) {
+            CheckRays(d_rays, "d_rays", true);
+            if (d_ids == nullptr) {
+                throw std::runtime_error("Bad buffer argument: d_ids is NULL");
+            }
+            if (d_t == nullptr) {
+                throw std::runtime_error("Bad buffer argument: d_t is NULL");
+            }
+        }
+        srt::DeviceScene* s = FromHandle(scene);
+        Bind bind(s->device());
+        s->Closest(d_rays, count, d_ids, d_t, d_bary, static_cast<hipStream_t>(stream));
+    });
+}
+
+RTR_API int rtrOccludedAsync(srt_device_scene scene, const float* d_rays, size_t count, unsigned char* d_out,
+                             void* stream) {
+    return Guarded([&] {
+        if (scene == nullptr) {
+            throw std::runtime_error("Bad scene handle");
+        }
+        if (count != 0) {
+            CheckRays(d_rays, "d_rays", true);
+            if (d_out == nullptr) {
+                throw std::runtime_error("Bad buffer argument: d_out is NULL");
+            }
+        }
+        srt::DeviceScene* s = FromHandle(scene);
+        Bind bind(s->device());
+        s->Occluded(d_rays, count, d_out, static_cast<hipStream_t>(stream));
+    });
+}
+
+RTR_API int rtrClosestHostFlags(const char* scene_path, const float* rays, size_t count, int* ids, float* t,
+                                float* bary, int flags) {
+    return Guarded([&] {
+        const bool box_clause = CheckedBoxClause(flags);
+        if (scene_path == nullptr) {
+            throw std::runtime_error("Bad argument: scene_path is NULL");
+        }
+        if (count != 0) {
+            CheckRays(rays, "rays", false);
+            if (ids == nullptr) {
+                throw std::runtime_error("Bad buffer argument: ids is NULL");
+            }
+            if (t == nullptr) {
+                throw std::runtime_error("Bad buffer argument: t is NULL");
+            }
+        }
+        const srt::Scene scene = srt::LoadScene(scene_path);
+        srt::HostRayClosest(scene, rays, count, ids, t, bary, box_clause);
+    });
+}
+
+RTR_API int rtrOccludedHostFlags(const char* scene_path, const float* rays, size_t count, unsigned char* out,
+                                 int flags) {
+    return Guarded([&] {
+        const bool box_clause = CheckedBoxClause(flags);
+        if (scene_path == nullptr) {
+            throw std::runtime_error("Bad argument: scene_path is NULL");
+        }
+        if (count != 0) {
+            CheckRays(rays, "rays", false);
+            if (out == nullptr) {
+                throw std::runtime_error("Bad buffer argument: out is NULL");
+            }
+        }
+        const srt::Scene scene = srt::LoadScene(scene_path);
+        srt::HostRayOccluded(scene, rays, count, out, box_clause);
+    });
+}
+
+RTR_API int rtrClosestHost(const char* scene_path, const float* rays, size_t count, int* ids, float* t, float* bary) {
+    return rtrClosestHostFlags(scene_path, rays, count, ids, t, bary, RTR_BOX_CLAUSE);
+}
+
+RTR_API int rtrOccludedHost(const char* scene_path, const float* rays, size_t count, unsigned char* out) {
+    return rtrOccludedHostFlags(scene_path, rays, count, out, RTR_BOX_CLAUSE);
 }
 
 #ifdef SRT_DIAG

@@ -2,7 +2,8 @@
 (include/srt_query.h), G-buffer outputs (include/srt_gbuffer.h), multi-sample frames
 (include/srt_samples.h), spot-light shadow masks (include/srt_light.h), omni-light shadow masks
 (include/srt_omni.h), direct lighting (include/srt_lighting.h; the lights: lighting.py), dynamic
-scenes (include/srt_motion.h) and vertex attributes (include/srt_surface.h).
+scenes (include/srt_motion.h), vertex attributes (include/srt_surface.h) and ray queries
+(include/srt_rays.h).
 
 ``DeviceScene`` keeps a scene resident on one GPU and launches the two stages on a caller's
 HIP stream with caller-owned device buffers (torch tensors or raw pointers):
@@ -19,6 +20,7 @@ HIP stream with caller-owned device buffers (torch tensors or raw pointers):
     scene.light(lights, offsets, ids, rgba, ambient, stream=s)   # the lit picture under several lights (also render_lit())
     scene.set_camera(camera, stream=s)                           # move the camera in place (also set_vertices(), OmniLight.set_origin())
     scene.surface_frame(offsets, ids, Surface(normals, uvs, texture), rgba=out)  # smooth, textured (also surface(), interpolate())
+    scene.closest(rays, ids, t, bary, stream=s)                  # caller-supplied rays, no prepare() needed (also occluded())
 
 This is the path bench.py times (inputs resident in HBM) and the one-process-per-GPU
 band renderer uses; ``runner.render`` is the host-image ml* path.
@@ -365,6 +367,113 @@ def order_host(vertices, camera):
     normals = np.empty((n, 4), np.float32)
     _check(_native.lib().rtmOrderHost(v.ctypes.data, n, _camera10(camera), order.ctypes.data, normals.ctypes.data))
     return order, normals
+
+
+def _host_rays(rays):
+    import numpy as np
+
+    r = np.ascontiguousarray(rays, np.float32)
+    if r.ndim != 2 or r.shape[1] != 8:
+        raise ValueError(f"rays must be (count, 8), got {r.shape}")
+    return r
+
+
+def closest_host(path: str, rays, box_clause: bool = True):
+    """Ray queries on the host (rtrClosestHost: brute force in ascending id, the library's canonical
+    math, no tree, no device): rays (count, 8) float32 = (ox, oy, oz, tmin, dx, dy, dz, tmax) ->
+    (ids int32, t float32, bary (count, 2) float32), a miss as (-1, +inf, (0, 0)).
+    box_clause=False leaves the box clause out of the definition (to measure what it costs)."""
+    import numpy as np
+
+    r = _host_rays(rays)
+    ids = np.empty(r.shape[0], np.int32)
+    t = np.empty(r.shape[0], np.float32)
+    bary = np.empty((r.shape[0], 2), np.float32)
+    _check(_native.lib().rtrClosestHostFlags(os.fsencode(path), r.ctypes.data, r.shape[0], ids.ctypes.data,
+                                             t.ctypes.data, bary.ctypes.data,
+                                             _native.RTR_BOX_CLAUSE if box_clause else _native.RTR_NO_BOX_CLAUSE))
+    return ids, t, bary
+
+
+def occluded_host(path: str, rays, box_clause: bool = True):
+    """Occlusion on the host (rtrOccludedHost): rays (count, 8) float32 -> (count,) uint8, 1 iff any
+    triangle counts for the ray."""
+    import numpy as np
+
+    r = _host_rays(rays)
+    out = np.empty(r.shape[0], np.uint8)
+    _check(_native.lib().rtrOccludedHostFlags(os.fsencode(path), r.ctypes.data, r.shape[0], out.ctypes.data,
+                                              _native.RTR_BOX_CLAUSE if box_clause else _native.RTR_NO_BOX_CLAUSE))
+    return out
+
+
+def camera_rays(camera, width: int, height: int, offsets):
+    """The rays of a frame's pixels as ray queries: (H * W, 8) float32, row-major, o = eye,
+    d = (base + fx du) + fy dv at pixel_positions(width, height, offsets), tmin = 0, tmax = +inf.
+    camera: a scene file's path (its own camera, through srtSceneFrame) or 10 floats (eye, lookat,
+    up, vfov_deg: DeviceScene.camera). NOT bit-equal to the trace: near a triangle's edges the ray
+    test's arithmetic differs from the frame's edge records, so a pixel there may answer
+    differently, and t is the trace's only up to rounding."""
+    import numpy as np
+
+    if isinstance(camera, (str, bytes, os.PathLike)):
+        origin, base, du, dv = (np.array(v, np.float32) for v in scene_frame(os.fspath(camera), width, height))
+    else:
+        origin, base, du, dv = _frame_of_camera(camera, width, height)
+    pos = pixel_positions(width, height, offsets)
+    rays = np.empty((pos.shape[0], 8), np.float32)
+    rays[:, 0:3] = origin
+    rays[:, 3] = 0.0
+    rays[:, 4:7] = (base[None, :] + pos[:, 0:1] * du[None, :]) + pos[:, 1:2] * dv[None, :]
+    rays[:, 7] = np.inf
+    return rays
+
+
+def _frame_of_camera(camera, width: int, height: int):
+    """(origin, base, du, dv) of 10 camera floats: the frame's definition in
+    double, each component rounded once to float32."""
+    import numpy as np
+
+    c = np.array([float(v) for v in camera], np.float64)
+    if c.shape != (10,):
+        raise ValueError(f"camera must be 10 floats (eye, lookat, up, vfov_deg), got {c.shape}")
+    eye, lookat, up, vfov = c[0:3], c[3:6], c[6:9], c[9]
+    f = lookat - eye
+    f /= np.linalg.norm(f)
+    r = np.cross(f, up)
+    r /= np.linalg.norm(r)
+    u = np.cross(r, f)
+    half_h = np.tan(np.radians(vfov) / 2.0)
+    half_w = half_h * width / height
+    du = 2.0 * half_w * r
+    dv = -2.0 * half_h * u
+    base = f - half_w * r + half_h * u
+    return tuple(np.asarray(v, np.float32) for v in (eye, base, du, dv))
+
+
+def bounce_rays(rays, t, normal, tmin: float = 2.0 ** -10, tmax: float = float("inf")):
+    """Mirror rays from G-buffer planes: rays (count, 8) float32 that found hits at depth t
+    (count,) -- closest()'s or gbuffer()'s depth -- on surfaces with unit normals `normal`
+    (count, 3) or (count, 4) (gbuffer()'s plane) -> (count, 8) float32: o' = o + t d,
+    d' = d - 2 (d . n) n, range [tmin, tmax] (tmin > 0 keeps a bounce off its own surface). A ray
+    that missed (t not finite) becomes a ray with d' = 0, which misses."""
+    import numpy as np
+
+    r = _host_rays(rays)
+    tt = np.asarray(t, np.float32).reshape(-1)
+    n = np.asarray(normal, np.float32).reshape(r.shape[0], -1)[:, :3]
+    if tt.shape != (r.shape[0],):
+        raise ValueError(f"t must be {(r.shape[0],)}, got {tt.shape}")
+    hit = np.isfinite(tt)
+    ts = np.where(hit, tt, np.float32(0))[:, None]
+    d = r[:, 4:7]
+    out = np.zeros_like(r)
+    out[:, 0:3] = r[:, 0:3] + ts * d
+    dn = np.sum(d * n, axis=1, dtype=np.float32)[:, None]
+    out[:, 4:7] = np.where(hit[:, None], d - np.float32(2) * dn * n, np.float32(0))
+    out[:, 3] = tmin
+    out[:, 7] = tmax
+    return out
 
 
 class Surface:
@@ -1007,6 +1116,46 @@ class DeviceScene:
         self._check_vertices(vertices)
         _check(self._lib.rtmSetVerticesAsync(self.handle, _ptr(vertices), RTM_REORDER if reorder else RTM_KEEP_ORDER,
                                              _stream(stream)))
+
+    def _ray_count(self, buffers):
+        """count of a ray call's buffers, (name, buffer, tail, dtype) with the rays first: shapes
+        (count,) + tail, checked like query()'s."""
+        count = None
+        for name, buf, tail, dtype in buffers:
+            if buf is None:
+                continue
+            if hasattr(buf, "shape"):
+                shape = tuple(buf.shape)
+                if len(shape) != 1 + len(tail) or shape[1:] != tail or (count is not None and shape[0] != count):
+                    want = ("count" if count is None else count,) + tail
+                    raise ValueError(f"{name} must be {want}, got {shape}")
+                count = shape[0]
+            self._check_tensor(name, buf, dtype)
+        if count is None:
+            raise ValueError("rays must have a shape (count, 8): raw pointers carry no count")
+        return count
+
+    def build_rays(self, stream=None):
+        """Build the world-space tree of the ray queries now (rtrBuildAsync), on `stream`, if it is
+        missing or stale; closest() and occluded() do so themselves otherwise."""
+        _check(self._lib.rtrBuildAsync(self.handle, _stream(stream)))
+
+    def closest(self, rays, ids, t, bary=None, stream=None):
+        """Ray queries (include/srt_rays.h): the closest hit of caller-supplied rays. rays (count, 8)
+        float32 = (ox, oy, oz, tmin, dx, dy, dz, tmax), d not normalised, t in units of d -> ids
+        (count,) int32 (-1 = miss), t (count,) float32 (+inf = miss) and, optionally, bary (count, 2)
+        float32: the weights of v1 and v2. No prepare() is needed: the answer does not depend on the
+        camera. Device buffers, checked like query()'s."""
+        count = self._ray_count((("rays", rays, (8,), "f32"), ("ids", ids, (), "i32"), ("t", t, (), "f32"),
+                                 ("bary", bary, (2,), "f32")))
+        _check(self._lib.rtrClosestAsync(self.handle, _ptr(rays), count, _ptr(ids), _ptr(t), _ptr(bary),
+                                         _stream(stream)))
+
+    def occluded(self, rays, out, stream=None):
+        """Occlusion of caller-supplied rays (rtrOccludedAsync): rays (count, 8) float32 as
+        closest()'s -> out (count,) uint8: 1 iff any triangle counts for the ray within its range."""
+        count = self._ray_count((("rays", rays, (8,), "f32"), ("out", out, (), "u8")))
+        _check(self._lib.rtrOccludedAsync(self.handle, _ptr(rays), count, _ptr(out), _stream(stream)))
 
     def spatial_order(self):
         """(order, build_ms): the record ids in spatial order (numpy uint32), built on the device
