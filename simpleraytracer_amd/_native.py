@@ -105,6 +105,40 @@ class RtgOutputs(ctypes.Structure):
     ]
 
 
+RTA_HEMISPHERE = 0    # include/srt_visibility.h: rta_generator.kind
+RTA_AREA = 1
+RTA_MIRROR = 2
+RTA_MAX_SAMPLES = 64
+RTA_ROTATIONS = 16
+
+
+class RtaGenerator(ctypes.Structure):
+    """``rta_generator`` (include/srt_visibility.h): the tables as raw addresses, 0 = none."""
+
+    _fields_ = [
+        ("struct_size", ctypes.c_size_t),
+        ("kind", ctypes.c_int),
+        ("samples", ctypes.c_uint),
+        ("d_samples", ctypes.c_void_p),
+        ("d_rotations", ctypes.c_void_p),
+        ("corner", ctypes.c_float * 3),
+        ("eu", ctypes.c_float * 3),
+        ("ev", ctypes.c_float * 3),
+        ("tmin", ctypes.c_float),
+        ("tmax", ctypes.c_float),
+    ]
+
+
+class RtaOutputs(ctypes.Structure):
+    """``rta_outputs`` (include/srt_visibility.h): the planes as raw addresses, 0 = not written."""
+
+    _fields_ = [
+        ("struct_size", ctypes.c_size_t),
+        ("visible", ctypes.c_void_p),
+        ("fraction", ctypes.c_void_p),
+    ]
+
+
 RTV_MAX_CHANNELS = 4     # include/srt_surface.h: floats per corner of a table
 RTV_MAX_TEXTURE = 16384  # texels per side of a texture
 RTV_WRAP_CLAMP = 1       # rtv_surface.flags
@@ -362,6 +396,21 @@ _SIGNATURES = {
     "rtrClosestHostFlags": (ctypes.c_int, [ctypes.c_char_p, ctypes.c_void_p, _SZ, ctypes.c_void_p, ctypes.c_void_p,
                                            ctypes.c_void_p, ctypes.c_int]),
     "rtrOccludedHostFlags": (ctypes.c_int, [ctypes.c_char_p, ctypes.c_void_p, _SZ, ctypes.c_void_p, ctypes.c_int]),
+    # include/srt_visibility.h: sampled visibility (generator tables: device addresses for *Async, host ones for *Host)
+    "rtaVisibilityFrameAsync": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, _SZ, _SZ,
+                                               ctypes.POINTER(RtaGenerator), ctypes.POINTER(RtaOutputs),
+                                               ctypes.c_void_p]),
+    "rtaVisibilityPointsAsync": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, _SZ,
+                                                ctypes.POINTER(RtaGenerator), ctypes.POINTER(RtaOutputs),
+                                                ctypes.c_void_p]),
+    "rtaRaysFrameAsync": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, _SZ, _SZ,
+                                         ctypes.POINTER(RtaGenerator), ctypes.c_void_p, ctypes.c_void_p]),
+    "rtaRaysPointsAsync": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, _SZ,
+                                          ctypes.POINTER(RtaGenerator), ctypes.c_void_p, ctypes.c_void_p]),
+    "rtaVisibilityHost": (ctypes.c_int, [ctypes.c_char_p, _SZ, _SZ, ctypes.c_void_p, ctypes.c_void_p, _SZ,
+                                         ctypes.POINTER(RtaGenerator), ctypes.POINTER(RtaOutputs)]),
+    "rtaRaysHost": (ctypes.c_int, [ctypes.c_char_p, _SZ, _SZ, ctypes.c_void_p, ctypes.c_void_p, _SZ,
+                                   ctypes.POINTER(RtaGenerator), ctypes.c_void_p]),
 }
 
 _lib = None

@@ -14,6 +14,7 @@
 #include <string>
 
 #include "ray_math.h"
+#include "ray_walk.h"
 #include "rays.h"
 
 namespace srt {
@@ -266,11 +267,6 @@ __device__ __forceinline__ Ray LoadRay(const float4* __restrict__ rays, unsigned
     return r;
 }
 
-struct RayBest {
-    int id = -1;
-    float t = __builtin_inff(), w1 = 0.f, w2 = 0.f;
-};
-
 template <bool kClosest>
 __device__ __forceinline__ void StoreAnswer(const RayQueryParams& p, unsigned long long i, const RayBest& best) {
     if (kClosest) {
@@ -284,25 +280,14 @@ __device__ __forceinline__ void StoreAnswer(const RayQueryParams& p, unsigned lo
     }
 }
 
-// One ray per lane. The tree is implicit and complete, so the walk keeps (level, idx) and no stack:
-// a node that passes is entered at its first child, idx 8; after a node is done the walk moves to
-// idx + 1, climbing first while idx is the last child of its parent. Rays of a wave diverge freely.
-// The per-level counts and offsets are recomputed from n into LDS (a lane indexes them by its level).
+// One ray per lane, walked by RayWalk (ray_walk.h): (level, idx) and no stack. Rays of a wave diverge
+// freely. The per-level counts and offsets are recomputed from n into LDS.
 template <bool kClosest>
 __global__ __launch_bounds__(256) void RayTreeKernel(RayQueryParams p) {
     __shared__ unsigned s_count[kBvhMaxLevels], s_offset[kBvhMaxLevels];
     __shared__ unsigned s_levels;
     if (threadIdx.x == 0) {
-        unsigned below = p.n, offset = 0, levels = 0;
-        do {
-            const unsigned c = (below + kBvhWidth - 1) / kBvhWidth;
-            s_count[levels] = c;
-            s_offset[levels] = offset;
-            offset += c;
-            ++levels;
-            below = c;
-        } while (below > 1 && levels < kBvhMaxLevels);
-        s_levels = levels;
+        RayLevelsInit(p.n, s_count, s_offset, &s_levels);
     }
     __syncthreads();
     const unsigned long long i = blockIdx.x * 256ull + threadIdx.x;
@@ -310,74 +295,11 @@ __global__ __launch_bounds__(256) void RayTreeKernel(RayQueryParams p) {
         return;
     }
     const Ray r = LoadRay(p.rays, i);
-    RayBest best;
-    if (!RayDegenerate(r)) {
-        float inv[3];
-        RayInverse(r, inv);
-        const unsigned top = s_levels - 1;
-        unsigned level = top, idx = 0;
-        for (;;) {
-            const float4 nlo = p.nodes[2ull * (s_offset[level] + idx)];
-            const float4 nhi = p.nodes[2ull * (s_offset[level] + idx) + 1];
-            const float lo[3] = {nlo.x, nlo.y, nlo.z}, hi[3] = {nhi.x, nhi.y, nhi.z};
-            bool pass = RayBoxClause(r, inv, lo, hi);
-            if (pass && level == 0) {
-                const float4* __restrict__ rec = p.records + 4ull * (static_cast<unsigned long long>(idx) * kBvhWidth);
-                bool done = false;
-                for (int c = 0; c < kBvhWidth; ++c) {
-                    const float4 q2 = rec[4 * c + 2], q3 = rec[4 * c + 3];
-                    const float plo[3] = {q2.y, q2.z, q2.w}, phi[3] = {q3.x, q3.y, q3.z};
-                    if (!RayBoxClause(r, inv, plo, phi)) {
-                        continue;
-                    }
-                    const float4 q0 = rec[4 * c], q1 = rec[4 * c + 1];
-                    const float v[9] = {q0.x, q0.y, q0.z, q0.w, q1.x, q1.y, q1.z, q1.w, q2.x};
-                    const RayHit h = RayEdgeTest(r, v);
-                    const int id = __float_as_int(q3.w);
-                    if (h.hit && RayCloser(h.t, id, best.t, best.id)) {
-                        best.id = id;
-                        best.t = h.t;
-                        best.w1 = h.w1;
-                        best.w2 = h.w2;
-                        if (!kClosest) {
-                            done = true;
-                            break;
-                        }
-                    }
-                }
-                if (done) {
-                    break;
-                }
-                pass = false;
-            }
-            if (pass) {
-                --level;
-                idx *= kBvhWidth;
-                continue;
-            }
-            bool end = false;
-            for (;;) {
-                if (level == top) {
-                    end = true;
-                    break;
-                }
-                if ((idx & (kBvhWidth - 1)) != kBvhWidth - 1 && idx + 1 < s_count[level]) {
-                    ++idx;
-                    break;
-                }
-                idx /= kBvhWidth;
-                ++level;
-            }
-            if (end) {
-                break;
-            }
-        }
-    }
+    const RayBest best = RayWalk<kClosest>(r, p.nodes, p.records, s_count, s_offset, &s_levels);
     StoreAnswer<kClosest>(p, i, best);
 }
 
-// Brute force over the scene's own vertices in ascending id: no structure. Every lane reads the
-// same triangle, so the loads are wave-uniform.
+// Brute force over the scene's own vertices in ascending id (ray_walk.h RayScan): no structure.
 template <bool kClosest>
 __global__ __launch_bounds__(256) void RayBruteKernel(RayQueryParams p) {
     const unsigned long long i = blockIdx.x * 256ull + threadIdx.x;
@@ -385,32 +307,7 @@ __global__ __launch_bounds__(256) void RayBruteKernel(RayQueryParams p) {
         return;
     }
     const Ray r = LoadRay(p.rays, i);
-    RayBest best;
-    if (!RayDegenerate(r)) {
-        float inv[3];
-        RayInverse(r, inv);
-        for (unsigned k = 0; k < p.n; ++k) {
-            const float* __restrict__ src = p.vertices + 9ull * k;
-            float v[9], plo[3], phi[3];
-#pragma unroll
-            for (int j = 0; j < 9; ++j) {
-                v[j] = src[j];
-            }
-            if (!RayTriangleBox(v, plo, phi) || !RayBoxClause(r, inv, plo, phi)) {
-                continue;
-            }
-            const RayHit h = RayEdgeTest(r, v);
-            if (h.hit && RayCloser(h.t, static_cast<int>(k), best.t, best.id)) {
-                best.id = static_cast<int>(k);
-                best.t = h.t;
-                best.w1 = h.w1;
-                best.w2 = h.w2;
-                if (!kClosest) {
-                    break;
-                }
-            }
-        }
-    }
+    const RayBest best = RayScan<kClosest>(r, p.vertices, p.n);
     StoreAnswer<kClosest>(p, i, best);
 }
 

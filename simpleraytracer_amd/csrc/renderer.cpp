@@ -14,6 +14,7 @@
 #include "lighting_math.h"
 #include "rays.h"
 #include "render.h"
+#include "visibility.h"
 
 namespace srt {
 namespace {
@@ -380,6 +381,64 @@ void DeviceScene::Occluded(const float* d_rays, std::size_t count, unsigned char
     }
     RecordOrder(stream);
     LogRayStats();
+}
+
+// Sampled visibility (visibility.h): elements as GBuffer's, the tree as Closest's.
+namespace {
+
+VisibilityElements ElementsOf(bool points, const float* d_where, const int* d_ids, std::size_t row_begin,
+                              std::size_t count, std::size_t width, std::size_t height) {
+    return VisibilityElements{points, d_where, d_ids, points ? count : width, points ? 1 : count,
+                              points ? 0 : row_begin, width, height};
+}
+
+}  // namespace
+
+void DeviceScene::Visibility(bool points, const float* d_where, const int* d_ids, std::size_t row_begin,
+                             std::size_t count, const VisibilityGen& gen, unsigned char* d_visible, float* d_fraction,
+                             hipStream_t stream) const {
+    if (m_width == 0) {
+        throw std::runtime_error("Visibility: Prepare() has not been called");
+    }
+    if (!points && (row_begin > m_height || count > m_height - row_begin)) {
+        throw std::runtime_error("Visibility: row band outside the frame");
+    }
+    if (count == 0 || (d_visible == nullptr && d_fraction == nullptr)) {
+        return;
+    }
+    OrderAfterPrevious(stream);
+    try {
+        const RayTree* tree = EnsureRayTree(stream);
+        LaunchVisibility(tree, m_vertices, m_n, m_frame, ElementsOf(points, d_where, d_ids, row_begin, count, m_width, m_height),
+                         gen, d_visible, d_fraction, stream);
+    } catch (...) {
+        RecordOrder(stream);
+        throw;
+    }
+    RecordOrder(stream);
+    LogRayStats();
+}
+
+void DeviceScene::VisibilityRays(bool points, const float* d_where, const int* d_ids, std::size_t row_begin,
+                                 std::size_t count, const VisibilityGen& gen, float* d_rays, hipStream_t stream) const {
+    if (m_width == 0) {
+        throw std::runtime_error("Visibility rays: Prepare() has not been called");
+    }
+    if (!points && (row_begin > m_height || count > m_height - row_begin)) {
+        throw std::runtime_error("Visibility rays: row band outside the frame");
+    }
+    if (count == 0) {
+        return;
+    }
+    OrderAfterPrevious(stream);
+    try {
+        LaunchVisibilityRays(m_vertices, m_n, m_frame, ElementsOf(points, d_where, d_ids, row_begin, count, m_width, m_height),
+                             gen, d_rays, stream);
+    } catch (...) {
+        RecordOrder(stream);
+        throw;
+    }
+    RecordOrder(stream);
 }
 
 // The block extents of the prepared frame, once per Prepare (on the first binned trace's stream,

@@ -25,6 +25,7 @@ struct OrderScratch;  // render.h
 struct SurfaceArgs;   // render.h
 struct LitSurface;    // render.h
 struct RayTree;       // rays.h
+struct VisibilityGen;  // visibility.h
 
 // Throws std::runtime_error("HIP error: <what>: <reason>") on failure.
 void HipCheck(hipError_t err, const char* what);
@@ -244,6 +245,18 @@ public:
         unsigned long long allocations = 0;
     };
     RayStats ray_stats() const { return m_ray_stats; }
+
+    // Sampled visibility (include/srt_visibility.h; visibility.h): the generator's S rays from the
+    // surface point of every element of the prepared frame -- elements as GBuffer's (points,
+    // d_where, d_ids, row_begin, count) -- traced through the ray queries' tree in the same launch
+    // and counted (Visibility: d_visible, d_fraction, a null plane is not written), or exported
+    // sample-major (VisibilityRays: d_rays, S x elements x 8 floats). Visibility builds or rebuilds
+    // the tree as Closest does (EnsureRayTree; env SRT_RAYS=brute); VisibilityRays reads the vertices
+    // only. The caller has checked the generator. Calls on the scene for the ordering rule.
+    void Visibility(bool points, const float* d_where, const int* d_ids, std::size_t row_begin, std::size_t count,
+                    const VisibilityGen& gen, unsigned char* d_visible, float* d_fraction, hipStream_t stream) const;
+    void VisibilityRays(bool points, const float* d_where, const int* d_ids, std::size_t row_begin, std::size_t count,
+                        const VisibilityGen& gen, float* d_rays, hipStream_t stream) const;
 
     std::size_t width() const { return m_width; }
     // The spatial order (device, triangles entries) and the time its build took at load (ms).

@@ -32,8 +32,11 @@
 #include "srt_render.h"
 #include "srt_samples.h"
 #include "srt_surface.h"
+#include "srt_visibility.h"
 #include "surface_math.h"
 #include "tile_lookup.h"
+#include "visibility.h"
+#include "visibility_math.h"
 
 namespace {
 
@@ -2047,6 +2050,186 @@ RTR_API int rtrClosestHost(const char* scene_path, const float* rays, size_t cou
 
 RTR_API int rtrOccludedHost(const char* scene_path, const float* rays, size_t count, unsigned char* out) {
     return rtrOccludedHostFlags(scene_path, rays, count, out, RTR_BOX_CLAUSE);
+}
+
+// Sampled visibility (include/srt_visibility.h): the rta family.
+static_assert(RTA_HEMISPHERE == srt::kVisibilityHemisphere && RTA_AREA == srt::kVisibilityArea &&
+                  RTA_MIRROR == srt::kVisibilityMirror && RTA_MAX_SAMPLES == srt::kVisibilityMaxSamples &&
+                  RTA_ROTATIONS == srt::kVisibilityRotations,
+              "include/srt_visibility.h and visibility_math.h agree");
+
+namespace {
+
+// The generator of a call, every field checked. visibility: a call that counts (no mirror).
+srt::VisibilityGen CheckedGenerator(const rta_generator* g, bool visibility) {
+    if (g == nullptr) {
+        throw std::runtime_error("Bad argument: gen is NULL");
+    }
+    if (g->struct_size != sizeof(rta_generator)) {
+        throw std::runtime_error("rta_generator.struct_size is " + std::to_string(g->struct_size) + ", expected " +
+                                 std::to_string(sizeof(rta_generator)));
+    }
+    if (g->kind != RTA_HEMISPHERE && g->kind != RTA_AREA && g->kind != RTA_MIRROR) {
+        throw std::runtime_error("rta_generator.kind is " + std::to_string(g->kind) +
+                                 ", expected RTA_HEMISPHERE, RTA_AREA or RTA_MIRROR");
+    }
+    if (g->kind == RTA_MIRROR && visibility) {
+        throw std::runtime_error("rta_generator.kind is RTA_MIRROR: the mirror generator is export only");
+    }
+    if (g->samples < 1 || g->samples > RTA_MAX_SAMPLES) {
+        throw std::runtime_error("rta_generator.samples must be 1 to " + std::to_string(RTA_MAX_SAMPLES) + ", got " +
+                                 std::to_string(g->samples));
+    }
+    if (g->kind == RTA_MIRROR && g->samples != 1) {
+        throw std::runtime_error("rta_generator.samples must be 1 for RTA_MIRROR, got " + std::to_string(g->samples));
+    }
+    if (g->kind != RTA_MIRROR && g->d_samples == nullptr) {
+        throw std::runtime_error("rta_generator.d_samples is NULL");
+    }
+    srt::VisibilityGen out{};
+    out.kind = g->kind;
+    out.count = g->samples;
+    out.samples = g->d_samples;
+    out.rotations = g->kind == RTA_HEMISPHERE ? g->d_rotations : nullptr;
+    if (g->kind == RTA_AREA) {
+        const struct {
+            const char* name;
+            const float* v;
+        } fields[3] = {{"corner", g->corner}, {"eu", g->eu}, {"ev", g->ev}};
+        for (const auto& f : fields) {
+            for (int k = 0; k < 3; ++k) {
+                if (!std::isfinite(f.v[k])) {
+                    throw std::runtime_error(std::string("rta_generator.") + f.name + " is not finite");
+                }
+            }
+        }
+        std::memcpy(out.corner, g->corner, sizeof out.corner);
+        std::memcpy(out.eu, g->eu, sizeof out.eu);
+        std::memcpy(out.ev, g->ev, sizeof out.ev);
+    }
+    out.tmin = g->tmin;
+    out.tmax = g->tmax;
+    return out;
+}
+
+rta_outputs CheckedVisibilityOutputs(const rta_outputs* o) {
+    if (o == nullptr) {
+        throw std::runtime_error("Bad argument: outputs is NULL");
+    }
+    if (o->struct_size != sizeof(rta_outputs)) {
+        throw std::runtime_error("rta_outputs.struct_size is " + std::to_string(o->struct_size) + ", expected " +
+                                 std::to_string(sizeof(rta_outputs)));
+    }
+    return *o;
+}
+
+void CheckElements(const float* where, const char* where_name, const int* ids, const char* ids_name) {
+    if (where == nullptr) {
+        throw std::runtime_error(std::string("Bad buffer argument: ") + where_name + " is NULL");
+    }
+    if (ids == nullptr) {
+        throw std::runtime_error(std::string("Bad buffer argument: ") + ids_name + " is NULL");
+    }
+}
+
+int VisibilityAsync(srt_device_scene scene, bool points, const float* d_where, const char* where_name,
+                    const int* d_ids, size_t row_begin, size_t count, const rta_generator* gen,
+                    const rta_outputs* outputs, void* stream) {
+    return Guarded([&] {
+        if (scene == nullptr) {
+            throw std::runtime_error("Bad scene handle");
+        }
+        const srt::VisibilityGen g = CheckedGenerator(gen, true);
+        const rta_outputs o = CheckedVisibilityOutputs(outputs);
+        if (count != 0 && (o.visible != nullptr || o.fraction != nullptr)) {
+            CheckElements(d_where, where_name, d_ids, "d_ids");
+        }
+        srt::DeviceScene* s = FromHandle(scene);
+        Bind bind(s->device());
+        s->Visibility(points, d_where, d_ids, row_begin, count, g, o.visible, o.fraction,
+                      static_cast<hipStream_t>(stream));
+    });
+}
+
+int VisibilityRaysAsync(srt_device_scene scene, bool points, const float* d_where, const char* where_name,
+                        const int* d_ids, size_t row_begin, size_t count, const rta_generator* gen, float* d_rays,
+                        void* stream) {
+    return Guarded([&] {
+        if (scene == nullptr) {
+            throw std::runtime_error("Bad scene handle");
+        }
+        const srt::VisibilityGen g = CheckedGenerator(gen, false);
+        if (count != 0) {
+            CheckElements(d_where, where_name, d_ids, "d_ids");
+            CheckRays(d_rays, "d_rays", true);
+        }
+        srt::DeviceScene* s = FromHandle(scene);
+        Bind bind(s->device());
+        s->VisibilityRays(points, d_where, d_ids, row_begin, count, g, d_rays, static_cast<hipStream_t>(stream));
+    });
+}
+
+}  // namespace
+
+RTA_API int rtaVisibilityFrameAsync(srt_device_scene scene, const float* d_offsets, const int* d_ids, size_t row_begin,
+                                    size_t row_count, const rta_generator* gen, const rta_outputs* outputs,
+                                    void* stream) {
+    return VisibilityAsync(scene, false, d_offsets, "d_offsets", d_ids, row_begin, row_count, gen, outputs, stream);
+}
+
+RTA_API int rtaVisibilityPointsAsync(srt_device_scene scene, const float* d_positions, const int* d_ids, size_t count,
+                                     const rta_generator* gen, const rta_outputs* outputs, void* stream) {
+    return VisibilityAsync(scene, true, d_positions, "d_positions", d_ids, 0, count, gen, outputs, stream);
+}
+
+RTA_API int rtaRaysFrameAsync(srt_device_scene scene, const float* d_offsets, const int* d_ids, size_t row_begin,
+                              size_t row_count, const rta_generator* gen, float* d_rays, void* stream) {
+    return VisibilityRaysAsync(scene, false, d_offsets, "d_offsets", d_ids, row_begin, row_count, gen, d_rays, stream);
+}
+
+RTA_API int rtaRaysPointsAsync(srt_device_scene scene, const float* d_positions, const int* d_ids, size_t count,
+                               const rta_generator* gen, float* d_rays, void* stream) {
+    return VisibilityRaysAsync(scene, true, d_positions, "d_positions", d_ids, 0, count, gen, d_rays, stream);
+}
+
+RTA_API int rtaVisibilityHost(const char* scene_path, size_t width, size_t height, const float* positions,
+                              const int* ids, size_t count, const rta_generator* gen, const rta_outputs* outputs) {
+    return Guarded([&] {
+        const srt::VisibilityGen g = CheckedGenerator(gen, true);
+        const rta_outputs o = CheckedVisibilityOutputs(outputs);
+        if (scene_path == nullptr) {
+            throw std::runtime_error("Bad argument: scene_path is NULL");
+        }
+        if (width == 0 || height == 0) {
+            throw std::runtime_error("Bad argument: frame dimensions must be non-zero");
+        }
+        if (count == 0 || (o.visible == nullptr && o.fraction == nullptr)) {
+            return;
+        }
+        CheckElements(positions, "positions", ids, "ids");
+        const srt::Scene scene = srt::LoadScene(scene_path);
+        srt::HostVisibility(scene, width, height, positions, ids, count, g, o.visible, o.fraction);
+    });
+}
+
+RTA_API int rtaRaysHost(const char* scene_path, size_t width, size_t height, const float* positions, const int* ids,
+                        size_t count, const rta_generator* gen, float* rays) {
+    return Guarded([&] {
+        const srt::VisibilityGen g = CheckedGenerator(gen, false);
+        if (scene_path == nullptr) {
+            throw std::runtime_error("Bad argument: scene_path is NULL");
+        }
+        if (width == 0 || height == 0) {
+            throw std::runtime_error("Bad argument: frame dimensions must be non-zero");
+        }
+        if (count == 0) {
+            return;
+        }
+        CheckElements(positions, "positions", ids, "ids");
+        CheckRays(rays, "rays", false);
+        const srt::Scene scene = srt::LoadScene(scene_path);
+        srt::HostVisibilityRays(scene, width, height, positions, ids, count, g, rays);
+    });
 }
 
 #ifdef SRT_DIAG

@@ -2,8 +2,8 @@
 (include/srt_query.h), G-buffer outputs (include/srt_gbuffer.h), multi-sample frames
 (include/srt_samples.h), spot-light shadow masks (include/srt_light.h), omni-light shadow masks
 (include/srt_omni.h), direct lighting (include/srt_lighting.h; the lights: lighting.py), dynamic
-scenes (include/srt_motion.h), vertex attributes (include/srt_surface.h) and ray queries
-(include/srt_rays.h).
+scenes (include/srt_motion.h), vertex attributes (include/srt_surface.h), ray queries
+(include/srt_rays.h) and sampled visibility (include/srt_visibility.h).
 
 ``DeviceScene`` keeps a scene resident on one GPU and launches the two stages on a caller's
 HIP stream with caller-owned device buffers (torch tensors or raw pointers):
@@ -21,6 +21,7 @@ HIP stream with caller-owned device buffers (torch tensors or raw pointers):
     scene.set_camera(camera, stream=s)                           # move the camera in place (also set_vertices(), OmniLight.set_origin())
     scene.surface_frame(offsets, ids, Surface(normals, uvs, texture), rgba=out)  # smooth, textured (also surface(), interpolate())
     scene.closest(rays, ids, t, bary, stream=s)                  # caller-supplied rays, no prepare() needed (also occluded())
+    scene.visibility_frame(offsets, ids, Hemisphere(samples, tmin, tmax), fraction=ao)  # ambient occlusion, soft shadows (also visibility(), generate_rays())
 
 This is the path bench.py times (inputs resident in HBM) and the one-process-per-GPU
 band renderer uses; ``runner.render`` is the host-image ml* path.
@@ -474,6 +475,112 @@ def bounce_rays(rays, t, normal, tmin: float = 2.0 ** -10, tmax: float = float("
     out[:, 3] = tmin
     out[:, 7] = tmax
     return out
+
+
+class _Generator:
+    """A ray generator of the sampled-visibility calls (``rta_generator``, include/srt_visibility.h).
+    Device tensors for the DeviceScene calls, numpy arrays for visibility_host() / rays_host(); the
+    holder keeps them alive and copies nothing."""
+
+    kind = -1
+    per_sample = 0  # floats per row of `samples`
+
+    def __init__(self, samples, tmin, tmax, rotations=None, corner=(0.0, 0.0, 0.0), eu=(0.0, 0.0, 0.0),
+                 ev=(0.0, 0.0, 0.0)):
+        if samples is not None:
+            shape = tuple(samples.shape)
+            if len(shape) != 2 or shape[1] != self.per_sample:
+                raise ValueError(f"samples must be (S, {self.per_sample}), got {shape}")
+        if rotations is not None and tuple(rotations.shape) != (_native.RTA_ROTATIONS, 2):
+            raise ValueError(f"rotations must be {(_native.RTA_ROTATIONS, 2)}, got {tuple(rotations.shape)}")
+        self.samples, self.rotations = samples, rotations
+        self.corner, self.eu, self.ev = _float3("corner", corner), _float3("eu", eu), _float3("ev", ev)
+        self.tmin, self.tmax = float(tmin), float(tmax)
+
+    @property
+    def count(self) -> int:
+        """S, the rays per element."""
+        return 1 if self.samples is None else int(self.samples.shape[0])
+
+    def _tables(self):
+        return (("samples", self.samples), ("rotations", self.rotations))
+
+    def _struct(self, address):
+        return _native.RtaGenerator(ctypes.sizeof(_native.RtaGenerator), self.kind, self.count, address(self.samples),
+                                    address(self.rotations), self.corner, self.eu, self.ev, self.tmin, self.tmax)
+
+
+class Hemisphere(_Generator):
+    """Ambient occlusion: samples (S, 3) float32 local directions (lx, ly, lz) around the normal
+    (samples.cosine_hemisphere), each ray's range [tmin, tmax] in units of the direction; rotations:
+    None or (16, 2) float32 (cos, sin) pairs (samples.rotations), one per pixel of a 4 x 4 block."""
+
+    kind = _native.RTA_HEMISPHERE
+    per_sample = 3
+
+    def __init__(self, samples, tmin, tmax, rotations=None):
+        super().__init__(samples, tmin, tmax, rotations)
+
+
+class AreaLight(_Generator):
+    """A parallelogram light corner + a eu + b ev: samples (S, 2) float32 (a, b) (samples.area_samples).
+    A ray runs from the surface point to the light's point, t in units of that segment."""
+
+    kind = _native.RTA_AREA
+    per_sample = 2
+
+    def __init__(self, corner, eu, ev, samples, tmin: float = 2.0 ** -10, tmax: float = 1.0 - 2.0 ** -10):
+        super().__init__(samples, tmin, tmax, None, corner, eu, ev)
+
+
+class Mirror(_Generator):
+    """The mirror bounce of the primary ray, one ray per element; generate_rays() only."""
+
+    kind = _native.RTA_MIRROR
+
+    def __init__(self, tmin: float = 2.0 ** -10, tmax: float = float("inf")):
+        super().__init__(None, tmin, tmax)
+
+
+def _host_generator(generator):
+    """The generator's struct over contiguous float32 numpy copies of its tables (kept alive by the
+    returned tuple)."""
+    import numpy as np
+
+    keep = {id(t): np.ascontiguousarray(t, np.float32) for _, t in generator._tables() if t is not None}
+    return generator._struct(lambda a: 0 if a is None else keep[id(a)].ctypes.data), keep
+
+
+def rays_host(path: str, width: int, height: int, positions, ids, generator):
+    """The rays of a generator on the host (rtaRaysHost: the library's canonical math, no device):
+    positions (count, 2) float32 and ids (count,) int32 on the file's width x height frame ->
+    (S, count, 8) float32 rays, sample-major. An element off a surface gives zero rays."""
+    import numpy as np
+
+    pos, idv = _host_elements(positions, ids)
+    g, keep = _host_generator(generator)
+    rays = np.empty((generator.count, pos.shape[0], 8), np.float32)
+    _check(_native.lib().rtaRaysHost(os.fsencode(path), width, height, pos.ctypes.data, idv.ctypes.data, pos.shape[0],
+                                     ctypes.byref(g), rays.ctypes.data))
+    del keep
+    return rays
+
+
+def visibility_host(path: str, width: int, height: int, positions, ids, generator):
+    """Sampled visibility on the host (rtaVisibilityHost): positions (count, 2) float32 and ids
+    (count,) int32 -> (visible (count,) uint8, fraction (count,) float32): how many of the
+    generator's S rays are unoccluded, and that over S."""
+    import numpy as np
+
+    pos, idv = _host_elements(positions, ids)
+    g, keep = _host_generator(generator)
+    visible = np.empty(pos.shape[0], np.uint8)
+    fraction = np.empty(pos.shape[0], np.float32)
+    out = _native.RtaOutputs(ctypes.sizeof(_native.RtaOutputs), visible.ctypes.data, fraction.ctypes.data)
+    _check(_native.lib().rtaVisibilityHost(os.fsencode(path), width, height, pos.ctypes.data, idv.ctypes.data,
+                                           pos.shape[0], ctypes.byref(g), ctypes.byref(out)))
+    del keep
+    return visible, fraction
 
 
 class Surface:
@@ -1156,6 +1263,80 @@ class DeviceScene:
         closest()'s -> out (count,) uint8: 1 iff any triangle counts for the ray within its range."""
         count = self._ray_count((("rays", rays, (8,), "f32"), ("out", out, (), "u8")))
         _check(self._lib.rtrOccludedAsync(self.handle, _ptr(rays), count, _ptr(out), _stream(stream)))
+
+    def _generator(self, generator):
+        """rta_generator of a holder of device tables, each checked to be float32 on this device."""
+        for name, table in generator._tables():
+            if table is not None:
+                self._check_tensor(name, table, "f32")
+        return generator._struct(_ptr)
+
+    def _visibility_outputs(self, visible, fraction, lead):
+        out = _native.RtaOutputs(ctypes.sizeof(_native.RtaOutputs), 0, 0)
+        for name, buf, dtype in (("visible", visible, "u8"), ("fraction", fraction, "f32")):
+            if buf is None:
+                continue
+            if hasattr(buf, "shape") and tuple(buf.shape) != lead:
+                raise ValueError(f"{name} must be {lead}, got {tuple(buf.shape)}")
+            self._check_tensor(name, buf, dtype)
+            setattr(out, name, _ptr(buf))
+        return out
+
+    def _check_rays_out(self, rays, lead):
+        if hasattr(rays, "shape") and tuple(rays.shape) != lead + (8,):
+            raise ValueError(f"rays must be {lead + (8,)}, got {tuple(rays.shape)}")
+        self._check_tensor("rays", rays, "f32")
+
+    def visibility(self, positions, ids, generator, visible=None, fraction=None, stream=None):
+        """Sampled visibility (include/srt_visibility.h) at arbitrary image positions of the prepared
+        frame: positions (count, 2) float32 and ids (count,) int32 -- query()'s input and output --
+        and a Hemisphere or an AreaLight of device tables -> visible (count,) uint8, how many of the
+        generator's S rays from the surface point are unoccluded, and fraction (count,) float32 =
+        visible / S; a plane left None is not written. One launch: the rays are generated and walked
+        through the ray queries' tree in the kernel."""
+        count = self._elements(positions, ids)
+        g = self._generator(generator)
+        out = self._visibility_outputs(visible, fraction, (count,))
+        _check(self._lib.rtaVisibilityPointsAsync(self.handle, _ptr(positions), _ptr(ids), count, ctypes.byref(g),
+                                                  ctypes.byref(out), _stream(stream)))
+
+    def visibility_frame(self, offsets, ids, generator, visible=None, fraction=None, row_begin: int = 0,
+                         row_count: int | None = None, stream=None):
+        """Sampled visibility of the prepared frame's rows from hit ids: offsets (rows, W, 2) float32
+        and ids (rows, W) int32, band-local -> visible (rows, W) uint8 and fraction (rows, W) float32
+        as visibility()'s. A Hemisphere's rotations are indexed by the pixel's place in its 4 x 4
+        block of the whole frame."""
+        if row_count is None:
+            row_count = self.height - row_begin
+        self._check_buffer("offsets", offsets, row_count, 2, "f32")
+        self._check_buffer("ids", ids, row_count, 0, "i32")
+        g = self._generator(generator)
+        out = self._visibility_outputs(visible, fraction, (row_count, self.width))
+        _check(self._lib.rtaVisibilityFrameAsync(self.handle, _ptr(offsets), _ptr(ids), row_begin, row_count,
+                                                 ctypes.byref(g), ctypes.byref(out), _stream(stream)))
+
+    def generate_rays(self, positions, ids, generator, rays, stream=None):
+        """The generator's rays themselves, for closest() / occluded(): positions and ids as
+        visibility()'s -> rays (S, count, 8) float32, sample-major (plane s holds sample s of every
+        element). A Mirror generator (S = 1) gives the primary rays' mirror bounces."""
+        count = self._elements(positions, ids)
+        g = self._generator(generator)
+        self._check_rays_out(rays, (generator.count, count))
+        _check(self._lib.rtaRaysPointsAsync(self.handle, _ptr(positions), _ptr(ids), count, ctypes.byref(g),
+                                            _ptr(rays), _stream(stream)))
+
+    def generate_rays_frame(self, offsets, ids, generator, rays, row_begin: int = 0, row_count: int | None = None,
+                            stream=None):
+        """generate_rays() for the prepared frame's rows: offsets and ids as visibility_frame()'s ->
+        rays (S, rows, W, 8) float32."""
+        if row_count is None:
+            row_count = self.height - row_begin
+        self._check_buffer("offsets", offsets, row_count, 2, "f32")
+        self._check_buffer("ids", ids, row_count, 0, "i32")
+        g = self._generator(generator)
+        self._check_rays_out(rays, (generator.count, row_count, self.width))
+        _check(self._lib.rtaRaysFrameAsync(self.handle, _ptr(offsets), _ptr(ids), row_begin, row_count, ctypes.byref(g),
+                                           _ptr(rays), _stream(stream)))
 
     def spatial_order(self):
         """(order, build_ms): the record ids in spatial order (numpy uint32), built on the device
