@@ -207,6 +207,16 @@ class RtdLightHost(ctypes.Structure):
     ]
 
 
+class RthBlend(ctypes.Structure):
+    """``rth_blend`` (include/srt_hits.h): the base picture as a raw address and the weight."""
+
+    _fields_ = [
+        ("struct_size", ctypes.c_size_t),
+        ("d_base", ctypes.c_void_p),
+        ("weight", ctypes.c_float * 3),
+    ]
+
+
 RTP_MAX_SHININESS_LOG2 = 12  # include/srt_material.h: the Blinn-Phong exponent is 2^shininess_log2
 
 
@@ -411,6 +421,13 @@ _SIGNATURES = {
                                          ctypes.POINTER(RtaGenerator), ctypes.POINTER(RtaOutputs)]),
     "rtaRaysHost": (ctypes.c_int, [ctypes.c_char_p, _SZ, _SZ, ctypes.c_void_p, ctypes.c_void_p, _SZ,
                                    ctypes.POINTER(RtaGenerator), ctypes.c_void_p]),
+    # include/srt_hits.h: lit ray hits (lights, ambient: rtdLight*'s; blend: an RthBlend or None)
+    "rthLightHitsAsync": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, _SZ, ctypes.POINTER(ctypes.c_float),
+                                         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, _SZ, ctypes.POINTER(RthBlend),
+                                         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "rthLightHitsHost": (ctypes.c_int, [ctypes.c_char_p, ctypes.c_void_p, _SZ, ctypes.POINTER(ctypes.c_float),
+                                        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, _SZ, ctypes.POINTER(RthBlend),
+                                        ctypes.c_void_p, ctypes.c_void_p]),
 }
 
 _lib = None

@@ -1,12 +1,14 @@
 #include "cpu_render.h"
 
 #include "gbuffer_math.h"
+#include "hits_math.h"
 #include "layers_math.h"
 #include "lighting_math.h"
 #include "material_math.h"
 #include "omni_math.h"
 #include "samples_math.h"
 #include "screen_box.h"
+#include "shading_normal.h"
 #include "shadow_math.h"
 #include "surface_math.h"
 
@@ -693,6 +695,94 @@ void HostOmniShadow(const Scene& scene, std::size_t width, std::size_t height, c
     });
 }
 
+namespace {
+
+// Every light's frames (1 or 6), their projection rows and every triangle's record under each.
+struct HostLightFrame {
+    Frame frame;
+    float rows[9];
+    std::vector<Rec> recs;
+};
+struct HostLightFrames {
+    std::vector<HostLightFrame> frames;
+    std::vector<std::size_t> first;  // per light
+};
+HostLightFrames MakeLightFrames(const Scene& scene, const HostLight* lights, std::size_t count) {
+    const std::size_t n = scene.triangle_count();
+    HostLightFrames all;
+    all.first.resize(count);
+    for (std::size_t l = 0; l < count; ++l) {
+        const HostLight& in = lights[l];
+        all.first[l] = all.frames.size();
+        const int faces = in.point ? kOmniFaces : 1;
+        for (int k = 0; k < faces; ++k) {
+            HostLightFrame lf;
+            lf.frame = in.point ? MakeFrame(OmniFaceCameraOf(in.origin, k), in.face_size, in.face_size)
+                                : MakeFrame(in.camera, in.width, in.height);
+            ShadowProjectionRows(lf.frame.base, lf.frame.du, lf.frame.dv, lf.rows);
+            lf.recs.resize(n);
+            Rec* out = lf.recs.data();
+            const Frame& fr = lf.frame;
+            ParallelFor(n, 1024, [&](std::size_t i) { out[i] = MakeRecord(scene.vertices.data() + 9 * i, fr); });
+            all.frames.push_back(std::move(lf));
+        }
+    }
+    return all;
+}
+
+// Light l at the surface point p of triangle id, whose geometric normal is nrm with nn = nrm.nrm and
+// nd = nrm.d (lighting_math.h; the one statement of the rule for HostLitSurface and HostLightHits):
+// q = p - origin, the light's class of p -- ShadowProjectOffset in its frame (the face OmniFace(q)
+// of a point light), the frame's closest hit by brute force in ascending id, ShadowClass -- and,
+// where the light contributes (class 1 and facing), its flat weight LightingWeight.
+struct HostLightAt {
+    unsigned char cls;
+    bool contributes;
+    float q[3], qq, w;  // qq, w: of a contributing light
+};
+HostLightAt LightAtPoint(const HostLightFrames& all, const HostLight& in, std::size_t l, std::size_t n, int id,
+                         const float p[3], const float nrm[3], float nn, float nd) {
+    const float inf = std::numeric_limits<float>::infinity();
+    HostLightAt at{};
+    const float* origin = all.frames[all.first[l]].frame.origin;
+    for (int k = 0; k < 3; ++k) {
+        at.q[k] = p[k] - origin[k];
+    }
+    const HostLightFrame& lf = all.frames[all.first[l] + (in.point ? static_cast<std::size_t>(OmniFace(at.q)) : 0)];
+    const ShadowPoint sp = ShadowProjectOffset(at.q, lf.rows, in.bias);
+    at.cls = kShadowOutside;
+    if (sp.inside) {
+        float best = inf;
+        int lid = -1;
+        for (std::size_t k = 0; k < n; ++k) {  // ascending ids: strict < keeps the lowest on ties
+            const float* c = lf.recs[k].c;
+            const float eA = std::fma(sp.gy, c[2], std::fma(sp.gx, c[1], c[0]));
+            const float eB = std::fma(sp.gy, c[5], std::fma(sp.gx, c[4], c[3]));
+            const float eC = std::fma(sp.gy, c[8], std::fma(sp.gx, c[7], c[6]));
+            if (eA >= 0.f && eB >= 0.f && eC >= 0.f) {
+                const float det = (eA + eB) + eC;
+                if (det > 0.f) {
+                    const float tt = lf.recs[k].vol / det;
+                    if (tt < best) {
+                        best = tt;
+                        lid = static_cast<int>(k);
+                    }
+                }
+            }
+        }
+        at.cls = ShadowClass(id, lid, best, sp.thr);
+    }
+    const float nl = ShadowDot(nrm, at.q);
+    at.contributes = at.cls == kShadowLit && LightingFacing(nl, nd);
+    if (at.contributes) {
+        at.qq = ShadowDot(at.q, at.q);
+        at.w = LightingWeight(nl, nn, at.qq, in.falloff);
+    }
+    return at;
+}
+
+}  // namespace
+
 void HostLitSurface(const Scene& scene, std::size_t width, std::size_t height, const HostLight* lights, std::size_t count,
                     const float ambient[3], const HostSurfaceTables* surface, const HostMaterial* material,
                     const float* offsets, const int* ids, std::size_t row_begin, std::size_t row_count, float* rgba,
@@ -713,32 +803,8 @@ void HostLitSurface(const Scene& scene, std::size_t width, std::size_t height, c
     }
     const Frame f = MakeFrame(scene.camera, width, height);
     const std::size_t n = scene.triangle_count();
-    // Every light's frames (1 or 6), their projection rows and every triangle's record under each.
-    struct LightFrame {
-        Frame frame;
-        float rows[9];
-        std::vector<Rec> recs;
-    };
-    std::vector<LightFrame> frames;
-    std::vector<std::size_t> first(count);
-    for (std::size_t l = 0; l < count; ++l) {
-        const HostLight& in = lights[l];
-        first[l] = frames.size();
-        const int faces = in.point ? kOmniFaces : 1;
-        for (int k = 0; k < faces; ++k) {
-            LightFrame lf;
-            lf.frame = in.point ? MakeFrame(OmniFaceCameraOf(in.origin, k), in.face_size, in.face_size)
-                                : MakeFrame(in.camera, in.width, in.height);
-            ShadowProjectionRows(lf.frame.base, lf.frame.du, lf.frame.dv, lf.rows);
-            lf.recs.resize(n);
-            Rec* out = lf.recs.data();
-            const Frame& fr = lf.frame;
-            ParallelFor(n, 1024, [&](std::size_t i) { out[i] = MakeRecord(scene.vertices.data() + 9 * i, fr); });
-            frames.push_back(std::move(lf));
-        }
-    }
+    const HostLightFrames frames = MakeLightFrames(scene, lights, count);
     const float wf = static_cast<float>(width), hf = static_cast<float>(height);
-    const float inf = std::numeric_limits<float>::infinity();
     const std::size_t plane = row_count * width;
     ParallelFor(plane, 64, [&](std::size_t i) {
         const std::size_t x = i % width, y = row_begin + i / width;
@@ -764,47 +830,17 @@ void HostLitSurface(const Scene& scene, std::size_t width, std::size_t height, c
         float e[3] = {ambient[0], ambient[1], ambient[2]}, sp[3] = {0.f, 0.f, 0.f};
         for (std::size_t l = 0; l < count; ++l) {
             const HostLight& in = lights[l];
-            const float* origin = frames[first[l]].frame.origin;
-            float q[3];
-            for (int k = 0; k < 3; ++k) {
-                q[k] = p[k] - origin[k];
-            }
-            const LightFrame& lf = frames[first[l] + (in.point ? static_cast<std::size_t>(OmniFace(q)) : 0)];
-            const ShadowPoint at = ShadowProjectOffset(q, lf.rows, in.bias);
-            unsigned char cls = kShadowOutside;
-            if (at.inside) {
-                float best = inf;
-                int lid = -1;
-                for (std::size_t k = 0; k < n; ++k) {  // ascending ids: strict < keeps the lowest on ties
-                    const float* c = lf.recs[k].c;
-                    const float eA = std::fma(at.gy, c[2], std::fma(at.gx, c[1], c[0]));
-                    const float eB = std::fma(at.gy, c[5], std::fma(at.gx, c[4], c[3]));
-                    const float eC = std::fma(at.gy, c[8], std::fma(at.gx, c[7], c[6]));
-                    if (eA >= 0.f && eB >= 0.f && eC >= 0.f) {
-                        const float det = (eA + eB) + eC;
-                        if (det > 0.f) {
-                            const float tt = lf.recs[k].vol / det;
-                            if (tt < best) {
-                                best = tt;
-                                lid = static_cast<int>(k);
-                            }
-                        }
-                    }
-                }
-                cls = ShadowClass(id, lid, best, at.thr);
-            }
+            const HostLightAt at = LightAtPoint(frames, in, l, n, id, p, r.n, nn, nd);
             if (classes != nullptr) {
-                classes[l * plane + i] = cls;
+                classes[l * plane + i] = at.cls;
             }
-            const float nl = ShadowDot(r.n, q);
-            if (cls == kShadowLit && LightingFacing(nl, nd)) {
-                const float qq = ShadowDot(q, q);
-                const float w = smooth ? MaterialDiffuse(on, q, qq, in.falloff) : LightingWeight(nl, nn, qq, in.falloff);
+            if (at.contributes) {
+                const float w = smooth ? MaterialDiffuse(on, at.q, at.qq, in.falloff) : at.w;
                 for (int k = 0; k < 3; ++k) {
                     e[k] = e[k] + in.color[k] * w;
                 }
                 if (material != nullptr && w > 0.f) {
-                    const float ws = MaterialSpecular(on, q, qq, d, material->shininess_log2, in.falloff);
+                    const float ws = MaterialSpecular(on, at.q, at.qq, d, material->shininess_log2, in.falloff);
                     for (int k = 0; k < 3; ++k) {
                         sp[k] = sp[k] + in.color[k] * ws;
                     }
@@ -815,6 +851,55 @@ void HostLitSurface(const Scene& scene, std::size_t width, std::size_t height, c
             out[k] = material != nullptr ? oa[k] * e[k] + material->specular[k] * sp[k] : oa[k] * e[k];
         }
         out[3] = static_cast<float>(id);
+        std::copy(out, out + 4, rgba + 4 * i);
+    });
+}
+
+void HostLightHits(const Scene& scene, const HostLight* lights, std::size_t count, const float ambient[3],
+                   const float* rays, const int* ids, const float* t, std::size_t elements, const float* base,
+                   const float weight[3], float* rgba, unsigned char* classes) {
+    const std::size_t n = scene.triangle_count();
+    const HostLightFrames frames = MakeLightFrames(scene, lights, count);
+    ParallelFor(elements, 64, [&](std::size_t i) {
+        const float* o = rays + 8 * i;
+        const float* d = o + 4;
+        const int id = ids[i];
+        const bool absent = HitAbsent(d);
+        const bool surface = HitSurface(o, d, id, t[i], static_cast<unsigned>(n));
+        float out[4] = {absent ? 0.f : scene.background[0], absent ? 0.f : scene.background[1],
+                        absent ? 0.f : scene.background[2], -1.f};
+        if (surface) {
+            float p[3];
+            HitPoint(o, d, t[i], p);
+            const float4 nr = ShadingNormal(scene.vertices.data() + 9 * static_cast<std::size_t>(id));
+            const float nrm[3] = {nr.x, nr.y, nr.z};
+            const float* al = scene.albedo.data() + 3 * static_cast<std::size_t>(id);
+            const float nn = ShadowDot(nrm, nrm), nd = ShadowDot(nrm, d);
+            float e[3] = {ambient[0], ambient[1], ambient[2]};
+            for (std::size_t l = 0; l < count; ++l) {
+                const HostLightAt at = LightAtPoint(frames, lights[l], l, n, id, p, nrm, nn, nd);
+                if (classes != nullptr) {
+                    classes[l * elements + i] = at.cls;
+                }
+                if (at.contributes) {
+                    for (int k = 0; k < 3; ++k) {
+                        e[k] = e[k] + lights[l].color[k] * at.w;
+                    }
+                }
+            }
+            for (int k = 0; k < 3; ++k) {
+                out[k] = al[k] * e[k];
+            }
+            out[3] = static_cast<float>(id);
+        } else {
+            for (std::size_t l = 0; l < count && classes != nullptr; ++l) {
+                classes[l * elements + i] = kShadowNoSurface;
+            }
+        }
+        if (base != nullptr) {
+            const float b[4] = {base[4 * i], base[4 * i + 1], base[4 * i + 2], base[4 * i + 3]};
+            HitBlend(absent, b, weight, out);
+        }
         std::copy(out, out + 4, rgba + 4 * i);
     });
 }

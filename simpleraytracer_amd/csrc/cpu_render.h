@@ -130,6 +130,14 @@ void HostLitSurface(const Scene& scene, std::size_t width, std::size_t height, c
                     const float* offsets, const int* ids, std::size_t row_begin, std::size_t row_count, float* rgba,
                     unsigned char* classes);
 
+// Lit ray hits (hits_math.h; the host answer of render.h LaunchLightHits): HostLighting for `elements`
+// hits given as (ray, id, t) -- rays elements x 8, ids and t elements each -- with the surface point
+// from the element's own ray; no view frame. base (elements x 4; null: store; may be rgba) with
+// weight[3]: the element is added onto it. classes (count x elements, light-major) may be null.
+void HostLightHits(const Scene& scene, const HostLight* lights, std::size_t count, const float ambient[3],
+                   const float* rays, const int* ids, const float* t, std::size_t elements, const float* base,
+                   const float weight[3], float* rgba, unsigned char* classes);
+
 // The light frame's projection rows (px, py, pz) as HostShadow and LaunchShadow compute them.
 void HostShadowRows(const Camera& light_camera, std::size_t light_width, std::size_t light_height, float rows[9]);
 

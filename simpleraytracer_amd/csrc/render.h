@@ -523,6 +523,29 @@ hipError_t LaunchLighting(const float* d_vertices, const float* d_shade, std::ui
                           const float background[3], const LightingLight* lights, std::size_t count,
                           const LightingArgs& args, hipStream_t stream);
 
+// Lit ray hits (render.hip LightHitsKernel; hits_math.h; DESIGN.md section 2 "Hits"): LaunchLighting
+// for elements given as (ray, id, t) -- the surface point is o + t d of the element's own ray, no
+// view frame is read -- with an optional blend onto a base picture. An element whose direction is
+// zero is absent ((0, 0, 0, -1), or the base element unchanged); one whose id lies outside [0, n) or
+// whose t, o or d is not finite is a miss (the background, alpha -1) and reads nothing through its
+// id. For the eye rays of a frame with the G-buffer's depth the answer is LaunchLighting's, bit for
+// bit.
+struct LightHitsArgs {
+    const float* rays;  // device, elements x 8 (ray_math.h Ray), 16-byte aligned; the range is not read
+    const int* ids;     // device, elements
+    const float* t;     // device, elements
+    std::size_t elements;  // at most 2^31 - 1
+    float ambient[3];
+    const float* base;  // device, elements x 4, 16-byte aligned, or null: the element is stored; may be rgba
+    float weight[3];    // finite (read with a base only): base.rgb + weight . rgb, base's alpha
+    float* rgba;        // device, elements x 4, 16-byte aligned
+    unsigned char* classes;  // device, count x elements (light-major), or null
+};
+// d_shade, n, background: the shaded scene's (n: of every scene). One launch whatever `count`; no
+// elements: none. With class planes a light that is not facing is still scanned, as LaunchLighting's.
+hipError_t LaunchLightHits(const float* d_shade, std::uint64_t n, const float background[3], const LightingLight* lights,
+                           std::size_t count, const LightHitsArgs& args, hipStream_t stream);
+
 // Lit surfaces (render.hip LitSurfaceKernel; material_math.h; DESIGN.md section 2 "Lit surfaces"):
 // LaunchLighting with the pixel's normal and albedo taken from LaunchSurface's tables instead of the
 // shading table, and with a material a Blinn-Phong term: the textured, smooth-shaded, shadowed frame

@@ -5,6 +5,7 @@
 // fmaf, so CPU (oracle/srt_oracle.c) and GPU evaluate bit-identical float expressions.
 #include "render.h"
 #include "gbuffer_math.h"
+#include "hits_math.h"
 #include "layers_math.h"
 #include "lighting_math.h"
 #include "material_math.h"
@@ -4874,6 +4875,94 @@ __global__ __launch_bounds__(kLightingThreads) void LightingKernel(const Lightin
 }
 
 // ---------------------------------------------------------------------------------------
+// Lit ray hits (render.h LaunchLightHits; hits_math.h; DESIGN.md section 5 "Lit hits"): LightingKernel
+// for elements that are (ray, id, t) instead of (pixel, id) -- the hits of a mirror bounce, of probe
+// rays, of rays from another vantage point. Nothing of a view frame is read: the surface point is
+// P = o + t d from the element's own ray, nd = N.d, and from there the light loop is LightingKernel's,
+// LightClassAt unchanged. Launch shape, light frames and light table are LightingKernel's
+// (LightingParams travels whole, the hit pointers and the blend behind it; of its view only n, shade,
+// bg and pixels = the elements mean anything).
+// Every lane of an element's group loads the ray (two float4: one 32-B line per element, contiguous
+// across the block's elements), the id and the t -- one address per group, one request -- decides
+// absent / surface (hits_math.h) and gathers the shading-table row (32 B by id) before the loop. The
+// elements of a bounce scatter over the light frames, so the groups of one wave scan different
+// tiles: the frame index was already per lane, the candidate lists no longer coincide. Lane 0 loads
+// the base element if there is a blend (after the loop: it is needed only for the store, and the
+// address may be the output's own), then stores the float4 and the class bytes. No LDS, no atomics,
+// no scratch.
+// ---------------------------------------------------------------------------------------
+struct LightHitsParams {
+    LightingParams lit;
+    const float4* rays;  // elements x 2
+    const int* ids;
+    const float* t;
+    const F4* base;  // null: store; may be lit.rgba itself
+    float weight[3];
+};
+static_assert(sizeof(LightHitsParams) == sizeof(LightingParams) + 48 && sizeof(LightHitsParams) < 4096,
+              "the light frames, the light table and the hits travel in the kernel-argument segment (< 4 KB)");
+
+template <bool RC>
+__global__ __launch_bounds__(kLightingThreads) void LightHitsKernel(const LightHitsParams h) {
+    const LightingParams& q = h.lit;
+    const unsigned lane = threadIdx.x & (kLightingLanes - 1);
+    const unsigned element = blockIdx.x * kLightingBlock + threadIdx.x / kLightingLanes;
+    if (element >= q.view.pixels) {
+        return;
+    }
+    const ViewBand& v = q.view;
+    const float4 ro = h.rays[2ull * element], rd = h.rays[2ull * element + 1ull];
+    const int code = h.ids[element];
+    const float t = h.t[element];
+    const float o[3] = {ro.x, ro.y, ro.z}, d[3] = {rd.x, rd.y, rd.z};
+    const bool absent = HitAbsent(d);
+    const bool surface = HitSurface(o, d, code, t, v.n);
+    // The element's facts, once for all lights.
+    float P[3] = {0.f, 0.f, 0.f}, N[3] = {0.f, 0.f, 0.f}, al[3] = {0.f, 0.f, 0.f};
+    float nn = 0.f, nd = 0.f;
+    if (surface) {
+        HitPoint(o, d, t, P);
+        const float4* sr = v.shade + 2ull * static_cast<unsigned>(code);
+        const float4 nr = sr[0], ar = sr[1];
+        N[0] = nr.x, N[1] = nr.y, N[2] = nr.z;
+        al[0] = ar.x, al[1] = ar.y, al[2] = ar.z;
+        nn = ShadowDot(N, N);
+        nd = ShadowDot(N, d);
+    }
+    float e0 = q.ambient[0], e1 = q.ambient[1], e2 = q.ambient[2];
+    for (unsigned l = 0u; l < q.count; ++l) {
+        const LightingLightParams& lt = q.light[l];
+        unsigned char cls = kShadowNoSurface;
+        if (surface) {
+            float off[3], nl;
+            bool facing;
+            cls = LightClassAt<RC>(q, lt, P, N, nd, code, lane, off, nl, facing);
+            if (cls == kShadowLit && facing) {
+                const float w = LightingWeight(nl, nn, ShadowDot(off, off), lt.falloff);
+                e0 = e0 + lt.color[0] * w;
+                e1 = e1 + lt.color[1] * w;
+                e2 = e2 + lt.color[2] * w;
+            }
+        }
+        if (lane == 0u && q.classes != nullptr) {
+            q.classes[static_cast<size_t>(l) * v.pixels + element] = cls;
+        }
+    }
+    if (lane == 0u) {
+        float out[4] = {absent ? 0.f : v.bg[0], absent ? 0.f : v.bg[1], absent ? 0.f : v.bg[2], -1.f};
+        if (surface) {
+            out[0] = al[0] * e0, out[1] = al[1] * e1, out[2] = al[2] * e2, out[3] = static_cast<float>(code);
+        }
+        if (h.base != nullptr) {
+            const F4 b = h.base[element];
+            const float base[4] = {b.x, b.y, b.z, b.w};
+            HitBlend(absent, base, h.weight, out);
+        }
+        StoreNontemporal(q.rgba + element, F4{out[0], out[1], out[2], out[3]});
+    }
+}
+
+// ---------------------------------------------------------------------------------------
 // Lit surfaces (render.h LaunchLitSurface; material_math.h; DESIGN.md section 5 "Lit surfaces"):
 // LightingKernel with the pixel's normal and albedo from SurfaceKernel's tables and, with a material,
 // a Blinn-Phong term -- the textured, smooth-shaded, shadowed pixel in one launch. Launch shape,
@@ -6655,13 +6744,12 @@ hipError_t LaunchOmniShadow(const float* d_vertices, const float* d_shade, std::
                           kOmniThreads, stream, q);
 }
 
-// The band, the light frames and the light table of a lighting launch (LaunchLighting,
-// LaunchLitSurface). False: arguments the launchers refuse; else `recompute` is the record source.
-static bool FillLighting(LightingParams& q, const float* d_vertices, const float* d_shade, std::uint64_t n,
-                         const Frame& frame, const float background[3], const LightingLight* lights, std::size_t count,
-                         const LightingArgs& args, bool& recompute) {
-    if (args.rgba == nullptr || count > static_cast<std::size_t>(kLightingMaxLights) || (count != 0 && lights == nullptr) ||
-        !FillViewBand(q.view, d_vertices, d_shade, n, frame, background, args, kLightingBlock)) {
+// The light frames and the light table of a lighting launch over n-triangle scenes, with its outputs
+// and the ambient colour (LaunchLighting, LaunchLitSurface, LaunchLightHits: the view's part is the
+// caller's). False: arguments the launchers refuse; else `recompute` is the record source.
+static bool FillLights(LightingParams& q, std::uint64_t n, const LightingLight* lights, std::size_t count,
+                       const float ambient[3], float* rgba, unsigned char* classes, bool& recompute) {
+    if (rgba == nullptr || count > static_cast<std::size_t>(kLightingMaxLights) || (count != 0 && lights == nullptr)) {
         return false;
     }
     recompute = false;
@@ -6691,13 +6779,24 @@ static bool FillLighting(LightingParams& q, const float* d_vertices, const float
             recompute = rc;
         }
     }
-    q.rgba = reinterpret_cast<F4*>(args.rgba);
-    q.classes = args.classes;
+    q.rgba = reinterpret_cast<F4*>(rgba);
+    q.classes = classes;
     q.count = static_cast<unsigned>(count);
     for (int k = 0; k < 3; ++k) {
-        q.ambient[k] = args.ambient[k];
+        q.ambient[k] = ambient[k];
     }
     return true;
+}
+
+// The band, the light frames and the light table of a lighting launch (LaunchLighting,
+// LaunchLitSurface). False: arguments the launchers refuse; else `recompute` is the record source.
+static bool FillLighting(LightingParams& q, const float* d_vertices, const float* d_shade, std::uint64_t n,
+                         const Frame& frame, const float background[3], const LightingLight* lights, std::size_t count,
+                         const LightingArgs& args, bool& recompute) {
+    return args.rgba != nullptr && count <= static_cast<std::size_t>(kLightingMaxLights) &&
+           (count == 0 || lights != nullptr) &&
+           FillViewBand(q.view, d_vertices, d_shade, n, frame, background, args, kLightingBlock) &&
+           FillLights(q, n, lights, count, args.ambient, args.rgba, args.classes, recompute);
 }
 
 hipError_t LaunchLighting(const float* d_vertices, const float* d_shade, std::uint64_t n, const Frame& frame,
@@ -6713,6 +6812,38 @@ hipError_t LaunchLighting(const float* d_vertices, const float* d_shade, std::ui
     }
     return LaunchBySource(recompute, LightingKernel<true>, LightingKernel<false>, ViewBandGrid(q.view, kLightingBlock),
                           kLightingThreads, stream, q);
+}
+
+hipError_t LaunchLightHits(const float* d_shade, std::uint64_t n, const float background[3], const LightingLight* lights,
+                           std::size_t count, const LightHitsArgs& args, hipStream_t stream) {
+    if (args.elements == 0) {
+        return hipSuccess;
+    }
+    LightHitsParams h{};
+    bool recompute = false;
+    const bool aligned = reinterpret_cast<std::uintptr_t>(args.rays) % 16 == 0 &&
+                         reinterpret_cast<std::uintptr_t>(args.rgba) % 16 == 0 &&
+                         reinterpret_cast<std::uintptr_t>(args.base) % 16 == 0;
+    if (args.rays == nullptr || args.ids == nullptr || args.t == nullptr || d_shade == nullptr || !aligned ||
+        n > 0x7FFFFFFFull || args.elements > 0x7FFFFFFFull || !std::isfinite(args.weight[0]) ||
+        !std::isfinite(args.weight[1]) || !std::isfinite(args.weight[2]) ||
+        !FillLights(h.lit, n, lights, count, args.ambient, args.rgba, args.classes, recompute)) {
+        return hipErrorInvalidValue;
+    }
+    ViewBand& v = h.lit.view;  // (no frame: what the kernel reads of it)
+    v.shade = reinterpret_cast<const float4*>(d_shade);
+    v.n = static_cast<unsigned>(n);
+    v.pixels = static_cast<unsigned>(args.elements);
+    for (int k = 0; k < 3; ++k) {
+        v.bg[k] = background[k];
+        h.weight[k] = args.weight[k];
+    }
+    h.rays = reinterpret_cast<const float4*>(args.rays);
+    h.ids = args.ids;
+    h.t = args.t;
+    h.base = reinterpret_cast<const F4*>(args.base);
+    return LaunchBySource(recompute, LightHitsKernel<true>, LightHitsKernel<false>, ViewBandGrid(v, kLightingBlock),
+                          kLightingThreads, stream, h);
 }
 
 hipError_t LaunchLitSurface(const float* d_vertices, const float* d_shade, std::uint64_t n, const Frame& frame,

@@ -1483,12 +1483,9 @@ void DeviceScene::LitSurface(const Light* lights, std::size_t count, const float
     LightingWith(&surface, lights, count, ambient, d_offsets, d_ids, row_begin, row_count, d_rgba, d_classes, stream);
 }
 
-void DeviceScene::LightingWith(const srt::LitSurface* surface, const Light* lights, std::size_t count,
-                               const float ambient[3], const float* d_offsets, const int* d_ids, std::size_t row_begin,
-                               std::size_t row_count, float* d_rgba, unsigned char* d_classes, hipStream_t stream) const {
-    if (m_width == 0) {
-        throw std::runtime_error("Lighting: Prepare() has not been called on the view scene");
-    }
+// What Lighting, LitSurface and LightHits check of their lights before anything is enqueued or built:
+// CheckLights' rules, then every light frame against this scene and the one record source.
+void DeviceScene::CheckLightFrames(const Light* lights, std::size_t count, const float ambient[3]) const {
     CheckLightCount(count);
     LightTerms terms[kLightingMaxLights];
     for (std::size_t l = 0; l < count; ++l) {
@@ -1519,12 +1516,13 @@ void DeviceScene::LightingWith(const srt::LitSurface* surface, const Light* ligh
             recompute = rc;
         }
     }
-    if (row_begin > m_height || row_count > m_height - row_begin) {
-        throw std::runtime_error("Lighting: row band outside the frame");
-    }
-    if (row_count == 0) {
-        return;
-    }
+}
+
+// The checked lights as a launch takes them: this scene and every light frame ordered after their
+// previous calls on `stream`, every light frame's setup (re)built if it has one, launch(ll), and the
+// call recorded on each.
+template <class Launch>
+void DeviceScene::WithLightFrames(const Light* lights, std::size_t count, hipStream_t stream, Launch&& launch) const {
     OrderAfterPrevious(stream);
     CullSetup setups[kLightingMaxFrames] = {};
     ShadowLight sl[kLightingMaxFrames];
@@ -1537,14 +1535,7 @@ void DeviceScene::LightingWith(const srt::LitSurface* surface, const Light* ligh
             sl[frames] = in.scenes[k]->AsLightFrame(*this, setups[frames], stream);
         }
     }
-    const LightingArgs args{d_offsets, d_ids,  m_width,  m_height, row_begin, row_count, {ambient[0], ambient[1], ambient[2]},
-                            d_rgba,    d_classes};
-    if (surface != nullptr) {
-        HipCheck(LaunchLitSurface(m_vertices, m_shade, m_n, m_frame, m_background, ll, count, args, *surface, stream),
-                 "lit surface launch");
-    } else {
-        HipCheck(LaunchLighting(m_vertices, m_shade, m_n, m_frame, m_background, ll, count, args, stream), "lighting launch");
-    }
+    launch(ll);
     RecordOrder(stream);
     for (std::size_t l = 0; l < count; ++l) {
         for (std::size_t k = 0; k < (lights[l].point ? 6u : 1u); ++k) {
@@ -1553,6 +1544,59 @@ void DeviceScene::LightingWith(const srt::LitSurface* surface, const Light* ligh
             }
         }
     }
+}
+
+void DeviceScene::LightingWith(const srt::LitSurface* surface, const Light* lights, std::size_t count,
+                               const float ambient[3], const float* d_offsets, const int* d_ids, std::size_t row_begin,
+                               std::size_t row_count, float* d_rgba, unsigned char* d_classes, hipStream_t stream) const {
+    if (m_width == 0) {
+        throw std::runtime_error("Lighting: Prepare() has not been called on the view scene");
+    }
+    CheckLightFrames(lights, count, ambient);
+    if (row_begin > m_height || row_count > m_height - row_begin) {
+        throw std::runtime_error("Lighting: row band outside the frame");
+    }
+    if (row_count == 0) {
+        return;
+    }
+    const LightingArgs args{d_offsets, d_ids,  m_width,  m_height, row_begin, row_count, {ambient[0], ambient[1], ambient[2]},
+                            d_rgba,    d_classes};
+    WithLightFrames(lights, count, stream, [&](const LightingLight* ll) {
+        if (surface != nullptr) {
+            HipCheck(LaunchLitSurface(m_vertices, m_shade, m_n, m_frame, m_background, ll, count, args, *surface, stream),
+                     "lit surface launch");
+        } else {
+            HipCheck(LaunchLighting(m_vertices, m_shade, m_n, m_frame, m_background, ll, count, args, stream),
+                     "lighting launch");
+        }
+    });
+}
+
+// Lit ray hits (render.h LaunchLightHits): Lighting's checks, ordering and setups for elements that
+// are (ray, id, t). This scene need not be prepared: the launch reads its shading table, its
+// triangle count and its background only.
+void DeviceScene::LightHits(const Light* lights, std::size_t count, const float ambient[3], const float* d_rays,
+                            const int* d_ids, const float* d_t, std::size_t elements, const float* d_base,
+                            const float weight[3], float* d_rgba, unsigned char* d_classes, hipStream_t stream) const {
+    CheckLightFrames(lights, count, ambient);
+    if (elements > 0x7FFFFFFFull) {
+        throw std::runtime_error("Light hits: at most 2147483647 elements per call, got " + std::to_string(elements));
+    }
+    for (int k = 0; k < 3; ++k) {
+        if (d_base != nullptr && !std::isfinite(weight[k])) {
+            throw std::runtime_error("Light hits: weight value " + std::to_string(k) + " is not finite");
+        }
+    }
+    if (elements == 0) {
+        return;
+    }
+    LightHitsArgs args{d_rays, d_ids, d_t, elements, {ambient[0], ambient[1], ambient[2]}, d_base, {0.f, 0.f, 0.f}, d_rgba, d_classes};
+    for (int k = 0; k < 3 && d_base != nullptr; ++k) {
+        args.weight[k] = weight[k];
+    }
+    WithLightFrames(lights, count, stream, [&](const LightingLight* ll) {
+        HipCheck(LaunchLightHits(m_shade, m_n, m_background, ll, count, args, stream), "light hits launch");
+    });
 }
 
 DeviceScene::StageTimes DeviceScene::TakeTimes() {

@@ -183,6 +183,14 @@ public:
     void LitSurface(const Light* lights, std::size_t count, const float ambient[3], const srt::LitSurface& surface,
                     const float* d_offsets, const int* d_ids, std::size_t row_begin, std::size_t row_count,
                     float* d_rgba, unsigned char* d_classes, hipStream_t stream) const;
+    // Lit ray hits (render.h LaunchLightHits): Lighting for `elements` (at most 2^31 - 1) hits given
+    // as (ray, id, t) -- d_rays elements x 8, d_ids and d_t elements each -- into d_rgba (elements x
+    // 4) and d_classes (may be null; count x elements). d_base (may be null: store; may be d_rgba)
+    // with weight[3] (finite; read with a base only): the element is added onto it. This scene need
+    // not be prepared; every rule of Lighting about the lights applies, in Lighting's words.
+    void LightHits(const Light* lights, std::size_t count, const float ambient[3], const float* d_rays, const int* d_ids,
+                   const float* d_t, std::size_t elements, const float* d_base, const float weight[3], float* d_rgba,
+                   unsigned char* d_classes, hipStream_t stream) const;
 
     // G-buffer: the surface attributes (render.h GBufferArgs: depth, bary, normal, albedo; a null
     // plane is not written) of hit ids on the prepared frame. points: `count` positions d_where
@@ -387,6 +395,11 @@ private:
         const char* its_scene;   // "the light scene" or "the light's scene": whose triangles are counted
     };
     void CheckLightScene(const DeviceScene& f, const DeviceScene& first, const LightWords& w) const;
+    // What Lighting, LitSurface and LightHits share: the lights checked before any side effect, and
+    // the launch between the ordering, the light frames' setups and the recording (renderer.cpp).
+    void CheckLightFrames(const Light* lights, std::size_t count, const float ambient[3]) const;
+    template <class Launch>
+    void WithLightFrames(const Light* lights, std::size_t count, hipStream_t stream, Launch&& launch) const;
     // Lighting (surface == nullptr) and LitSurface: the same checks, ordering and setups, one launch.
     void LightingWith(const srt::LitSurface* surface, const Light* lights, std::size_t count, const float ambient[3],
                       const float* d_offsets, const int* d_ids, std::size_t row_begin, std::size_t row_count,

@@ -21,6 +21,7 @@
 #include "renderer.h"
 #include "scene.h"
 #include "srt_gbuffer.h"
+#include "srt_hits.h"
 #include "srt_layers.h"
 #include "srt_light.h"
 #include "srt_lighting.h"
@@ -1391,6 +1392,79 @@ static_assert(RTD_MAX_LIGHTS == srt::kLightingMaxLights && RTD_MAX_FRAMES == srt
 
 namespace {
 
+// The device lights of a call as DeviceScene takes them (rtdLightAsync, rtpLightSurfaceAsync,
+// rthLightHitsAsync): `in` holds count lights, `scenes` count x 6 scene pointers.
+void CollectDeviceLights(const rtd_light* lights, size_t count, srt::DeviceScene::Light* in,
+                         const srt::DeviceScene** scenes) {
+    for (size_t l = 0; l < count; ++l) {
+        const rtd_light& lt = lights[l];
+        const std::string who = "Lighting: light " + std::to_string(l);
+        if (lt.struct_size != sizeof(rtd_light)) {
+            throw std::runtime_error(who + ": rtd_light.struct_size is " + std::to_string(lt.struct_size) +
+                                     ", expected " + std::to_string(sizeof(rtd_light)));
+        }
+        if ((lt.spot != nullptr) == (lt.point != nullptr)) {
+            throw std::runtime_error(who + ": exactly one of spot and point must be set, got " +
+                                     (lt.spot != nullptr ? "both" : "neither"));
+        }
+        const srt::DeviceScene** mine = scenes + l * srt::kOmniFaces;
+        const bool point = lt.point != nullptr;
+        for (int k = 0; k < (point ? srt::kOmniFaces : 1); ++k) {
+            mine[k] = point ? lt.point->faces[k].get() : FromHandle(lt.spot);
+        }
+        in[l] = srt::DeviceScene::Light{mine, point, {lt.color[0], lt.color[1], lt.color[2]}, lt.falloff, lt.bias};
+    }
+}
+
+// The host lights of a call, checked (rtdLightHost, rtpLightSurfaceHost, rthLightHitsHost): the
+// structs, DeviceScene::CheckLights' rules with the ambient colour, then each light's geometry.
+void CollectHostLights(const rtd_light_host* lights, size_t count, const float ambient[3],
+                       std::vector<srt::HostLight>& in) {
+    std::vector<srt::DeviceScene::LightTerms> terms(count);
+    for (size_t l = 0; l < count; ++l) {
+        const rtd_light_host& lt = lights[l];
+        const std::string who = "Lighting: light " + std::to_string(l);
+        if (lt.struct_size != sizeof(rtd_light_host)) {
+            throw std::runtime_error(who + ": rtd_light_host.struct_size is " + std::to_string(lt.struct_size) +
+                                     ", expected " + std::to_string(sizeof(rtd_light_host)));
+        }
+        if (lt.kind != 0 && lt.kind != 1) {
+            throw std::runtime_error(who + ": kind must be 0 (spot) or 1 (point), got " + std::to_string(lt.kind));
+        }
+        terms[l] = srt::DeviceScene::LightTerms{lt.kind == 1, lt.color, lt.falloff, lt.bias};
+    }
+    srt::DeviceScene::CheckLights(terms.data(), count, ambient);
+    in.assign(count, srt::HostLight{});
+    for (size_t l = 0; l < count; ++l) {
+        const rtd_light_host& lt = lights[l];
+        srt::HostLight& h = in[l];
+        h = srt::HostLight{};
+        h.point = lt.kind == 1;
+        try {
+            if (h.point) {
+                CheckedOrigin(lt.origin);
+                if (lt.face_size == 0) {
+                    throw std::runtime_error("face_size must be non-zero");
+                }
+                std::copy(lt.origin, lt.origin + 3, h.origin);
+                h.face_size = lt.face_size;
+            } else {
+                if (lt.width == 0 || lt.height == 0) {
+                    throw std::runtime_error("frame dimensions must be non-zero");
+                }
+                h.camera = CheckedCamera(lt.camera10);
+                h.width = lt.width;
+                h.height = lt.height;
+            }
+        } catch (std::exception& e) {
+            throw std::runtime_error("Lighting: light " + std::to_string(l) + ": " + e.what());
+        }
+        std::copy(lt.color, lt.color + 3, h.color);
+        h.falloff = lt.falloff;
+        h.bias = lt.bias;
+    }
+}
+
 // rtdLightAsync, and with a `surface` (checked by the caller) rtpLightSurfaceAsync.
 int LightAsync(srt_device_scene view, const rtd_light* lights, size_t count, const float ambient[3],
                const srt::LitSurface* surface, const float* d_offsets, const int* d_ids, size_t row_begin,
@@ -1408,24 +1482,7 @@ int LightAsync(srt_device_scene view, const rtd_light* lights, size_t count, con
         }
         std::vector<srt::DeviceScene::Light> in(count);
         std::vector<const srt::DeviceScene*> scenes(count * srt::kOmniFaces);
-        for (size_t l = 0; l < count; ++l) {
-            const rtd_light& lt = lights[l];
-            const std::string who = "Lighting: light " + std::to_string(l);
-            if (lt.struct_size != sizeof(rtd_light)) {
-                throw std::runtime_error(who + ": rtd_light.struct_size is " + std::to_string(lt.struct_size) +
-                                         ", expected " + std::to_string(sizeof(rtd_light)));
-            }
-            if ((lt.spot != nullptr) == (lt.point != nullptr)) {
-                throw std::runtime_error(who + ": exactly one of spot and point must be set, got " +
-                                         (lt.spot != nullptr ? "both" : "neither"));
-            }
-            const srt::DeviceScene** mine = scenes.data() + l * srt::kOmniFaces;
-            const bool point = lt.point != nullptr;
-            for (int k = 0; k < (point ? srt::kOmniFaces : 1); ++k) {
-                mine[k] = point ? lt.point->faces[k].get() : FromHandle(lt.spot);
-            }
-            in[l] = srt::DeviceScene::Light{mine, point, {lt.color[0], lt.color[1], lt.color[2]}, lt.falloff, lt.bias};
-        }
+        CollectDeviceLights(lights, count, in.data(), scenes.data());
         if (row_count != 0) {
             if (d_offsets == nullptr) {
                 throw std::runtime_error("Bad buffer argument: d_offsets is NULL");
@@ -1468,49 +1525,8 @@ int LightHost(const char* scene_path, size_t width, size_t height, const rtd_lig
         if (ambient == nullptr) {
             throw std::runtime_error("Bad argument: ambient is NULL");
         }
-        std::vector<srt::DeviceScene::LightTerms> terms(count);
-        for (size_t l = 0; l < count; ++l) {
-            const rtd_light_host& lt = lights[l];
-            const std::string who = "Lighting: light " + std::to_string(l);
-            if (lt.struct_size != sizeof(rtd_light_host)) {
-                throw std::runtime_error(who + ": rtd_light_host.struct_size is " + std::to_string(lt.struct_size) +
-                                         ", expected " + std::to_string(sizeof(rtd_light_host)));
-            }
-            if (lt.kind != 0 && lt.kind != 1) {
-                throw std::runtime_error(who + ": kind must be 0 (spot) or 1 (point), got " + std::to_string(lt.kind));
-            }
-            terms[l] = srt::DeviceScene::LightTerms{lt.kind == 1, lt.color, lt.falloff, lt.bias};
-        }
-        srt::DeviceScene::CheckLights(terms.data(), count, ambient);
-        std::vector<srt::HostLight> in(count);
-        for (size_t l = 0; l < count; ++l) {
-            const rtd_light_host& lt = lights[l];
-            srt::HostLight& h = in[l];
-            h = srt::HostLight{};
-            h.point = lt.kind == 1;
-            try {
-                if (h.point) {
-                    CheckedOrigin(lt.origin);
-                    if (lt.face_size == 0) {
-                        throw std::runtime_error("face_size must be non-zero");
-                    }
-                    std::copy(lt.origin, lt.origin + 3, h.origin);
-                    h.face_size = lt.face_size;
-                } else {
-                    if (lt.width == 0 || lt.height == 0) {
-                        throw std::runtime_error("frame dimensions must be non-zero");
-                    }
-                    h.camera = CheckedCamera(lt.camera10);
-                    h.width = lt.width;
-                    h.height = lt.height;
-                }
-            } catch (std::exception& e) {
-                throw std::runtime_error("Lighting: light " + std::to_string(l) + ": " + e.what());
-            }
-            std::copy(lt.color, lt.color + 3, h.color);
-            h.falloff = lt.falloff;
-            h.bias = lt.bias;
-        }
+        std::vector<srt::HostLight> in;
+        CollectHostLights(lights, count, ambient, in);
         if (row_begin > height || row_count > height - row_begin) {
             throw std::runtime_error("Bad argument: row band outside the frame");
         }
@@ -2240,3 +2256,104 @@ ML_API_ENTRY int srtDiagRead(void* host, size_t bytes) {
 #endif
 
 }  // extern "C"
+
+// Lit ray hits (include/srt_hits.h): the rth family. The lights are the rtd family's, collected and
+// checked by the same code, so a refused light is refused in the same words.
+namespace {
+
+// The blend of a call: its base (null without a blend) and weight, the struct checked.
+const float* CheckedBlend(const rth_blend* blend, bool device, float weight[3]) {
+    weight[0] = weight[1] = weight[2] = 0.f;
+    if (blend == nullptr) {
+        return nullptr;
+    }
+    if (blend->struct_size != sizeof(rth_blend)) {
+        throw std::runtime_error("Light hits: rth_blend.struct_size is " + std::to_string(blend->struct_size) +
+                                 ", expected " + std::to_string(sizeof(rth_blend)));
+    }
+    for (int k = 0; k < 3; ++k) {
+        if (!std::isfinite(blend->weight[k])) {
+            throw std::runtime_error("Light hits: weight value " + std::to_string(k) + " is not finite");
+        }
+        weight[k] = blend->weight[k];
+    }
+    return blend->d_base;
+}
+
+void CheckHitBuffers(const float* rays, const int* ids, const float* t, size_t elements, const rth_blend* blend,
+                     const float* base, const float* rgba, bool device) {
+    if (elements > 0x7FFFFFFFull) {
+        throw std::runtime_error("Light hits: at most 2147483647 elements per call, got " + std::to_string(elements));
+    }
+    if (elements == 0) {
+        return;
+    }
+    const std::string d = device ? "d_" : "";
+    CheckRays(rays, (d + "rays").c_str(), device);
+    if (ids == nullptr) {
+        throw std::runtime_error("Bad buffer argument: " + d + "ids is NULL");
+    }
+    if (t == nullptr) {
+        throw std::runtime_error("Bad buffer argument: " + d + "t is NULL");
+    }
+    if (blend != nullptr) {
+        CheckRays(base, "blend->d_base", device);
+    }
+    CheckRays(rgba, (d + "rgba").c_str(), device);
+}
+
+}  // namespace
+
+RTH_API int rthLightHitsAsync(srt_device_scene scene, const rtd_light* lights, size_t count, const float ambient[3],
+                              const float* d_rays, const int* d_ids, const float* d_t, size_t elements,
+                              const rth_blend* blend, float* d_rgba, unsigned char* d_classes, void* stream) {
+    return Guarded([&] {
+        if (scene == nullptr) {
+            throw std::runtime_error("Bad scene handle: scene is NULL");
+        }
+        srt::DeviceScene::CheckLightCount(count);
+        if (count != 0 && lights == nullptr) {
+            throw std::runtime_error("Bad argument: lights is NULL");
+        }
+        if (ambient == nullptr) {
+            throw std::runtime_error("Bad argument: ambient is NULL");
+        }
+        std::vector<srt::DeviceScene::Light> in(count);
+        std::vector<const srt::DeviceScene*> scenes(count * srt::kOmniFaces);
+        CollectDeviceLights(lights, count, in.data(), scenes.data());
+        float weight[3];
+        const float* d_base = CheckedBlend(blend, true, weight);
+        CheckHitBuffers(d_rays, d_ids, d_t, elements, blend, d_base, d_rgba, true);
+        srt::DeviceScene* s = FromHandle(scene);
+        Bind bind(s->device());
+        s->LightHits(in.data(), count, ambient, d_rays, d_ids, d_t, elements, d_base, weight, d_rgba, d_classes,
+                     static_cast<hipStream_t>(stream));
+    });
+}
+
+RTH_API int rthLightHitsHost(const char* scene_path, const rtd_light_host* lights, size_t count, const float ambient[3],
+                             const float* rays, const int* ids, const float* t, size_t elements,
+                             const rth_blend* blend, float* rgba, unsigned char* classes) {
+    return Guarded([&] {
+        if (scene_path == nullptr) {
+            throw std::runtime_error("Bad argument: scene_path is NULL");
+        }
+        srt::DeviceScene::CheckLightCount(count);
+        if (count != 0 && lights == nullptr) {
+            throw std::runtime_error("Bad argument: lights is NULL");
+        }
+        if (ambient == nullptr) {
+            throw std::runtime_error("Bad argument: ambient is NULL");
+        }
+        std::vector<srt::HostLight> in;
+        CollectHostLights(lights, count, ambient, in);
+        float weight[3];
+        const float* base = CheckedBlend(blend, false, weight);
+        CheckHitBuffers(rays, ids, t, elements, blend, base, rgba, false);
+        if (elements == 0) {
+            return;
+        }
+        const srt::Scene scene = srt::LoadScene(scene_path);
+        srt::HostLightHits(scene, in.data(), count, ambient, rays, ids, t, elements, base, weight, rgba, classes);
+    });
+}

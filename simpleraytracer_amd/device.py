@@ -3,7 +3,8 @@
 (include/srt_samples.h), spot-light shadow masks (include/srt_light.h), omni-light shadow masks
 (include/srt_omni.h), direct lighting (include/srt_lighting.h; the lights: lighting.py), dynamic
 scenes (include/srt_motion.h), vertex attributes (include/srt_surface.h), ray queries
-(include/srt_rays.h) and sampled visibility (include/srt_visibility.h).
+(include/srt_rays.h), sampled visibility (include/srt_visibility.h) and lit ray hits
+(include/srt_hits.h).
 
 ``DeviceScene`` keeps a scene resident on one GPU and launches the two stages on a caller's
 HIP stream with caller-owned device buffers (torch tensors or raw pointers):
@@ -22,6 +23,7 @@ HIP stream with caller-owned device buffers (torch tensors or raw pointers):
     scene.surface_frame(offsets, ids, Surface(normals, uvs, texture), rgba=out)  # smooth, textured (also surface(), interpolate())
     scene.closest(rays, ids, t, bary, stream=s)                  # caller-supplied rays, no prepare() needed (also occluded())
     scene.visibility_frame(offsets, ids, Hemisphere(samples, tmin, tmax), fraction=ao)  # ambient occlusion, soft shadows (also visibility(), generate_rays())
+    scene.light_hits(lights, rays, ids, t, rgba, ambient, stream=s)  # what closest()'s hits look like under the lights (also render_reflection())
 
 This is the path bench.py times (inputs resident in HBM) and the one-process-per-GPU
 band renderer uses; ``runner.render`` is the host-image ml* path.
@@ -338,6 +340,51 @@ def lighting_host(path: str, width: int, height: int, lights, ambient, offsets, 
                                       count, lighting.ambient3(ambient), off.ctypes.data, idv.ctypes.data, row_begin,
                                       row_count, rgba.ctypes.data, classes.ctypes.data))
     return rgba, classes
+
+
+def _blend(base_address: int, weight):
+    """The rth_blend of a base picture's address and a weight of 3 floats."""
+    w = tuple(float(v) for v in weight)
+    if len(w) != 3:
+        raise ValueError(f"weight must be 3 floats, got {len(w)}")
+    return _native.RthBlend(ctypes.sizeof(_native.RthBlend), base_address, w)
+
+
+def light_hits_host(path: str, lights, ambient, rays, ids, t, base=None, weight=(1.0, 1.0, 1.0), classes: bool = False):
+    """Lit ray hits on the host (rthLightHitsHost: brute force, the library's canonical math, no
+    device): what the hits of `rays` (count, 8) float32 -- closest_host()'s ids (count,) int32 and t
+    (count,) float32 -- look like under `lights`, a sequence of 0 to 8 lighting.SpotLightHost /
+    lighting.PointLightHost of path's triangles, and the ambient colour -> rgba (count, 4) float32:
+    albedo . (ambient + the lights that reach the hit from the ray's side of its triangle), alpha =
+    the id; the background and -1 for a miss; zeros and -1 for a zero ray (no ray here). base
+    (count, 4) float32 with weight (3 floats): rgba = (base.rgb + weight . rgb, base's alpha), a
+    zero ray keeping base's element. classes=True: -> (rgba, classes (len(lights), count) uint8 of
+    shadow_host()'s classes, light-major)."""
+    import numpy as np
+
+    from . import lighting
+
+    r = _host_rays(rays)
+    count = r.shape[0]
+    idv = np.ascontiguousarray(ids, np.int32)
+    tv = np.ascontiguousarray(t, np.float32)
+    if idv.shape != (count,):
+        raise ValueError(f"ids must be {(count,)}, got {idv.shape}")
+    if tv.shape != (count,):
+        raise ValueError(f"t must be {(count,)}, got {tv.shape}")
+    blend = None
+    if base is not None:
+        b = np.ascontiguousarray(base, np.float32)
+        if b.shape != (count, 4):
+            raise ValueError(f"base must be {(count, 4)}, got {b.shape}")
+        blend = ctypes.byref(_blend(b.ctypes.data, weight))
+    arr, n_lights = lighting.pack_host(lights)
+    rgba = np.empty((count, 4), np.float32)
+    planes = np.empty((n_lights, count), np.uint8) if classes else None
+    _check(_native.lib().rthLightHitsHost(os.fsencode(path), ctypes.addressof(arr) if arr is not None else None, n_lights,
+                                          lighting.ambient3(ambient), r.ctypes.data, idv.ctypes.data, tv.ctypes.data,
+                                          count, blend, rgba.ctypes.data, planes.ctypes.data if classes else None))
+    return (rgba, planes) if classes else rgba
 
 
 def tile_of(width: int, height: int, fx: float, fy: float):
@@ -747,6 +794,21 @@ def _stream(s) -> int:
     if hasattr(s, "cuda_stream"):
         return s.cuda_stream
     return int(s)
+
+
+class ReflectionScratch:
+    """What DeviceScene.render_reflection() keeps of the bounce between its steps, for a width x
+    height frame on cuda:device: rays (1, H, W, 8) float32, ids (H * W,) int32 and t (H * W,)
+    float32 -- the bounce's hits, there to be read after the call."""
+
+    def __init__(self, width: int, height: int, device: int = 0):
+        import torch
+
+        dev = torch.device("cuda", device)
+        self.width, self.height = width, height
+        self.rays = torch.empty((1, height, width, 8), dtype=torch.float32, device=dev)
+        self.ids = torch.empty((height * width,), dtype=torch.int32, device=dev)
+        self.t = torch.empty((height * width,), dtype=torch.float32, device=dev)
 
 
 class DeviceScene:
@@ -1410,6 +1472,53 @@ class DeviceScene:
         available), then light() from them, both on `stream`."""
         self.trace_ids(offsets, ids, variant=variant, stream=stream)
         self.light(lights, offsets, ids, rgba, ambient=ambient, classes=classes, stream=stream)
+
+    def light_hits(self, lights, rays, ids, t, rgba, ambient=(0.0, 0.0, 0.0), classes=None, base=None,
+                   weight=(1.0, 1.0, 1.0), stream=None):
+        """Lit ray hits (include/srt_hits.h): light() for the hits of caller-supplied rays -- a
+        mirror bounce, probe rays, rays from another vantage point. rays (count, 8) float32 with
+        closest()'s ids (count,) int32 and t (count,) float32 -> rgba (count, 4) float32: albedo .
+        (ambient + the lights that reach the hit from the ray's side of its triangle), alpha = the
+        id; the background and -1 for a miss; zeros and -1 for a zero ray (generate_rays()'s "no ray
+        here"). classes (len(lights), count) uint8, optional. base (count, 4) float32 with weight
+        (3 floats): rgba = (base.rgb + weight . rgb, base's alpha), a zero ray keeping base's
+        element; base may be rgba itself. `lights` as light()'s; this scene needs no prepare(). One
+        launch whatever len(lights). Device buffers, checked like closest()'s."""
+        from . import lighting
+
+        count = self._ray_count((("rays", rays, (8,), "f32"), ("ids", ids, (), "i32"), ("t", t, (), "f32"),
+                                 ("rgba", rgba, (4,), "f32"), ("base", base, (4,), "f32")))
+        arr, n_lights = lighting.pack_device(lights)
+        if classes is not None:
+            if hasattr(classes, "shape") and tuple(classes.shape) != (n_lights, count):
+                raise ValueError(f"classes must be {(n_lights, count)}, got {tuple(classes.shape)}")
+            self._check_tensor("classes", classes, "u8")
+        blend = ctypes.byref(_blend(_ptr(base), weight)) if base is not None else None
+        _check(self._lib.rthLightHitsAsync(self.handle, ctypes.addressof(arr) if arr is not None else None, n_lights,
+                                           lighting.ambient3(ambient), _ptr(rays), _ptr(ids), _ptr(t), count, blend,
+                                           _ptr(rgba), _ptr(classes), _stream(stream)))
+
+    def render_reflection(self, lights, offsets, ids, rgba, reflectivity, ambient=(0.0, 0.0, 0.0),
+                          tmin: float = 2.0 ** -10, scratch=None, variant: str = "cull", stream=None):
+        """The lit picture of the whole prepared frame with one mirror bounce added, on `stream`:
+        trace_ids() into ids ((H, W) int32), light() into rgba ((H, W, 4) float32), the mirror rays
+        of the frame (generate_rays_frame(Mirror(tmin))), their closest() hits, and light_hits() of
+        those onto rgba in place with weight `reflectivity` (3 floats). A pixel without a surface has
+        no bounce and keeps the lit frame's background. scratch: a ReflectionScratch of the frame's
+        size holding the bounce's rays, ids and t (None: a new one; pass one to allocate nothing in
+        later calls). Returns the scratch."""
+        if scratch is None:
+            scratch = ReflectionScratch(self.width, self.height, self.device)
+        if (scratch.width, scratch.height) != (self.width, self.height):
+            raise ValueError(f"scratch is {scratch.width} x {scratch.height}, the frame {self.width} x {self.height}")
+        flat = rgba.view(-1, 4)
+        self.trace_ids(offsets, ids, variant=variant, stream=stream)
+        self.light(lights, offsets, ids, rgba, ambient=ambient, stream=stream)
+        self.generate_rays_frame(offsets, ids, Mirror(tmin), scratch.rays, stream=stream)
+        self.closest(scratch.rays.view(-1, 8), scratch.ids, scratch.t, stream=stream)
+        self.light_hits(lights, scratch.rays.view(-1, 8), scratch.ids, scratch.t, flat, ambient=ambient, base=flat,
+                        weight=reflectivity, stream=stream)
+        return scratch
 
     def light_surface(self, lights, offsets, ids, surface, rgba, ambient=(0.0, 0.0, 0.0), material=None, classes=None,
                       row_begin: int = 0, row_count: int | None = None, stream=None):
