@@ -16,13 +16,13 @@ HIPFLAGS := --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -ffp-contract=off -fno-s
             -fvisibility=hidden -DRADEONPROML_BUILD -Iinclude -Wall -Wno-unused-result
 LDFLAGS  := -shared -L/opt/rocm/lib -lrccl -Wl,-rpath,/opt/rocm/lib -Wl,--no-undefined
 
-OBJS := $(BUILD)/render.o $(BUILD)/spatial.o $(BUILD)/rays.o $(BUILD)/visibility.o $(BUILD)/renderer.o $(BUILD)/engine.o $(BUILD)/comm.o $(BUILD)/cpu_render.o \
+OBJS := $(BUILD)/render.o $(BUILD)/spatial.o $(BUILD)/rays.o $(BUILD)/visibility.o $(BUILD)/radiance.o $(BUILD)/renderer.o $(BUILD)/engine.o $(BUILD)/comm.o $(BUILD)/cpu_render.o \
         $(BUILD)/scene.o $(BUILD)/image.o $(BUILD)/model.o $(BUILD)/context.o $(BUILD)/srt_api.o
 
 HEADERS := $(wildcard $(CSRC)/*.h) include/model_runner.h include/srt_render.h include/srt_query.h include/srt_gbuffer.h \
            include/srt_samples.h include/srt_light.h include/srt_layers.h include/srt_omni.h \
            include/srt_lighting.h include/srt_motion.h include/srt_surface.h include/srt_material.h \
-           include/srt_rays.h include/srt_visibility.h include/srt_hits.h
+           include/srt_rays.h include/srt_visibility.h include/srt_hits.h include/srt_radiance.h
 
 # Diagnostic build (per-block cull phase counters, srtDiagRead): never the product library.
 DIAG_BUILD := build/diag

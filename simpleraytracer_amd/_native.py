@@ -217,6 +217,16 @@ class RthBlend(ctypes.Structure):
     ]
 
 
+class RtiOptions(ctypes.Structure):
+    """``rti_options`` (include/srt_radiance.h): modulate and the blend (an RthBlend's address, or None)."""
+
+    _fields_ = [
+        ("struct_size", ctypes.c_size_t),
+        ("modulate", ctypes.c_int),
+        ("blend", ctypes.POINTER(RthBlend)),
+    ]
+
+
 RTP_MAX_SHININESS_LOG2 = 12  # include/srt_material.h: the Blinn-Phong exponent is 2^shininess_log2
 
 
@@ -428,6 +438,16 @@ _SIGNATURES = {
     "rthLightHitsHost": (ctypes.c_int, [ctypes.c_char_p, ctypes.c_void_p, _SZ, ctypes.POINTER(ctypes.c_float),
                                         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, _SZ, ctypes.POINTER(RthBlend),
                                         ctypes.c_void_p, ctypes.c_void_p]),
+    # include/srt_radiance.h: sampled radiance (lights, ambient: rtdLight*'s; gen: rta's; options: an RtiOptions or None)
+    "rtiRadianceFrameAsync": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, _SZ, ctypes.POINTER(ctypes.c_float),
+                                             ctypes.c_void_p, ctypes.c_void_p, _SZ, _SZ, ctypes.POINTER(RtaGenerator),
+                                             ctypes.POINTER(RtiOptions), ctypes.c_void_p, ctypes.c_void_p]),
+    "rtiRadiancePointsAsync": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, _SZ, ctypes.POINTER(ctypes.c_float),
+                                              ctypes.c_void_p, ctypes.c_void_p, _SZ, ctypes.POINTER(RtaGenerator),
+                                              ctypes.POINTER(RtiOptions), ctypes.c_void_p, ctypes.c_void_p]),
+    "rtiRadianceHost": (ctypes.c_int, [ctypes.c_char_p, _SZ, _SZ, ctypes.c_void_p, _SZ, ctypes.POINTER(ctypes.c_float),
+                                       ctypes.c_void_p, ctypes.c_void_p, _SZ, ctypes.POINTER(RtaGenerator),
+                                       ctypes.POINTER(RtiOptions), ctypes.c_void_p]),
 }
 
 _lib = None

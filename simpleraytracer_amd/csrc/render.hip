@@ -9,6 +9,8 @@
 #include "layers_math.h"
 #include "lighting_math.h"
 #include "material_math.h"
+#include "radiance.h"
+#include "ray_walk.h"
 #include "samples_math.h"
 #include "screen_box.h"
 #include "omni_math.h"
@@ -16,6 +18,7 @@
 #include "shadow_math.h"
 #include "surface_math.h"
 #include "tile_lookup.h"
+#include "visibility_device.h"
 
 #include <hip/hip_ext.h>
 
@@ -4963,6 +4966,232 @@ __global__ __launch_bounds__(kLightingThreads) void LightHitsKernel(const LightH
 }
 
 // ---------------------------------------------------------------------------------------
+// Sampled radiance (radiance.h LaunchRadiance; DESIGN.md sections 2 and 5 "Radiance"): per element of
+// the prepared frame the S rays of a generator, each walked to its closest hit, the hit shaded under
+// the lights and the S colours added in ascending s -- the composition VisibilityKernel (export) ->
+// RayTreeKernel -> LightHitsKernel -> an ordered sum in one launch, a ray living in registers and LDS.
+// It joins two lane mappings. The block compacts its 256 elements on a surface into LDS slots as
+// VisibilityPackedKernel does and deals the slots x S rays sample-major, item = s slots + slot, in
+// rounds of 256:
+//   walk    lane i generates item base + i (RayOf) and walks it (RayWalk<true>, or RayScan<true>:
+//           BRUTE), leaving the direction, the t and the id in the round's LDS record i;
+//   shade   the block's 16 groups of kLightingLanes lanes take the round's records 16 j + group,
+//           j = 0 ... 15: LightHitsKernel's body on (the slot's point, the record), LightClassAt
+//           unchanged; lane 0 of the group leaves the colour and the alpha in the record's place;
+//   add     lane i < slots adds slot i's colours of the round in ascending item, so in ascending s:
+//           rounds follow each other in ascending item too, and the sum is a plain register chain --
+//           no atomics, no tree.
+// After the last round the sums go through LDS to the elements' own lanes, which divide, modulate,
+// blend and store. A block without an element on a surface takes no round. LDS: 9 + 1 + 5 KB of slot
+// and record rows and under 1 KB of tables.
+// ---------------------------------------------------------------------------------------
+struct RadianceParams {
+    LightingParams lit;  // (of its view: n, shade, bg)
+    VisibilityParams vis;
+    const F4* base;  // null: store; may be lit.rgba itself
+    float weight[3];
+    unsigned modulate;
+    unsigned points;  // 1: a points call
+    int kind;         // kVisibilityHemisphere or kVisibilityMirror
+};
+static_assert(sizeof(RadianceParams) < 4096,
+              "the light frames, the light table and the generator travel in the kernel-argument segment (< 4 KB)");
+static_assert(kVisibilityThreads == 256 && kLightingThreads == 256 && kLightingLanes == 16,
+              "RadianceKernel: a round is 256 rays, shaded by 16 groups of 16 lanes");
+
+template <bool RC, bool BRUTE>
+__global__ __launch_bounds__(kLightingThreads) void RadianceKernel(const RadianceParams r) {
+    constexpr unsigned kThreads = kLightingThreads, kWaves = kThreads / kWave, kGroups = kThreads / kLightingLanes;
+    const LightingParams& q = r.lit;
+    const VisibilityParams& p = r.vis;
+    __shared__ float s_samples[kVisibilityMaxSamples * 3];
+    __shared__ float2 s_turns[kVisibilityRotations];
+    __shared__ unsigned s_count[kBvhMaxLevels], s_offset[kBvhMaxLevels];
+    __shared__ unsigned s_levels;
+    __shared__ float s_surface[9][kThreads];  // p.xyz, n.xyz, d.xyz (the mirror's) by slot
+    __shared__ unsigned s_turn[kThreads];     // the slot's rotation index
+    __shared__ unsigned s_wave[kWaves];
+    // The round's records: direction (then colour), t (then alpha), id. After the last round: the sums.
+    __shared__ float s_rec[5][kThreads];
+    const unsigned tid = threadIdx.x;
+    const unsigned S = p.samples_count;
+    const bool hemisphere = r.kind == kVisibilityHemisphere;
+    const bool rotate = hemisphere && p.rotations != nullptr;
+    if (hemisphere) {
+        for (unsigned i = tid; i < S * 3u; i += kThreads) {  // (S <= 64: at most 192 floats)
+            s_samples[i] = p.samples[i];
+        }
+    }
+    if (rotate && tid < kVisibilityRotations) {
+        s_turns[tid] = p.rotations[tid];
+    }
+    if (!BRUTE && tid == 0) {
+        RayLevelsInit(p.n, s_count, s_offset, &s_levels);
+    }
+    // Compact the block's elements on a surface (VisibilityPackedKernel's ranks).
+    const unsigned wave = tid / kWave, wlane = tid & (kWave - 1);
+    const VisibilityElement el = r.points != 0u ? ElementOf<true>(p, tid) : ElementOf<false>(p, tid);
+    const bool on = el.in && el.sf.valid;
+    const unsigned long long ballot = __ballot(on);
+    unsigned rank = static_cast<unsigned>(__popcll(ballot & ((1ull << wlane) - 1ull)));
+    if (wlane == 0) {
+        s_wave[wave] = static_cast<unsigned>(__popcll(ballot));
+    }
+    __syncthreads();
+    unsigned slots = 0;
+#pragma unroll
+    for (unsigned w = 0; w < kWaves; ++w) {
+        if (w == wave) {
+            rank += slots;
+        }
+        slots += s_wave[w];
+    }
+    if (on) {
+#pragma unroll
+        for (int j = 0; j < 3; ++j) {
+            s_surface[j][rank] = el.sf.p[j];
+            s_surface[3 + j][rank] = el.sf.n[j];
+            s_surface[6 + j][rank] = el.sf.d[j];
+        }
+        s_turn[rank] = el.turn;
+    }
+    __syncthreads();
+    const unsigned items = slots * S;  // (<= 256 x 64)
+    const unsigned group = tid / kLightingLanes, lane = tid & (kLightingLanes - 1);
+    const ViewBand& v = q.view;
+    float sum[3] = {0.f, 0.f, 0.f};  // of slot tid
+    unsigned hits = 0;
+    for (unsigned begin = 0; begin < items; begin += kThreads) {
+        const unsigned live = items - begin < kThreads ? items - begin : kThreads;
+        // Walk: one ray per lane.
+        if (tid < live) {
+            const unsigned item = begin + tid;
+            const unsigned s = item / slots, at = item - s * slots;
+            const float pt[3] = {s_surface[0][at], s_surface[1][at], s_surface[2][at]};
+            const float n[3] = {s_surface[3][at], s_surface[4][at], s_surface[5][at]};
+            Ray ray;
+            if (hemisphere) {
+                float T[3], B[3];
+                float2 turn = make_float2(1.f, 0.f);
+                VisibilityBasis(n, T, B);
+                if (rotate) {
+                    turn = s_turns[s_turn[at] & (kVisibilityRotations - 1)];
+                }
+                ray = RayOf<kVisibilityHemisphere>(p, s_samples, s, pt, pt, n, T, B, rotate, turn.x, turn.y);
+            } else {
+                const float d[3] = {s_surface[6][at], s_surface[7][at], s_surface[8][at]};
+                ray = RayOf<kVisibilityMirror>(p, s_samples, s, pt, d, n, n, n, false, 1.f, 0.f);
+            }
+            RayBest best;
+            if constexpr (BRUTE) {
+                best = RayScan<true>(ray, p.vertices, p.n);
+            } else {
+                best = RayWalk<true>(ray, p.nodes, p.records, s_count, s_offset, &s_levels);
+            }
+            s_rec[0][tid] = ray.d[0];
+            s_rec[1][tid] = ray.d[1];
+            s_rec[2][tid] = ray.d[2];
+            s_rec[3][tid] = best.t;
+            s_rec[4][tid] = __int_as_float(best.id);
+        }
+        __syncthreads();
+        // Shade: LightHitsKernel's body, a group of kLightingLanes lanes per record.
+        for (unsigned j = 0; j < kThreads / kGroups; ++j) {
+            const unsigned h = j * kGroups + group;
+            if (h >= live) {
+                break;  // (the same for the whole group)
+            }
+            const unsigned at = (begin + h) % slots;
+            const float o[3] = {s_surface[0][at], s_surface[1][at], s_surface[2][at]};
+            const float d[3] = {s_rec[0][h], s_rec[1][h], s_rec[2][h]};
+            const float t = s_rec[3][h];
+            const int code = __float_as_int(s_rec[4][h]);
+            const bool absent = HitAbsent(d);
+            const bool surface = HitSurface(o, d, code, t, v.n);
+            float P[3] = {0.f, 0.f, 0.f}, N[3] = {0.f, 0.f, 0.f}, al[3] = {0.f, 0.f, 0.f};
+            float nn = 0.f, nd = 0.f;
+            if (surface) {
+                HitPoint(o, d, t, P);
+                const float4* sr = v.shade + 2ull * static_cast<unsigned>(code);
+                const float4 nr = sr[0], ar = sr[1];
+                N[0] = nr.x, N[1] = nr.y, N[2] = nr.z;
+                al[0] = ar.x, al[1] = ar.y, al[2] = ar.z;
+                nn = ShadowDot(N, N);
+                nd = ShadowDot(N, d);
+            }
+            float e0 = q.ambient[0], e1 = q.ambient[1], e2 = q.ambient[2];
+            for (unsigned l = 0u; l < q.count; ++l) {
+                const LightingLightParams& lt = q.light[l];
+                if (surface) {
+                    float off[3], nl;
+                    bool facing;
+                    const unsigned char cls = LightClassAt<RC>(q, lt, P, N, nd, code, lane, off, nl, facing);
+                    if (cls == kShadowLit && facing) {
+                        const float w = LightingWeight(nl, nn, ShadowDot(off, off), lt.falloff);
+                        e0 = e0 + lt.color[0] * w;
+                        e1 = e1 + lt.color[1] * w;
+                        e2 = e2 + lt.color[2] * w;
+                    }
+                }
+            }
+            if (lane == 0u) {
+                float out[4] = {absent ? 0.f : v.bg[0], absent ? 0.f : v.bg[1], absent ? 0.f : v.bg[2], -1.f};
+                if (surface) {
+                    out[0] = al[0] * e0, out[1] = al[1] * e1, out[2] = al[2] * e2, out[3] = static_cast<float>(code);
+                }
+                s_rec[0][h] = out[0];
+                s_rec[1][h] = out[1];
+                s_rec[2][h] = out[2];
+                s_rec[3][h] = out[3];
+            }
+        }
+        __syncthreads();
+        // Add: slot tid's records of the round, ascending.
+        if (tid < slots) {
+            const unsigned skip = begin % slots;
+            for (unsigned h = tid >= skip ? tid - skip : tid + slots - skip; h < live; h += slots) {
+                sum[0] = sum[0] + s_rec[0][h];
+                sum[1] = sum[1] + s_rec[1][h];
+                sum[2] = sum[2] + s_rec[2][h];
+                hits += s_rec[3][h] >= 0.f ? 1u : 0u;
+            }
+        }
+        __syncthreads();
+    }
+    if (tid < slots) {
+        s_rec[0][tid] = sum[0];
+        s_rec[1][tid] = sum[1];
+        s_rec[2][tid] = sum[2];
+        s_rec[3][tid] = __uint_as_float(hits);
+    }
+    __syncthreads();
+    if (!el.in) {
+        return;
+    }
+    float out[4] = {0.f, 0.f, 0.f, 0.f};
+    if (on) {
+        const float fs = static_cast<float>(S);
+        float al[3] = {1.f, 1.f, 1.f};
+        if (r.modulate != 0u) {
+            const float4 ar = v.shade[2ull * static_cast<unsigned>(p.ids[el.e]) + 1ull];
+            al[0] = ar.x, al[1] = ar.y, al[2] = ar.z;
+        }
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            const float m = s_rec[k][rank] / fs;
+            out[k] = r.modulate != 0u ? al[k] * m : m;
+        }
+        out[3] = static_cast<float>(__float_as_uint(s_rec[3][rank])) / fs;
+    }
+    if (r.base != nullptr) {
+        const F4 b = r.base[el.e];
+        const float base[4] = {b.x, b.y, b.z, b.w};
+        HitBlend(!on, base, r.weight, out);
+    }
+    StoreNontemporal(q.rgba + el.e, F4{out[0], out[1], out[2], out[3]});
+}
+
+// ---------------------------------------------------------------------------------------
 // Lit surfaces (render.h LaunchLitSurface; material_math.h; DESIGN.md section 5 "Lit surfaces"):
 // LightingKernel with the pixel's normal and albedo from SurfaceKernel's tables and, with a material,
 // a Blinn-Phong term -- the textured, smooth-shaded, shadowed pixel in one launch. Launch shape,
@@ -6844,6 +7073,54 @@ hipError_t LaunchLightHits(const float* d_shade, std::uint64_t n, const float ba
     h.base = reinterpret_cast<const F4*>(args.base);
     return LaunchBySource(recompute, LightHitsKernel<true>, LightHitsKernel<false>, ViewBandGrid(v, kLightingBlock),
                           kLightingThreads, stream, h);
+}
+
+hipError_t LaunchRadiance(const RayTree* tree, const float* d_vertices, const float* d_shade, std::uint64_t n,
+                          const Frame& frame, const float background[3], const LightingLight* lights, std::size_t count,
+                          const float ambient[3], const VisibilityElements& e, const VisibilityGen& gen,
+                          const RadianceStore& store, hipStream_t stream) {
+    const unsigned long long elements = static_cast<unsigned long long>(e.width) * e.rows;
+    if (elements == 0) {
+        return hipSuccess;
+    }
+    RadianceParams r{};
+    bool recompute = false;
+    const bool aligned = reinterpret_cast<std::uintptr_t>(store.rgba) % 16 == 0 &&
+                         reinterpret_cast<std::uintptr_t>(store.base) % 16 == 0;
+    const bool kind = gen.kind == kVisibilityHemisphere || (gen.kind == kVisibilityMirror && gen.count == 1);
+    if (e.where == nullptr || e.ids == nullptr || d_shade == nullptr || !aligned || !kind || gen.count < 1 ||
+        gen.count > kVisibilityMaxSamples || (gen.kind == kVisibilityHemisphere && gen.samples == nullptr) ||
+        n > 0x7FFFFFFFull || elements > 0x7FFFFFFFull || !std::isfinite(store.weight[0]) ||
+        !std::isfinite(store.weight[1]) || !std::isfinite(store.weight[2]) ||
+        !FillLights(r.lit, n, lights, count, ambient, store.rgba, nullptr, recompute)) {
+        return hipErrorInvalidValue;
+    }
+    ViewBand& v = r.lit.view;  // (what the light scan and the store read of it)
+    v.shade = reinterpret_cast<const float4*>(d_shade);
+    v.n = static_cast<unsigned>(n);
+    v.pixels = static_cast<unsigned>(elements);
+    for (int k = 0; k < 3; ++k) {
+        v.bg[k] = background[k];
+        r.weight[k] = store.weight[k];
+    }
+    r.vis.vertices = d_vertices;
+    r.vis.n = static_cast<unsigned>(n);
+    const bool brute = tree == nullptr || n == 0;
+    if (!brute) {
+        r.vis.nodes = tree->nodes;
+        r.vis.records = tree->records;
+    }
+    const dim3 grid = FillVisibility(r.vis, frame, e, gen, 1u);
+    r.base = reinterpret_cast<const F4*>(store.base);
+    r.modulate = store.modulate ? 1u : 0u;
+    r.points = e.points ? 1u : 0u;
+    r.kind = gen.kind;
+    if (brute) {
+        return LaunchBySource(recompute, RadianceKernel<true, true>, RadianceKernel<false, true>, grid, kLightingThreads,
+                              stream, r);
+    }
+    return LaunchBySource(recompute, RadianceKernel<true, false>, RadianceKernel<false, false>, grid, kLightingThreads,
+                          stream, r);
 }
 
 hipError_t LaunchLitSurface(const float* d_vertices, const float* d_shade, std::uint64_t n, const Frame& frame,

@@ -12,6 +12,7 @@
 #include "comm.h"
 #include "engine.h"
 #include "lighting_math.h"
+#include "radiance.h"
 #include "rays.h"
 #include "render.h"
 #include "visibility.h"
@@ -1597,6 +1598,46 @@ void DeviceScene::LightHits(const Light* lights, std::size_t count, const float 
     WithLightFrames(lights, count, stream, [&](const LightingLight* ll) {
         HipCheck(LaunchLightHits(m_shade, m_n, m_background, ll, count, args, stream), "light hits launch");
     });
+}
+
+// Sampled radiance (radiance.h LaunchRadiance): Visibility's frame checks, Lighting's light checks,
+// then -- nothing enqueued or built before every check has passed -- the ordering and the light
+// frames' setups of Lighting, the ray tree of Closest, and one launch.
+void DeviceScene::Radiance(const Light* lights, std::size_t count, const float ambient[3], bool points,
+                           const float* d_where, const int* d_ids, std::size_t row_begin, std::size_t elements,
+                           const VisibilityGen& gen, bool modulate, const float* d_base, const float weight[3],
+                           float* d_rgba, hipStream_t stream) const {
+    if (m_width == 0) {
+        throw std::runtime_error("Radiance: Prepare() has not been called");
+    }
+    CheckLightFrames(lights, count, ambient);
+    if (!points && (row_begin > m_height || elements > m_height - row_begin)) {
+        throw std::runtime_error("Radiance: row band outside the frame");
+    }
+    const VisibilityElements e = ElementsOf(points, d_where, d_ids, row_begin, elements, m_width, m_height);
+    if (static_cast<unsigned long long>(e.width) * e.rows > 0x7FFFFFFFull) {
+        throw std::runtime_error("Radiance: at most 2147483647 elements per call, got " +
+                                 std::to_string(static_cast<unsigned long long>(e.width) * e.rows));
+    }
+    if (elements == 0) {
+        return;
+    }
+    RadianceStore store{modulate, d_base, {0.f, 0.f, 0.f}, d_rgba};
+    for (int k = 0; k < 3 && d_base != nullptr; ++k) {
+        store.weight[k] = weight[k];
+    }
+    WithLightFrames(lights, count, stream, [&](const LightingLight* ll) {
+        try {
+            const RayTree* tree = EnsureRayTree(stream);
+            HipCheck(LaunchRadiance(tree, m_vertices, m_shade, m_n, m_frame, m_background, ll, count, ambient, e, gen, store,
+                                    stream),
+                     "radiance launch");
+        } catch (...) {
+            RecordOrder(stream);
+            throw;
+        }
+    });
+    LogRayStats();
 }
 
 DeviceScene::StageTimes DeviceScene::TakeTimes() {

@@ -191,6 +191,15 @@ public:
     void LightHits(const Light* lights, std::size_t count, const float ambient[3], const float* d_rays, const int* d_ids,
                    const float* d_t, std::size_t elements, const float* d_base, const float weight[3], float* d_rgba,
                    unsigned char* d_classes, hipStream_t stream) const;
+    // Sampled radiance (radiance.h LaunchRadiance): per element of the prepared frame -- Visibility's
+    // elements -- the generator's rays walked to their closest hits, the hits shaded as LightHits shades
+    // them and averaged in ascending sample order, one launch. gen.kind: hemisphere or mirror.
+    // modulate: times the albedo of the element's own triangle. d_base (may be null: store; may be
+    // d_rgba) with weight[3] (finite; read with a base only). The ray tree as Closest's; every rule of
+    // Lighting about the lights applies, in Lighting's words.
+    void Radiance(const Light* lights, std::size_t count, const float ambient[3], bool points, const float* d_where,
+                  const int* d_ids, std::size_t row_begin, std::size_t elements, const VisibilityGen& gen, bool modulate,
+                  const float* d_base, const float weight[3], float* d_rgba, hipStream_t stream) const;
 
     // G-buffer: the surface attributes (render.h GBufferArgs: depth, bary, normal, albedo; a null
     // plane is not written) of hit ids on the prepared frame. points: `count` positions d_where

@@ -15,6 +15,7 @@
 #include "lighting_math.h"
 #include "material_math.h"
 #include "omni_math.h"
+#include "radiance.h"
 #include "ray_math.h"
 #include "rays.h"
 #include "render.h"
@@ -29,6 +30,7 @@
 #include "srt_motion.h"
 #include "srt_omni.h"
 #include "srt_query.h"
+#include "srt_radiance.h"
 #include "srt_rays.h"
 #include "srt_render.h"
 #include "srt_samples.h"
@@ -2357,3 +2359,147 @@ RTH_API int rthLightHitsHost(const char* scene_path, const rtd_light_host* light
         srt::HostLightHits(scene, in.data(), count, ambient, rays, ids, t, elements, base, weight, rgba, classes);
     });
 }
+
+// Sampled radiance (include/srt_radiance.h): the rti family. The generator is the rta family's, the
+// lights the rtd family's and the blend the rth family's, each checked by that family's code.
+namespace {
+
+struct RadianceOptions {
+    bool modulate;
+    const float* base;  // null without a blend
+    float weight[3];
+};
+
+RadianceOptions CheckedRadianceOptions(const rti_options* options) {
+    RadianceOptions out{false, nullptr, {0.f, 0.f, 0.f}};
+    if (options == nullptr) {
+        return out;
+    }
+    if (options->struct_size != sizeof(rti_options)) {
+        throw std::runtime_error("Radiance: rti_options.struct_size is " + std::to_string(options->struct_size) +
+                                 ", expected " + std::to_string(sizeof(rti_options)));
+    }
+    out.modulate = options->modulate != 0;
+    const rth_blend* blend = options->blend;
+    if (blend == nullptr) {
+        return out;
+    }
+    if (blend->struct_size != sizeof(rth_blend)) {
+        throw std::runtime_error("Radiance: rth_blend.struct_size is " + std::to_string(blend->struct_size) +
+                                 ", expected " + std::to_string(sizeof(rth_blend)));
+    }
+    for (int k = 0; k < 3; ++k) {
+        if (!std::isfinite(blend->weight[k])) {
+            throw std::runtime_error("Radiance: blend weight value " + std::to_string(k) + " is not finite");
+        }
+        out.weight[k] = blend->weight[k];
+    }
+    if (blend->d_base == nullptr) {
+        throw std::runtime_error("Bad buffer argument: blend->d_base is NULL");
+    }
+    out.base = blend->d_base;
+    return out;
+}
+
+// The generator of a radiance call: rta's checks, then the kinds whose rays aim at surfaces.
+srt::VisibilityGen CheckedRadianceGenerator(const rta_generator* gen) {
+    const srt::VisibilityGen g = CheckedGenerator(gen, false);
+    if (g.kind == RTA_AREA) {
+        throw std::runtime_error(
+            "rta_generator.kind is RTA_AREA: its rays aim at a light, not at surfaces; radiance takes RTA_HEMISPHERE or "
+            "RTA_MIRROR");
+    }
+    return g;
+}
+
+void CheckRadianceBuffers(const float* where, const char* where_name, const int* ids, const char* ids_name,
+                          const RadianceOptions& o, const float* rgba, const char* rgba_name, bool device) {
+    CheckElements(where, where_name, ids, ids_name);
+    if (o.base != nullptr) {
+        CheckRays(o.base, "blend->d_base", device);
+    }
+    CheckRays(rgba, rgba_name, device);
+}
+
+int RadianceAsync(srt_device_scene scene, const rtd_light* lights, size_t count, const float ambient[3], bool points,
+                  const float* d_where, const char* where_name, const int* d_ids, size_t row_begin, size_t elements,
+                  const rta_generator* gen, const rti_options* options, float* d_rgba, void* stream) {
+    return Guarded([&] {
+        if (scene == nullptr) {
+            throw std::runtime_error("Bad scene handle: scene is NULL");
+        }
+        srt::DeviceScene::CheckLightCount(count);
+        if (count != 0 && lights == nullptr) {
+            throw std::runtime_error("Bad argument: lights is NULL");
+        }
+        if (ambient == nullptr) {
+            throw std::runtime_error("Bad argument: ambient is NULL");
+        }
+        const srt::VisibilityGen g = CheckedRadianceGenerator(gen);
+        const RadianceOptions o = CheckedRadianceOptions(options);
+        std::vector<srt::DeviceScene::Light> in(count);
+        std::vector<const srt::DeviceScene*> scenes(count * srt::kOmniFaces);
+        CollectDeviceLights(lights, count, in.data(), scenes.data());
+        if (elements != 0) {
+            CheckRadianceBuffers(d_where, where_name, d_ids, "d_ids", o, d_rgba, "d_rgba", true);
+        }
+        srt::DeviceScene* s = FromHandle(scene);
+        Bind bind(s->device());
+        s->Radiance(in.data(), count, ambient, points, d_where, d_ids, row_begin, elements, g, o.modulate, o.base,
+                    o.weight, d_rgba, static_cast<hipStream_t>(stream));
+    });
+}
+
+}  // namespace
+
+extern "C" {
+
+RTI_API int rtiRadianceFrameAsync(srt_device_scene scene, const rtd_light* lights, size_t count, const float ambient[3],
+                                  const float* d_offsets, const int* d_ids, size_t row_begin, size_t row_count,
+                                  const rta_generator* gen, const rti_options* options, float* d_rgba, void* stream) {
+    return RadianceAsync(scene, lights, count, ambient, false, d_offsets, "d_offsets", d_ids, row_begin, row_count, gen,
+                         options, d_rgba, stream);
+}
+
+RTI_API int rtiRadiancePointsAsync(srt_device_scene scene, const rtd_light* lights, size_t count, const float ambient[3],
+                                   const float* d_positions, const int* d_ids, size_t elements,
+                                   const rta_generator* gen, const rti_options* options, float* d_rgba, void* stream) {
+    return RadianceAsync(scene, lights, count, ambient, true, d_positions, "d_positions", d_ids, 0, elements, gen,
+                         options, d_rgba, stream);
+}
+
+RTI_API int rtiRadianceHost(const char* scene_path, size_t width, size_t height, const rtd_light_host* lights,
+                            size_t count, const float ambient[3], const float* positions, const int* ids,
+                            size_t elements, const rta_generator* gen, const rti_options* options, float* rgba) {
+    return Guarded([&] {
+        if (scene_path == nullptr) {
+            throw std::runtime_error("Bad argument: scene_path is NULL");
+        }
+        if (width == 0 || height == 0) {
+            throw std::runtime_error("Bad argument: frame dimensions must be non-zero");
+        }
+        srt::DeviceScene::CheckLightCount(count);
+        if (count != 0 && lights == nullptr) {
+            throw std::runtime_error("Bad argument: lights is NULL");
+        }
+        if (ambient == nullptr) {
+            throw std::runtime_error("Bad argument: ambient is NULL");
+        }
+        const srt::VisibilityGen g = CheckedRadianceGenerator(gen);
+        const RadianceOptions o = CheckedRadianceOptions(options);
+        std::vector<srt::HostLight> in;
+        CollectHostLights(lights, count, ambient, in);
+        if (elements > 0x7FFFFFFFull) {
+            throw std::runtime_error("Radiance: at most 2147483647 elements per call, got " + std::to_string(elements));
+        }
+        if (elements == 0) {
+            return;
+        }
+        CheckRadianceBuffers(positions, "positions", ids, "ids", o, rgba, "rgba", false);
+        const srt::Scene scene = srt::LoadScene(scene_path);
+        const srt::RadianceStore store{o.modulate, o.base, {o.weight[0], o.weight[1], o.weight[2]}, rgba};
+        srt::HostRadiance(scene, width, height, in.data(), count, ambient, positions, ids, elements, g, store);
+    });
+}
+
+}  // extern "C"

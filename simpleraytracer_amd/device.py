@@ -581,7 +581,7 @@ class AreaLight(_Generator):
 
 
 class Mirror(_Generator):
-    """The mirror bounce of the primary ray, one ray per element; generate_rays() only."""
+    """The mirror bounce of the primary ray, one ray per element; generate_rays() and radiance() only."""
 
     kind = _native.RTA_MIRROR
 
@@ -628,6 +628,47 @@ def visibility_host(path: str, width: int, height: int, positions, ids, generato
                                            pos.shape[0], ctypes.byref(g), ctypes.byref(out)))
     del keep
     return visible, fraction
+
+
+def _radiance_options(modulate: bool, base_address, weight):
+    """The rti_options of a call and what keeps its blend alive."""
+    blend = _blend(base_address, weight) if base_address is not None else None
+    options = _native.RtiOptions(ctypes.sizeof(_native.RtiOptions), 1 if modulate else 0,
+                                 ctypes.pointer(blend) if blend is not None else None)
+    return options, blend
+
+
+def radiance_host(path: str, width: int, height: int, lights, ambient, positions, ids, generator, modulate: bool = False,
+                  base=None, weight=(1.0, 1.0, 1.0)):
+    """Sampled radiance on the host (rtiRadianceHost: the composition rays_host() -> closest_host()
+    -> light_hits_host() and the sum in ascending sample order, no device): positions (count, 2)
+    float32 and ids (count,) int32 on the file's width x height frame, a Hemisphere or a Mirror of
+    numpy tables, `lights` as lighting_host()'s -> rgba (count, 4) float32: the mean colour of what
+    the generator's S rays hit (the background for a miss), times the element's own albedo with
+    modulate, alpha = the share of rays that hit a surface; zeros off a surface. base (count, 4)
+    float32 with weight (3 floats): rgba = (base.rgb + weight . mean, base's alpha), an element off a
+    surface keeping base's."""
+    import numpy as np
+
+    from . import lighting
+
+    pos, idv = _host_elements(positions, ids)
+    count = pos.shape[0]
+    g, keep = _host_generator(generator)
+    b = None
+    if base is not None:
+        b = np.ascontiguousarray(base, np.float32)
+        if b.shape != (count, 4):
+            raise ValueError(f"base must be {(count, 4)}, got {b.shape}")
+    options, blend = _radiance_options(modulate, b.ctypes.data if b is not None else None, weight)
+    arr, n_lights = lighting.pack_host(lights)
+    rgba = np.empty((count, 4), np.float32)
+    _check(_native.lib().rtiRadianceHost(os.fsencode(path), width, height,
+                                         ctypes.addressof(arr) if arr is not None else None, n_lights,
+                                         lighting.ambient3(ambient), pos.ctypes.data, idv.ctypes.data, count,
+                                         ctypes.byref(g), ctypes.byref(options), rgba.ctypes.data))
+    del keep, blend
+    return rgba
 
 
 class Surface:
@@ -1519,6 +1560,68 @@ class DeviceScene:
         self.light_hits(lights, scratch.rays.view(-1, 8), scratch.ids, scratch.t, flat, ambient=ambient, base=flat,
                         weight=reflectivity, stream=stream)
         return scratch
+
+    def _radiance_call(self, lights, ambient, generator, rgba, lead, modulate, base, weight):
+        from . import lighting
+
+        for name, buf in (("rgba", rgba), ("base", base)):
+            if buf is None:
+                continue
+            if hasattr(buf, "shape") and tuple(buf.shape) != lead + (4,):
+                raise ValueError(f"{name} must be {lead + (4,)}, got {tuple(buf.shape)}")
+            self._check_tensor(name, buf, "f32")
+        g = self._generator(generator)
+        options, blend = _radiance_options(modulate, _ptr(base) if base is not None else None, weight)
+        arr, n_lights = lighting.pack_device(lights)
+        return (ctypes.addressof(arr) if arr is not None else None, n_lights, lighting.ambient3(ambient), g, options,
+                (arr, blend))
+
+    def radiance(self, lights, positions, ids, generator, rgba, ambient=(0.0, 0.0, 0.0), modulate: bool = False,
+                 base=None, weight=(1.0, 1.0, 1.0), stream=None):
+        """Sampled radiance (include/srt_radiance.h) at arbitrary image positions of the prepared
+        frame: one bounce of indirect light. positions (count, 2) float32 and ids (count,) int32 --
+        query()'s input and output --, a Hemisphere (S = 1 ... 64) or a Mirror of device tables, and
+        `lights` as light()'s -> rgba (count, 4) float32: the mean of what light_hits() gives for the
+        closest() hits of the generator's S rays (the background for a miss), in ascending sample
+        order; alpha = the share of rays that hit a surface; zeros off a surface. modulate: times the
+        element's own albedo. base (count, 4) float32 with weight (3 floats): rgba = (base.rgb +
+        weight . mean, base's alpha), an element off a surface keeping base's; base may be rgba
+        itself. One launch whatever len(lights) and S, no scratch: the bits of generate_rays() ->
+        closest() -> light_hits() -> a float32 sum over the samples."""
+        count = self._elements(positions, ids)
+        arr, n_lights, amb, g, options, keep = self._radiance_call(lights, ambient, generator, rgba, (count,), modulate,
+                                                                   base, weight)
+        _check(self._lib.rtiRadiancePointsAsync(self.handle, arr, n_lights, amb, _ptr(positions), _ptr(ids), count,
+                                                ctypes.byref(g), ctypes.byref(options), _ptr(rgba), _stream(stream)))
+        del keep
+
+    def radiance_frame(self, lights, offsets, ids, generator, rgba, ambient=(0.0, 0.0, 0.0), modulate: bool = False,
+                       base=None, weight=(1.0, 1.0, 1.0), row_begin: int = 0, row_count: int | None = None,
+                       stream=None):
+        """radiance() for the prepared frame's rows from hit ids: offsets (rows, W, 2) float32 and ids
+        (rows, W) int32, band-local -> rgba (rows, W, 4) float32; base (rows, W, 4). A Hemisphere's
+        rotations are indexed by the pixel's place in its 4 x 4 block of the whole frame."""
+        if row_count is None:
+            row_count = self.height - row_begin
+        self._check_buffer("offsets", offsets, row_count, 2, "f32")
+        self._check_buffer("ids", ids, row_count, 0, "i32")
+        arr, n_lights, amb, g, options, keep = self._radiance_call(lights, ambient, generator, rgba,
+                                                                   (row_count, self.width), modulate, base, weight)
+        _check(self._lib.rtiRadianceFrameAsync(self.handle, arr, n_lights, amb, _ptr(offsets), _ptr(ids), row_begin,
+                                               row_count, ctypes.byref(g), ctypes.byref(options), _ptr(rgba),
+                                               _stream(stream)))
+        del keep
+
+    def render_indirect(self, lights, offsets, ids, rgba, generator, ambient=(0.0, 0.0, 0.0), weight=(1.0, 1.0, 1.0),
+                        variant: str = "cull", stream=None):
+        """The lit picture of the whole prepared frame with one bounce of indirect light added, on
+        `stream`: trace_ids() into ids ((H, W) int32), light() into rgba ((H, W, 4) float32), then
+        radiance_frame(generator, modulate=True) onto rgba in place with `weight`. Three calls,
+        nothing allocated. A pixel without a surface keeps the lit frame's background."""
+        self.trace_ids(offsets, ids, variant=variant, stream=stream)
+        self.light(lights, offsets, ids, rgba, ambient=ambient, stream=stream)
+        self.radiance_frame(lights, offsets, ids, generator, rgba, ambient=ambient, modulate=True, base=rgba,
+                            weight=weight, stream=stream)
 
     def light_surface(self, lights, offsets, ids, surface, rgba, ambient=(0.0, 0.0, 0.0), material=None, classes=None,
                       row_begin: int = 0, row_count: int | None = None, stream=None):
