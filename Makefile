@@ -22,7 +22,7 @@ OBJS := $(BUILD)/render.o $(BUILD)/spatial.o $(BUILD)/rays.o $(BUILD)/visibility
 HEADERS := $(wildcard $(CSRC)/*.h) include/model_runner.h include/srt_render.h include/srt_query.h include/srt_gbuffer.h \
            include/srt_samples.h include/srt_light.h include/srt_layers.h include/srt_omni.h \
            include/srt_lighting.h include/srt_motion.h include/srt_surface.h include/srt_material.h \
-           include/srt_rays.h include/srt_visibility.h include/srt_hits.h include/srt_radiance.h
+           include/srt_rays.h include/srt_visibility.h include/srt_hits.h include/srt_radiance.h include/srt_pins.h
 
 # Diagnostic build (per-block cull phase counters, srtDiagRead): never the product library.
 DIAG_BUILD := build/diag

@@ -482,6 +482,7 @@ struct FrameEngine::Device {
     std::size_t x_groups = 0;
     std::vector<Queue> queues;
     float* full = nullptr;  // inputs x H x W x 2
+    std::size_t pinned = 0;  // its first `pinned` inputs are pinned on every queue's scene (SetInputs)
     float* band_in = nullptr;  // per role (FrameEngine::Role): inputs x the role's rows x W x 2
     std::size_t row_begin = 0, rows = 0;  // the band MeasureStages traces (kShare: the sender role)
     std::vector<Role> roles;
@@ -1055,7 +1056,7 @@ void FrameEngine::Release() noexcept {
         }
         (void)hipSetDevice(dp->device);
         for (Queue& q : dp->queues) {
-            q.scene.reset();
+            q.scene.reset();  // (with it its pins of this device's inputs, which are freed below)
             (void)hipFree(q.send);
             (void)hipFree(q.recv);
             (void)hipFree(q.rgba);
@@ -1141,12 +1142,33 @@ void FrameEngine::SetInputs(const float* host_offsets, std::size_t count) {
             HipCheck(hipStreamSynchronize(q.stream), "hipStreamSynchronize(inputs)");
             q.used = false;  // frames of the previous inputs are no longer verifiable / readable
         }
+        // The previous inputs' pins go before their memory does: the new allocation often lands at the
+        // old address, and a pin left standing would serve the old contents' facts for it.
+        for (std::size_t r = 0; r < d.pinned; ++r) {
+            for (Queue& q : d.queues) {
+                q.scene->UnpinOffsets(d.full + r * ff);  // (not pinned: nothing)
+            }
+        }
+        d.pinned = 0;
         (void)hipFree(d.full);
         (void)hipFree(d.band_in);
         d.full = d.band_in = nullptr;
         d.full = DeviceAlloc<float>(count * ff, "hipMalloc(inputs)");
         HipCheck(hipMemcpy(d.full, host_offsets, count * ff * sizeof(float), hipMemcpyHostToDevice),
                  "hipMemcpy(inputs)");
+        // Whole frames on the shared setup: the engine owns these buffers and writes them here only,
+        // so every queue's scene keeps their tile facts (DeviceScene::PinOffsets) and the frame loop
+        // runs no facts launch. Inputs beyond a scene's pin count stay unpinned and are classified
+        // per frame; the band inputs of the exchange modes are not whole frames.
+        if (!m_exchange && m_opt.variant == kTraceCull && CullBinnable(m_width, m_height)) {
+            d.pinned = std::min(count, PinTable::kMaxPins);  // (set first: a failure half way unpins them all)
+            for (Queue& q : d.queues) {
+                for (std::size_t r = 0; r < d.pinned; ++r) {
+                    q.scene->PinOffsets(d.full + r * ff, q.stream);
+                }
+                HipCheck(hipStreamSynchronize(q.stream), "hipStreamSynchronize(pinned inputs)");
+            }
+        }
         if (m_exchange && !m_rotate) {  // each role's rows of every input, band-local and contiguous
             const std::size_t row_floats = m_width * 2;
             std::size_t all_rows = 0;

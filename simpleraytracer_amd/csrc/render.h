@@ -265,6 +265,11 @@ struct CullFrame {
     const float* edges;
     const CullBins* bins;
     BandArgs band;
+    // LaunchSharedCullFrames only: the frame's tile facts stand here already (tiles x 16 B, written by
+    // LaunchTileFacts for this offsets buffer and W x H: a pinned buffer, DeviceScene::PinOffsets), so
+    // the facts launch leaves the frame out and its trace reads these. Read-only: any number of
+    // launches may read one such buffer at once. Null: the launch computes the frame's facts.
+    const void* facts = nullptr;
 };
 // Frames of one launch whose parameters travel in a device table instead of the kernel
 // arguments (count > kMaxBatch): `device` and `host` (page-locked) of CullTableBytes(frames) bytes
@@ -375,10 +380,19 @@ hipError_t LaunchCullSetup(const CullSetup& setup, std::uint64_t n, const Frame&
 // `count` whole frames on the setup. frames[f].bins: the frame slot's own state -- tile_info (the
 // frame's 16-B tile facts are written there), arrive, split_keys, and descs == setup.descs; edges
 // unused. Events: bin = the tile-facts launch, begin / end = the trace.
+// Frames with CullFrame::facts set come last in `frames`: the facts launch runs over the frames in
+// front of them only (the kernels take a frame's parameters by blockIdx.z: a smaller grid z), and
+// not at all when every frame has its facts. Such frames are refused with setup.facts_fill on the
+// sweep, whose facts launch stores pixels of every frame.
 hipError_t LaunchSharedCullFrames(const CullFrame* frames, std::size_t count, const CullSetup& setup, std::uint64_t n,
                                   const float* d_vertices, const float* d_shade, const Frame& frame,
                                   const float background[3], hipStream_t stream, const StageEvents* events,
                                   const CullTable* table = nullptr);
+// The facts launch of LaunchSharedCullFrames alone, for one whole frame (band: offsets, width,
+// height = row_count; the outputs unused) into d_facts (CullTiles(width, height) x 16 B): the same
+// kernels on the same parameters, so the same bits. lean: which of the two (CullSetup::lean_facts).
+// A function of the offsets' contents and W x H only: no scene, camera or setup is read.
+hipError_t LaunchTileFacts(const BandArgs& band, void* d_facts, bool lean, hipStream_t stream);
 
 // Point queries (render.hip QueryKernel): the closest hit at `count` arbitrary image positions
 // (fx, fy) of the frame -- the quantity ray generation produces, nothing about pixels: ids[i] = the

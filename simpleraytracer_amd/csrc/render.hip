@@ -6539,16 +6539,26 @@ namespace {
 // TileInfoKernel<.., true>, a 256-thread block per two tiles on the frames' BinParams, which has the
 // whole tile's loads in flight at once and is what a launch reading its offsets from HBM wants
 // (profiles/facts_fill/README.md: the rotating-inputs and single-frame legs decided).
+// fz: the frames the facts launch works on, the first fz of the z frames (the later ones bring their
+// facts: CullFrame::facts); 0: no facts launch.
 template <class TB, class BB>
-void LaunchSharedStages(const TB& tb, const BB& bb, bool lean, unsigned z, unsigned gx, unsigned gy, bool recompute,
-                        bool streamed, unsigned descs, hipStream_t stream, const StageEvents& ev) {
-    // (descs: the trace grid -- the plan's room, or SharedTraceBlocks with the empty sweep)
+void LaunchFactsStage(const TB& tb, const BB& bb, bool lean, unsigned fz, unsigned gx, unsigned gy, hipStream_t stream,
+                      const StageEvents& ev) {
+    if (fz == 0u) {
+        return;
+    }
     if (lean) {
-        Launch(TileFactsKernel<TB>, dim3(gx, gy, z), dim3(kWave), stream, ev.bin_begin, ev.bin_end, tb);
+        Launch(TileFactsKernel<TB>, dim3(gx, gy, fz), dim3(kWave), stream, ev.bin_begin, ev.bin_end, tb);
     } else {
-        Launch(TileInfoKernel<BB, true>, dim3(gx, (gy + kInfoTiles - 1) / kInfoTiles, z), dim3(kBinThreads), stream,
+        Launch(TileInfoKernel<BB, true>, dim3(gx, (gy + kInfoTiles - 1) / kInfoTiles, fz), dim3(kBinThreads), stream,
                ev.bin_begin, ev.bin_end, bb);
     }
+}
+template <class TB, class BB>
+void LaunchSharedStages(const TB& tb, const BB& bb, bool lean, unsigned fz, unsigned z, unsigned gx, unsigned gy,
+                        bool recompute, bool streamed, unsigned descs, hipStream_t stream, const StageEvents& ev) {
+    // (descs: the trace grid -- the plan's room, or SharedTraceBlocks with the empty sweep)
+    LaunchFactsStage(tb, bb, lean, fz, gx, gy, stream, ev);
     if (recompute) {
         Launch(TraceCullKernel<TB, true, true>, dim3(descs, 1, z), dim3(kWave * kCullWaves), stream, ev.begin, ev.end, tb);
     } else if (streamed) {
@@ -6558,7 +6568,42 @@ void LaunchSharedStages(const TB& tb, const BB& bb, bool lean, unsigned z, unsig
         Launch(TraceCullKernel<TB, false, true>, dim3(descs, 1, z), dim3(kWave * kCullWaves), stream, ev.begin, ev.end, tb);
     }
 }
+
+// The block facts kernel's view of the frame of `p`, its facts going to `facts`.
+BinParams FactsBinParams(const TraceParams& p, TileFacts* facts) {
+    BinParams b{};
+    b.offsets = p.offsets;
+    b.tile_facts = facts;
+    b.tiles_x = p.tiles_x;
+    b.tiles_y = static_cast<int>(p.tiles / static_cast<unsigned>(p.tiles_x));
+    b.width = p.width;
+    b.row_count = p.row_count;
+    b.row_begin = p.row_begin;
+    b.row_interleave = p.row_interleave;
+    b.wf = p.wf;
+    b.hf = p.hf;
+    b.exp = p.exp;
+    return b;
+}
 }  // namespace
+
+hipError_t LaunchTileFacts(const BandArgs& band, void* d_facts, bool lean, hipStream_t stream) {
+    if (band.offsets == nullptr || d_facts == nullptr || band.width == 0 || band.height == 0 || band.row_begin != 0 ||
+        band.row_count != band.height || band.row_interleave != 1 || !CullBinnable(band.width, band.row_count)) {
+        return hipErrorInvalidValue;  // whole frames of a shape the shared setup serves
+    }
+    // What the facts kernels read of a frame's parameters is the band alone (its offsets, shape and
+    // row pattern); no record, plan or output pointer, and no fill (facts_fill stays 0).
+    const float none[3] = {0.f, 0.f, 0.f};
+    TraceBatch tb{};
+    BinBatch bb{};
+    tb.f[0] = MakeTraceParams(EdgeLayout{}, 0, nullptr, nullptr, Frame{}, none, band);
+    tb.f[0].tile_facts = static_cast<const TileFacts*>(d_facts);
+    bb.f[0] = FactsBinParams(tb.f[0], static_cast<TileFacts*>(d_facts));
+    const unsigned gx = static_cast<unsigned>(tb.f[0].tiles_x), gy = tb.f[0].tiles / gx;
+    LaunchFactsStage(tb, bb, lean, 1u, gx, gy, stream, StageEvents{});
+    return hipGetLastError();
+}
 
 hipError_t LaunchSharedCullFrames(const CullFrame* frames, std::size_t count, const CullSetup& setup, std::uint64_t n,
                                   const float* d_vertices, const float* d_shade, const Frame& frame,
@@ -6594,6 +6639,7 @@ hipError_t LaunchSharedCullFrames(const CullFrame* frames, std::size_t count, co
     // The facts fill is the lean kernel's; without it the caller's choice (CullSetup::lean_facts).
     const bool lean = setup.lean_facts || (group != 0u && setup.facts_fill);
     const EdgeLayout e = SetupRecords(setup);
+    unsigned fz = 0;  // frames of the facts launch: those in front of the first one with its facts
     for (std::size_t i = 0; i < count; ++i) {
         const CullFrame& f = frames[i];
         if (f.bins == nullptr || f.bins->order == nullptr || f.bins->svertices == nullptr ||
@@ -6622,19 +6668,17 @@ hipError_t LaunchSharedCullFrames(const CullFrame* frames, std::size_t count, co
         p.empty_group = group;
         p.empty_map = setup.empty_map;
         p.facts_fill = group != 0u && setup.facts_fill ? 1u : 0u;  // (ignored with the sweep off)
-        BinParams& b = bp[i];  // (the block facts kernel's view of the frame)
-        b = BinParams{};
-        b.offsets = p.offsets;
-        b.tile_facts = static_cast<TileFacts*>(f.bins->tile_info);
-        b.tiles_x = p.tiles_x;
-        b.tiles_y = static_cast<int>(p.tiles / static_cast<unsigned>(p.tiles_x));
-        b.width = p.width;
-        b.row_count = p.row_count;
-        b.row_begin = p.row_begin;
-        b.row_interleave = p.row_interleave;
-        b.wf = p.wf;
-        b.hf = p.hf;
-        b.exp = p.exp;
+        bp[i] = FactsBinParams(p, static_cast<TileFacts*>(f.bins->tile_info));
+        if (f.facts != nullptr) {  // the frame brings its facts: the facts launch stops in front of it
+            if (p.facts_fill != 0u) {
+                return hipErrorInvalidValue;  // (that facts launch stores the frame's pixels too)
+            }
+            p.tile_facts = static_cast<const TileFacts*>(f.facts);
+        } else if (fz != i) {
+            return hipErrorInvalidValue;  // (the frames with facts come last)
+        } else {
+            ++fz;
+        }
     }
     const unsigned z = static_cast<unsigned>(count);
     const unsigned gx = static_cast<unsigned>(tp[0].tiles_x), gy = tp[0].tiles / gx;
@@ -6646,7 +6690,7 @@ hipError_t LaunchSharedCullFrames(const CullFrame* frames, std::size_t count, co
     blocks = group != 0u ? std::max(setup.list_descs, 1u) : blocks;
 #endif
     if (!use_table) {
-        LaunchSharedStages(tb, bb, lean, z, gx, gy, setup.recompute, streamed, blocks, stream, ev);
+        LaunchSharedStages(tb, bb, lean, fz, z, gx, gy, setup.recompute, streamed, blocks, stream, ev);
         return hipGetLastError();
     }
     if (table->host_device != nullptr) {
@@ -6668,7 +6712,7 @@ hipError_t LaunchSharedCullFrames(const CullFrame* frames, std::size_t count, co
     unsigned char* dev = static_cast<unsigned char*>(table->device);
     const BinTable bt{(ConstantPtr<BinParams>)(dev + lay.bin)};
     const TraceTable tt{(ConstantPtr<TraceParams>)(dev + lay.trace)};
-    LaunchSharedStages(tt, bt, lean, z, gx, gy, setup.recompute, streamed, blocks, stream, ev);
+    LaunchSharedStages(tt, bt, lean, fz, z, gx, gy, setup.recompute, streamed, blocks, stream, ev);
     return hipGetLastError();
 }
 

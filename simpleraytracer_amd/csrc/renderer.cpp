@@ -183,6 +183,10 @@ DeviceScene::~DeviceScene() {
     (void)hipFree(m_block_ext);
     (void)hipFree(m_setup);
     (void)hipFree(m_stream);
+    m_pins.Clear();
+    for (void* facts : m_pins.TakeRetired()) {
+        (void)hipFree(facts);
+    }
     for (CullArena& a : m_arenas) {
         (void)hipFree(a.work);
     }
@@ -217,6 +221,10 @@ void DeviceScene::Prepare(std::size_t width, std::size_t height, hipStream_t str
     }
     if (width != m_width || height != m_height) {
         DropPlans(~std::size_t{0});  // (a plan is scheduling only; a new shape deserves a new one)
+        if (!m_pins.empty()) {  // pinned facts are of the old tile grid: the caller pins again if it wants
+            m_pins.Clear();
+            ReleaseRetiredPins();
+        }
     }
     const Frame frame = MakeFrame(m_camera, width, height);
     if (width != m_width || height != m_height || std::memcmp(&frame, &m_frame, sizeof(Frame)) != 0) {
@@ -1043,6 +1051,18 @@ int FactsKernelFromEnv() {
     return v == "auto" ? -1 : v == "lean" ? 1 : 0;
 }
 
+// SRT_FACTS_PINS = 1 (default) | 0, read per call: whether a whole-frame trace on the shared setup
+// reads the stored facts of its pinned offsets buffers (DeviceScene::PinOffsets); 0: it computes
+// every frame's facts as if nothing were pinned -- the same frames, the A/B leg of a measurement.
+bool FactsPinsFromEnv() {
+    const char* e = std::getenv("SRT_FACTS_PINS");
+    const std::string v = e == nullptr || *e == '\0' ? "1" : e;
+    if (v != "1" && v != "0") {
+        throw std::runtime_error("SRT_FACTS_PINS must be 1 or 0, got '" + v + "'");
+    }
+    return v == "1";
+}
+
 // SRT_TRACE_STREAM_CAP (tests only): the longest record stream, in records, instead of
 // kStreamCapRecords -- forces the indexed fallback at small sizes, as SRT_CULL_BIN_CAP forces list overflow.
 std::size_t StreamCapFromEnv() {
@@ -1102,43 +1122,72 @@ void DeviceScene::LogSetupStats() const {
     std::fprintf(stderr,
                  "srt setup: scene %p builds %llu shared_frames %llu per_frame_frames %llu stream_frames %llu "
                  "stream_records %llu empty_descs %llu sweep_blocks %llu facts_fill_frames %llu "
-                 "lean_facts_frames %llu\n",
+                 "lean_facts_frames %llu pinned_frames %llu facts_launches %llu\n",
                  static_cast<const void*>(this), m_setup_stats.builds, m_setup_stats.shared_frames,
                  m_setup_stats.per_frame_frames, m_setup_stats.stream_frames, m_setup_stats.stream_records,
                  m_setup_stats.empty_descs, m_setup_stats.sweep_blocks, m_setup_stats.facts_fill_frames,
-                 m_setup_stats.lean_facts_frames);
+                 m_setup_stats.lean_facts_frames, m_setup_stats.pinned_frames, m_setup_stats.facts_launches);
     std::fflush(stderr);
 }
 
 void DeviceScene::TraceShared(const float* const* d_offsets, float* const* d_rgba, int* const* d_ids,
                               std::size_t frames, hipStream_t stream, int id_planes, bool rgba_frame_rows,
                               std::size_t plan_frames) const {
+    // An explicit SRT_FACTS_KERNEL=lean|block asks for that facts kernel in the launch (the switch of
+    // the facts kernels' own measurements and tests), so such a call computes its facts too.
+    const int want = FactsKernelFromEnv();
+    const bool use_pins = FactsPinsFromEnv() && want < 0 && !m_pins.empty();  // (junk is an error, pins or none)
     OrderAfterPrevious(stream);
     // The frame slots' own state (tile facts, split key slices, arrival counters) lives in the cull
     // work of the whole-frame shape; no edge slots: the records are the setup's.
     EnsureCullWork(frames, m_height, stream);
     const CullArena& a = m_arenas.at(m_arena);
     const std::size_t tiles = CullTiles(m_width, m_height);
+    const unsigned descs = std::min(CullBinLayout(a.work, m_n, m_width, m_height).descs, CullDescriptors(tiles, plan_frames));
+    CullSetup setup = EnsureSetup(descs, stream);
+    // The launch's order: the frames that need their facts computed first, those whose offsets are
+    // pinned after them, so the facts launch is the first `unpinned` frames of the grid (render.h
+    // LaunchSharedCullFrames). A frame's parameters are self-contained: its place in the launch is
+    // not part of its result. SRT_EMPTY_FILL=facts on the sweep: that facts launch stores pixels,
+    // so it runs for every frame and no pin is used.
+    std::vector<const void*> facts(frames, nullptr);
+    std::vector<std::size_t> at(frames);  // launch position -> the caller's frame
+    std::size_t unpinned = 0;
+    if (use_pins && !(setup.sweep && setup.facts_fill)) {
+        for (std::size_t f = 0; f < frames; ++f) {
+            facts[f] = m_pins.Find(d_offsets[f]);
+        }
+    }
+    for (std::size_t f = 0; f < frames; ++f) {
+        if (facts[f] == nullptr) {
+            at[unpinned++] = f;
+        }
+    }
+    for (std::size_t f = 0, k = unpinned; f < frames; ++f) {
+        if (facts[f] != nullptr) {
+            at[k++] = f;
+        }
+    }
     std::vector<CullBins> bins(frames);
     std::vector<CullFrame> cf(frames);
-    for (std::size_t f = 0; f < frames; ++f) {
+    for (std::size_t k = 0; k < frames; ++k) {
+        const std::size_t f = at[k];
         // (not CullSlot: the slot's count parity and its per-frame plan stay as the per-frame path left them)
-        bins[f] = CullBinLayout(a.work + f * a.layout, m_n, m_width, m_height);
-        bins[f].descs = std::min(bins[f].descs, CullDescriptors(tiles, plan_frames));
-        bins[f].order = m_order;
-        bins[f].svertices = m_svertices;
-        cf[f].edges = nullptr;
-        cf[f].bins = &bins[f];
-        cf[f].band = BandArgs{d_offsets[f], d_rgba != nullptr ? d_rgba[f] : nullptr, m_width, m_height, 0, m_height,
+        bins[k] = CullBinLayout(a.work + k * a.layout, m_n, m_width, m_height);
+        bins[k].descs = descs;
+        bins[k].order = m_order;
+        bins[k].svertices = m_svertices;
+        cf[k].edges = nullptr;
+        cf[k].bins = &bins[k];
+        cf[k].band = BandArgs{d_offsets[f], d_rgba != nullptr ? d_rgba[f] : nullptr, m_width, m_height, 0, m_height,
                               d_ids != nullptr ? d_ids[f] : nullptr, 1, id_planes, rgba_frame_rows};
+        cf[k].facts = facts[f];
     }
-    CullSetup setup = EnsureSetup(bins[0].descs, stream);
     {
-        const int want = FactsKernelFromEnv();
-        bool reused = false;  // some frames of the launch read the same offsets buffer
-        for (std::size_t f = 1; f < frames && !reused; ++f) {
-            for (std::size_t g = 0; g < f && !reused; ++g) {
-                reused = d_offsets[f] == d_offsets[g];
+        bool reused = false;  // some frames of the facts launch read the same offsets buffer
+        for (std::size_t k = 1; k < unpinned && !reused; ++k) {
+            for (std::size_t g = 0; g < k && !reused; ++g) {
+                reused = cf[k].band.offsets == cf[g].band.offsets;
             }
         }
         setup.lean_facts = want < 0 ? reused : want == 1;
@@ -1147,7 +1196,8 @@ void DeviceScene::TraceShared(const float* const* d_offsets, float* const* d_rgb
     m_setup_stats.sweep_blocks =
         setup.sweep ? SharedTraceBlocks(setup.descs, setup.list_descs, setup.empty_descs, setup.empty_group) - setup.list_descs
                     : 0;
-    const StageEvents ev = BindStageEvents(false, true);
+    // (no facts launch: no bin events, and TakeTimes reports a bin stage of 0 for the call)
+    const StageEvents ev = BindStageEvents(false, unpinned != 0);
     ParamTable* table = frames > static_cast<std::size_t>(kMaxBatch) ? &AcquireTable(frames, stream) : nullptr;
     const CullTable ct{table != nullptr ? table->device : nullptr, table != nullptr ? table->host : nullptr,
                        table != nullptr ? table->frames : 0, table != nullptr ? table->host_device : nullptr,
@@ -1161,9 +1211,84 @@ void DeviceScene::TraceShared(const float* const* d_offsets, float* const* d_rgb
     m_setup_stats.shared_frames += frames;
     m_setup_stats.stream_frames += setup.stream != nullptr ? frames : 0;
     m_setup_stats.facts_fill_frames += setup.sweep && setup.facts_fill ? frames : 0;
-    m_setup_stats.lean_facts_frames += setup.lean_facts || (setup.sweep && setup.facts_fill) ? frames : 0;
+    m_setup_stats.lean_facts_frames += setup.lean_facts || (setup.sweep && setup.facts_fill) ? unpinned : 0;
+    m_setup_stats.pinned_frames += frames - unpinned;
+    m_setup_stats.facts_launches += unpinned != 0 ? 1 : 0;
     LogSetupStats();
     RecordOrder(stream);
+}
+
+// Pinned offsets (renderer.h): the facts kernel once, for one frame, into the pin's own buffer.
+void DeviceScene::PinOffsets(const float* d_offsets, hipStream_t stream) {
+    if (d_offsets == nullptr) {
+        throw std::runtime_error("PinOffsets: null offsets pointer");
+    }
+    if (m_width == 0) {
+        throw std::runtime_error("PinOffsets: Prepare() has not been called");
+    }
+    if (!CullBinnable(m_width, m_height)) {
+        throw std::runtime_error("PinOffsets: no tile facts for a frame of this size (its traces are not binned)");
+    }
+    // A launch of one frame brings its own buffer: the block kernel, unless the env names one.
+    const int want = FactsKernelFromEnv();
+    void* facts = m_pins.Find(d_offsets);
+    const bool fresh = facts == nullptr;
+    if (fresh) {
+        if (m_pins.full()) {
+            throw std::runtime_error("PinOffsets: at most " + std::to_string(PinTable::kMaxPins) +
+                                     " pinned buffers per scene (unpin one first)");
+        }
+        facts = DeviceAlloc<unsigned char>(CullTiles(m_width, m_height) * 16, "hipMalloc(pinned facts)");
+    }
+    OrderAfterPrevious(stream);  // (a pin again: earlier traces read the buffer this launch rewrites)
+    const BandArgs band{d_offsets, nullptr, m_width, m_height, 0, m_height};
+    const hipError_t launched = LaunchTileFacts(band, facts, want == 1, stream);
+    RecordOrder(stream);
+    if (launched != hipSuccess) {
+        // Facts that were not computed must not be read: the pin is gone (a fresh buffer was never
+        // visible to any launch; a standing one may be read by queued traces: retired, released later).
+        if (fresh) {
+            (void)hipFree(facts);
+        } else {
+            m_pins.Remove(d_offsets);
+        }
+    } else if (fresh) {
+        m_pins.Insert(d_offsets, facts);
+    }
+    HipCheck(launched, "pinned facts launch");
+    ++m_setup_stats.facts_launches;
+    LogSetupStats();
+}
+
+void DeviceScene::UnpinOffsets(const float* d_offsets) {
+    m_pins.Remove(d_offsets);
+    ReleaseRetiredPins();
+}
+
+std::size_t DeviceScene::pinned() const { return m_pins.size(); }
+
+// Calls on one scene form one chain (OrderAfterPrevious), so the newest order event stands for all
+// of the scene's work so far.
+void DeviceScene::WaitForPrevious() const {
+    if (!m_used) {
+        return;
+    }
+#if SRT_ORDER_EVENTS == 0
+    HipCheck(hipEventRecord(m_order_events[0], m_last_stream), "hipEventRecord(scene order)");
+    HipCheck(hipEventSynchronize(m_order_events[0]), "hipEventSynchronize(scene order)");
+#else
+    HipCheck(hipEventSynchronize(m_order_events[m_order_next]), "hipEventSynchronize(scene order)");
+#endif
+}
+
+void DeviceScene::ReleaseRetiredPins() {
+    if (m_pins.retired() == 0) {
+        return;
+    }
+    WaitForPrevious();  // (throws: the buffers stay retired, and are freed with the scene at the latest)
+    for (void* facts : m_pins.TakeRetired()) {
+        (void)hipFree(facts);
+    }
 }
 
 // The shared setup of the prepared frame for a trace grid of `descs` descriptors: (re)allocated,

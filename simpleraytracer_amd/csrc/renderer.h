@@ -13,6 +13,7 @@
 #include <string>
 #include <vector>
 
+#include "pin_table.h"
 #include "scene.h"
 
 namespace srt {
@@ -111,6 +112,26 @@ public:
     // band shape, for every frame; cull variant, bands short of the whole frame.
     // plan_frames > frames: on the shared setup the trace grid is the one of a plan_frames-frame
     // call, so the chunks of a longer frame set -- RenderSamples' -- share one setup build.)
+
+    // Pinned offsets (include/srt_pins.h rtnPinOffsetsAsync). The tile facts of a whole-frame offsets
+    // buffer -- per tile its first offset and whether its offsets are all equal, usable and in range
+    // -- are a function of the buffer's contents and of W x H alone, and a caller that keeps a sample
+    // pattern for many frames says so here: PinOffsets computes them once, on `stream`, with the
+    // facts kernel of the traces themselves (render.h LaunchTileFacts; the same bits) into a buffer
+    // the scene owns, keyed by the pointer. TraceShared then gives a frame with that pointer the
+    // stored facts, and a launch whose frames are all pinned runs no facts launch. The scene cannot
+    // see a buffer change: while pinned, the caller does not write it, and unpins it before freeing
+    // it; pinning it again recomputes the facts (new contents). At most PinTable::kMaxPins, one more
+    // is an error. A call on the scene for the ordering rule; needs a prepared scene. Prepare at the
+    // same size, SetCamera and SetVertices keep the pins; Prepare at another size drops them all.
+    // Bands, SRT_SETUP=frame, the other variants, SRT_EMPTY_FILL=facts and an explicit
+    // SRT_FACTS_KERNEL=lean|block (which asks for that facts kernel in the launch) compute their own
+    // facts whatever is pinned; env SRT_FACTS_PINS=0 (read per call; default 1) makes every trace do so.
+    void PinOffsets(const float* d_offsets, hipStream_t stream);
+    // Forgets the pin of d_offsets (not pinned: nothing). Waits for the scene's previous work, which
+    // may read the facts, before it frees them.
+    void UnpinOffsets(const float* d_offsets);
+    std::size_t pinned() const;
 
     // Point queries: the closest hit at `count` image positions (fx, fy) of the prepared frame
     // (d_positions: count x 2) into d_ids (-1 = miss), d_t (+inf = miss) and, non-null, d_how
@@ -288,7 +309,8 @@ public:
         unsigned launches = 0;     // timed Trace calls
         double prepare_ms = 0.0;   // PrepareKernel (mean over timed Prepare calls)
         double bin_ms = 0.0;       // bin stage (cull: BinTriangles start .. WorkOrder end; on the shared setup
-                                   // the per-frame tile-facts launch, the one-off build uncounted); 0 otherwise
+                                   // the per-frame tile-facts launch, the one-off build uncounted, and a launch
+                                   // of pinned frames, which has none, not counted as a stage); 0 otherwise
         double kernel_ms = 0.0;    // the trace kernel alone
     };
     void SetTiming(bool on);
@@ -316,6 +338,10 @@ public:
         // Of shared_frames, those whose facts launch was the lean kernel (env SRT_FACTS_KERNEL; auto:
         // launches in which frames share an offsets buffer).
         unsigned long long lean_facts_frames = 0;
+        // Of shared_frames, those whose trace read the stored facts of a pinned offsets buffer, and
+        // the facts launches issued: one per shared launch with an unpinned frame, one per PinOffsets.
+        unsigned long long pinned_frames = 0;
+        unsigned long long facts_launches = 0;
     };
     SetupStats setup_stats() const { return m_setup_stats; }
 
@@ -378,6 +404,11 @@ private:
     mutable SetupKey m_setup_key{};
     mutable SetupStats m_setup_stats{};
     void LogSetupStats() const;
+    // Pinned offsets: pointer -> facts buffer (CullTiles(W, H) x 16 B each, hipMalloc'ed here). A
+    // removed pin's buffer is freed by ReleaseRetiredPins, after the scene's previous work.
+    PinTable m_pins;
+    void WaitForPrevious() const;  // the host waits for the scene's last call
+    void ReleaseRetiredPins();
     // Whether a binned cull trace of this band runs on the shared setup (env SRT_SETUP).
     bool OnSharedSetup(std::size_t row_begin, std::size_t row_count, std::size_t row_interleave) const;
     // Whole frames on the shared setup: the setup (re)built if need be, then tile facts + trace.

@@ -30,6 +30,7 @@
 #include "srt_motion.h"
 #include "srt_omni.h"
 #include "srt_query.h"
+#include "srt_pins.h"
 #include "srt_radiance.h"
 #include "srt_rays.h"
 #include "srt_render.h"
@@ -2503,3 +2504,34 @@ RTI_API int rtiRadianceHost(const char* scene_path, size_t width, size_t height,
 }
 
 }  // extern "C"
+
+// Pinned offsets (include/srt_pins.h): the rtn family.
+static_assert(RTN_MAX_PINS == srt::PinTable::kMaxPins, "include/srt_pins.h RTN_MAX_PINS");
+
+RTN_API int rtnPinOffsetsAsync(srt_device_scene scene, const float* d_offsets, void* stream) {
+    return Guarded([&] {
+        if (scene == nullptr) {
+            throw std::runtime_error("Bad scene handle");
+        }
+        if (d_offsets == nullptr) {
+            throw std::runtime_error("Bad buffer argument");
+        }
+        srt::DeviceScene* s = FromHandle(scene);
+        Bind bind(s->device());
+        s->PinOffsets(d_offsets, static_cast<hipStream_t>(stream));
+    });
+}
+
+RTN_API int rtnUnpinOffsets(srt_device_scene scene, const float* d_offsets) {
+    return Guarded([&] {
+        if (scene == nullptr) {
+            throw std::runtime_error("Bad scene handle");
+        }
+        if (d_offsets == nullptr) {
+            throw std::runtime_error("Bad buffer argument");
+        }
+        srt::DeviceScene* s = FromHandle(scene);
+        Bind bind(s->device());
+        s->UnpinOffsets(d_offsets);
+    });
+}

@@ -40,6 +40,7 @@ from ._native import (RTK_MAX_LAYERS, RTM_KEEP_ORDER, RTM_REORDER, RTS_MAX_SAMPL
 SCENE_KINDS = {"triangle": SRT_SCENE_TRIANGLE, "cornell": SRT_SCENE_CORNELL, "soup": SRT_SCENE_SOUP}
 TRACE_VARIANTS = {"lds": SRT_TRACE_LDS, "scalar": SRT_TRACE_SCALAR, "cull": SRT_TRACE_CULL, "bvh": SRT_TRACE_BVH}
 MAX_BATCH = SRT_MAX_BATCH
+MAX_PINS = 64  # include/srt_pins.h RTN_MAX_PINS: pinned offsets buffers per device scene
 SOUP_SEED = 0x5EED  # 100k soup seed; the 1M soup uses SOUP_SEED + 1
 
 
@@ -983,6 +984,21 @@ class DeviceScene:
                     stream=None, ids: bool = False, row_interleave: int = 1):
         """One batched call (bind_trace_batch) run once."""
         self.bind_trace_batch(offsets, outs, row_begin, row_count, variant, stream, ids, row_interleave)()
+
+    def pin_offsets(self, offsets, stream=None):
+        """Pins a whole-frame offsets buffer ((H, W, 2) float32 on this device; rtnPinOffsetsAsync):
+        its tile classification is computed once and every later whole-frame cull trace given this
+        buffer skips that pass. While pinned the buffer is neither written nor freed; pinning it
+        again announces new contents. At most MAX_PINS per scene; preparing at another size drops
+        every pin."""
+        if self.width:  # (an unprepared scene has no frame shape to check against: the library refuses it)
+            self._check_buffer("offsets", offsets, self.height, 2, "f32")
+        _check(self._lib.rtnPinOffsetsAsync(self.handle, _ptr(offsets), _stream(stream)))
+
+    def unpin_offsets(self, offsets):
+        """Forgets the pin of `offsets` (rtnUnpinOffsets; not pinned: nothing). Waits for the scene's
+        enqueued work first."""
+        _check(self._lib.rtnUnpinOffsets(self.handle, _ptr(offsets)))
 
     def shade(self, offsets, ids, rgba, row_begin: int = 0, row_count: int | None = None, stream=None):
         """Deferred shading of the prepared frame's rows from hit ids: the RGBA trace() stores."""
