@@ -30,6 +30,13 @@
  * explicit SRT_FACTS_KERNEL=lean|block (which asks for that classification kernel in the launch). Env
  * SRT_FACTS_PINS=0 (read per call; default 1; anything else is an error) makes every trace ignore
  * them: the same frames, for measurements.
+ *
+ * A pin also learns, behind the same launch and still without blocking, whether every tile of the
+ * buffer has one offset, usable and in [0, 1] -- a pixel-centre or per-tile sample pattern. A call
+ * whose RGBA frames are all pinned so, and whose pins' summaries have arrived (the work queued by
+ * rtnPinOffsetsAsync has completed), traces with a kernel that keeps no per-pixel position table and
+ * fits one more block per compute unit; any other call traces as before. The same bits either way.
+ * Env SRT_TRACE_POS=table (read per call; default auto; anything else is an error) never does so.
  */
 #ifndef SRT_PINS_H
 #define SRT_PINS_H

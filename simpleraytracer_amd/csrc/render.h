@@ -322,7 +322,8 @@ struct CullSetup {
     void* work_tmp;        // descs descriptors of scratch (LaunchStreamPlan's partition)
     unsigned* work_count;
     // [0]: records of the record stream (LaunchStreamPlan), pad records included; [1]: the plan's
-    // descriptors that are not statically empty (low word) and those that are (high word)
+    // descriptors that are not statically empty (low word) and those that are (high word); [2]:
+    // non-zero when some descriptor is statically empty and FULL at once (full_empty_descs below)
     unsigned long long* stream_count;
     // The record stream (below): an allocation of its own, sized from stream_count after the plan;
     // null: the traces read the records through the lists (the indexed path).
@@ -349,6 +350,15 @@ struct CullSetup {
     // Which of the two facts kernels a launch runs (read per launch; render.hip LaunchSharedStages):
     // the lean one-wave-per-tile kernel, or the block kernel. facts_fill implies the lean one.
     bool lean_facts;
+    // A regular launch (read per launch; render.hip TraceCullKernel<RegularFrames<..>, ..>): the trace runs the kernel
+    // without the per-pixel position table, at seven blocks per CU. The caller vouches that every
+    // tile of every frame is regular, usable and in range -- every frame brings its facts
+    // (CullFrame::facts) and their summary says so (LaunchFactsSummary) --, for a tile that is not
+    // would be traced wrongly; a launch with a facts stage is refused. full_empty_descs (the built
+    // plan's, stream_count[2]): non-zero when a sweep block could have a descriptor to trace whatever
+    // the facts say, which that kernel does not do: such a setup's regular launch is refused too.
+    bool regular_trace = false;
+    unsigned full_empty_descs = 0;
 };
 // The empty sweep: with setup.sweep the trace grid is the list descriptors, one block each, and one
 // sweep block per empty_group statically empty descriptors (render.hip TraceCullKernel), instead of
@@ -393,6 +403,13 @@ hipError_t LaunchSharedCullFrames(const CullFrame* frames, std::size_t count, co
 // kernels on the same parameters, so the same bits. lean: which of the two (CullSetup::lean_facts).
 // A function of the offsets' contents and W x H only: no scene, camera or setup is read.
 hipError_t LaunchTileFacts(const BandArgs& band, void* d_facts, bool lean, hipStream_t stream);
+// The summary of such a facts buffer, after its facts launch on the same stream: one small block ANDs
+// regular, usable and in-range over the `tiles` tiles and stores one word, kFactsSummaryDone with
+// kFactsSummaryRegular when every tile has all three. d_word: the device's address of a word the
+// host can read (page-locked, mapped), valid once the work queued behind this launch has completed.
+constexpr unsigned kFactsSummaryDone = 0x80000000u;
+constexpr unsigned kFactsSummaryRegular = 1u;
+hipError_t LaunchFactsSummary(const void* d_facts, std::size_t tiles, unsigned* d_word, hipStream_t stream);
 
 // Point queries (render.hip QueryKernel): the closest hit at `count` arbitrary image positions
 // (fx, fy) of the frame -- the quantity ray generation produces, nothing about pixels: ids[i] = the

@@ -1753,7 +1753,12 @@ static_assert(kWindowPackets == 2 * kWave, "window prefix: two packets per lane"
 // Batch entry of thread tid's slice e (kPacketBatch < kCullThreads: the first threads only).
 __device__ __forceinline__ bool InBatch(int e, int tid) { return e * kCullThreads + tid < kPacketBatch; }
 
-struct CullShared {
+// POS = false (a regular launch: TraceCullKernel<RegularFrames<..>, ..>): no position table. In a regular tile the
+// position of pixel (c, r) is (clo[c], rlo[r]) bit for bit (PacketTables), so the table's 8 KB --
+// a zero-length array here, which takes no room -- buy a seventh block per CU.
+template <bool POS>
+struct CullSharedT {
+    static constexpr bool kPos = POS;
     union {
         struct {
             float4 sv0[kPacketBatch];  // compacted survivors: plane 0 (sv0, sv1 adjacent: PacketTables scratch)
@@ -1768,7 +1773,7 @@ struct CullShared {
     unsigned wave_n[kSlices * kCullWaves];   // survivors per (slice, wave)
     unsigned wave_pk[kSlices * kCullWaves];  // pixels per (slice, wave)
     uint2 pk[2][kWindowPackets];  // window packet k: last-pixel bits (lo, hi); two buffers, alternate batches
-    float2 fxy[kBlockRows][kWave];  // ray position (fx, fy) of every pixel of the block (512-B rows:
+    float2 fxy[POS ? kBlockRows : 0][kWave];  // ray position (fx, fy) of every pixel of the block (512-B rows:
                                     // rows padded by 8 or 16 B to skew the banks measured 3-6 % slower)
     float clo[kWave], chi[kWave];    // monotone column bounds of fx (suffix min, prefix max)
     float rlo[kBlockRows], rhi[kBlockRows];  // monotone row bounds of fy
@@ -1778,6 +1783,8 @@ struct CullShared {
     unsigned todo_hi;  // a sweep block: high word (the 4 B in front of the 8-B aligned keys: no LDS added)
     unsigned long long keys[kBlockRows][kWave];  // per-pixel lexicographic (t, id) keys
 };
+using CullShared = CullSharedT<true>;
+static_assert(sizeof(CullSharedT<false>) + sizeof(float2) * kBlockRows * kWave == sizeof(CullShared), "only the table goes");
 static_assert(sizeof(float2) * kWave * kCullWaves <= sizeof(float4) * 2 * kPacketBatch, "PacketTables scratch");
 static_assert((kPacketBatch + kStreamStep) * 4 <= sizeof(float4) * 3 * kPacketBatch, "stream ids alias the planes");
 constexpr int kFlushBatches = (kPacketBatch + kStreamStep - 1 + kPacketBatch - 1) / kPacketBatch;  // per flush
@@ -1904,17 +1911,20 @@ __device__ __forceinline__ float WaveMax(float v) {
 // The block's position tables (see the section comment) from the lane's rays. `regular`:
 // every ray of the block has the same sample offset, so fx_lane (column `lane`) and fy_lane
 // (row `lane` < kBlockRows) already are the monotone tables. Ends with a barrier.
-__device__ __forceinline__ void PacketTables(CullShared& sh, const Rays<kCullR>& s, bool regular, float fx_lane,
+template <class SH>
+__device__ __forceinline__ void PacketTables(SH& sh, const Rays<kCullR>& s, bool regular, float fx_lane,
                                              float fy_lane, int nc, int nr) {
     constexpr int R = kCullR;
     const int tid = threadIdx.x;
     const int lane = tid & (kWave - 1);
     const int wave = __builtin_amdgcn_readfirstlane(tid / kWave);
+    if constexpr (SH::kPos) {
 #pragma unroll
-    for (int r = 0; r < R; ++r) {
-        sh.fxy[wave * R + r][lane] = make_float2(s.fx[r], s.fy[r]);
+        for (int r = 0; r < R; ++r) {
+            sh.fxy[wave * R + r][lane] = make_float2(s.fx[r], s.fy[r]);
+        }
     }
-    if (regular) {
+    if (!SH::kPos || regular) {  // (no table: every tile of the launch is regular, the host saw to it)
         if (tid < kWave) {
             sh.clo[tid] = fx_lane;
             sh.chi[tid] = fx_lane;
@@ -1926,6 +1936,7 @@ __device__ __forceinline__ void PacketTables(CullShared& sh, const Rays<kCullR>&
         __syncthreads();
         return;
     }
+    if constexpr (SH::kPos) {
     // Per column: min / max of fx over this wave's rows (scratch in the survivor planes, which
     // the first batch writes only after later barriers); per row: over the valid columns.
     float2* part = reinterpret_cast<float2*>(sh.sv0);
@@ -1964,6 +1975,7 @@ __device__ __forceinline__ void PacketTables(CullShared& sh, const Rays<kCullR>&
         }
     }
     __syncthreads();
+    }
 }
 
 // Per-block constants of the packet walk: valid columns / rows and the linear models of the
@@ -1973,7 +1985,8 @@ struct PacketFrame {
     bool use_sb;
     float fx_first, fx_scale, fy_first, fy_scale;
 };
-__device__ __forceinline__ PacketFrame MakePacketFrame(const CullShared& sh, int nc, int nr, bool use_sb) {
+template <class SH>
+__device__ __forceinline__ PacketFrame MakePacketFrame(const SH& sh, int nc, int nr, bool use_sb) {
     PacketFrame f;
     f.nc = nc;
     f.nr = nr;
@@ -1993,8 +2006,8 @@ __device__ __forceinline__ PacketFrame MakePacketFrame(const CullShared& sh, int
 // batch's first barrier separates this walk from its plane writes, the range-end bitmap
 // alternates between two buffers (`buf` = batch parity; this batch clears the other one), and
 // the caller puts a barrier between the last batch and its reads of sh.keys.
-template <class F>
-__device__ __forceinline__ void PacketBatch(CullShared& sh, const Box& bb, const PacketFrame& pf,
+template <class SH, class F>
+__device__ __forceinline__ void PacketBatch(SH& sh, const Box& bb, const PacketFrame& pf,
                                             const CullRecord (&cr)[kSlices], const bool (&valid)[kSlices],
                                             unsigned buf, F&& prefetch) {
     constexpr int W = kCullWaves;
@@ -2105,7 +2118,7 @@ __device__ __forceinline__ void PacketBatch(CullShared& sh, const Box& bb, const
     // range. The waves split each window's packets evenly, kPacketIlp at a time (independent
     // chains; a tail repeats the last packet, harmless under the atomic min).
     constexpr int kPacketIlp = SRT_PACKET_ILP;
-    const char* fxy = reinterpret_cast<const char*>(&sh.fxy[0][0]);
+    [[maybe_unused]] const char* fxy = reinterpret_cast<const char*>(sh.fxy);
     char* keys = reinterpret_cast<char*>(&sh.keys[0][0]);
     const unsigned last_slot = n_surv == 0u ? 0u : n_surv - 1u;
     unsigned ended = 0u;  // ranges that end before the window (block-uniform)
@@ -2193,7 +2206,11 @@ __device__ __forceinline__ void PacketBatch(CullShared& sh, const Box& bb, const
             for (int u = 0; u < kPacketIlp; ++u) {
 #pragma unroll
                 for (int j = 0; j < kLanePixels; ++j) {
-                    f[u][j] = *reinterpret_cast<const float2*>(fxy + px[u][j].pixb);
+                    if constexpr (SH::kPos) {
+                        f[u][j] = *reinterpret_cast<const float2*>(fxy + px[u][j].pixb);
+                    } else {  // pixb = row << 9 | col << 3: the pixel's column and row tables' entries
+                        f[u][j] = make_float2(sh.clo[(px[u][j].pixb >> 3) & (kWave - 1u)], sh.rlo[px[u][j].pixb >> 9]);
+                    }
                 }
             }
 #pragma unroll
@@ -3430,13 +3447,31 @@ __global__ __launch_bounds__(kWave) void TileFactsKernel(const Frames batch) {
 }
 static_assert(sizeof(FrameArgs<TraceParams>) < 4096, "kMaxBatch frames' TraceParams as kernel arguments: under 4 KB");
 
+// A regular launch (render.h CullSetup::regular_trace; DESIGN.md section 5 "Regular launches"): the
+// host knows every tile of every frame to be regular, usable and in range, and says so in the type of
+// the frames. The kernel is then compiled without the position table (POS = false: CullSharedT,
+// `regular` a constant) and without the sweep blocks' second copy of the body (TODO = false: under
+// such facts no sweep block has a descriptor to trace), at seven blocks per CU where the general
+// kernel has six: 72 VGPRs and 18.2 KB of LDS. The general instantiations keep their names and text.
+template <class F>
+struct RegularFrames : F {};
+template <class F>
+struct IsRegularFrames : std::false_type {};
+template <class F>
+struct IsRegularFrames<RegularFrames<F>> : std::true_type {};
+constexpr int kRegularOcc = 7;
+template <class F>
+constexpr int kTraceOcc = IsRegularFrames<F>::value ? kRegularOcc : SRT_TRACE_OCC;
+
 template <class Frames, bool RC = false, bool SHARED = false, bool STREAM = false>
-__global__ __launch_bounds__(kCullThreads, SRT_TRACE_OCC) void TraceCullKernel(const Frames batch) {
+__global__ __launch_bounds__(kCullThreads, kTraceOcc<Frames>) void TraceCullKernel(const Frames batch) {
     static_assert(!STREAM || (SHARED && !RC), "the record stream: stored records of the shared setup");
+    constexpr bool POS = !IsRegularFrames<Frames>::value, TODO = POS;
+    static_assert(POS || SHARED, "no position table: pinned frames of the shared setup");
     const TraceParams& p = batch[blockIdx.z];
     using Recs = TraceRecords<RC>;
     constexpr int R = kCullR;
-    __shared__ CullShared sh;
+    __shared__ CullSharedT<POS> sh;
 #ifdef SRT_DIAG
     const unsigned long long d_rt0 = __builtin_amdgcn_s_memrealtime();
 #endif
@@ -3751,7 +3786,7 @@ __global__ __launch_bounds__(kCullThreads, SRT_TRACE_OCC) void TraceCullKernel(c
     // from lane (wave R + r) of fy_lane (the GenerateRays expressions, bit for bit).
     const int x = tx * kWave + lane;
     const int y0 = row0 + wave * R;
-    const bool regular = (flags & kItemRegular) != 0u;
+    const bool regular = !POS || (flags & kItemRegular) != 0u;  // (no table: regular, known at compile time)
     float fy_lane = __builtin_nanf("");
     Rays<R> s;
     Box lane_box;
@@ -3987,7 +4022,12 @@ __global__ __launch_bounds__(kCullThreads, SRT_TRACE_OCC) void TraceCullKernel(c
         for (int r = 0; r < R; ++r) {
             const int y = y0 + r;
             if (y < p.row_count) {
-                const float2 f = sh.fxy[wave * R + r][lane];
+                float2 f;
+                if constexpr (POS) {
+                    f = sh.fxy[wave * R + r][lane];
+                } else {
+                    f = make_float2(sh.clo[lane], sh.rlo[wave * R + r]);
+                }
                 StoreRgba(p, x, y, ShadeRecord(p, f.x, f.y, id[r], nr[r], al[r]));
             }
         }
@@ -4001,7 +4041,9 @@ __global__ __launch_bounds__(kCullThreads, SRT_TRACE_OCC) void TraceCullKernel(c
     if constexpr (SHARED) {
         sweep_fill();
     }
-    if (todo != 0ull) {  // (block-uniform: every wave made the same ballot)
+    // (TODO = false: the host established that no sweep block of the launch has anything to trace --
+    // every tile's facts valid, no swept descriptor FULL --, and the second copy is not compiled)
+    if (TODO && todo != 0ull) {  // (block-uniform: every wave made the same ballot)
         if (threadIdx.x == 0) {
             sh.last = static_cast<unsigned>(todo);
             sh.todo_hi = static_cast<unsigned>(todo >> 32);
@@ -6372,9 +6414,15 @@ __global__ __launch_bounds__(kPlanBlock) void StreamPlanKernel(uint4* work, uint
     const unsigned d_lo = min(tid * per, descs), d_hi = min(d_lo + per, descs);
     {
         unsigned long long mine = 0ull;  // low word: list descriptors of [d_lo, d_hi), high word: empty ones
+        unsigned both = 0u;  // empty and FULL at once: a sweep block would have to trace them (stream_count[2])
         for (unsigned d = d_lo; d < d_hi; ++d) {
             const uint4 w0 = work[2 * d];
             mine += w0.x == kWorkEnd ? 0ull : (w0.w & kItemEmpty) != 0u ? 1ull << 32 : 1ull;
+            both += w0.x != kWorkEnd && (w0.w & (kItemEmpty | kItemFull)) == (kItemEmpty | kItemFull) ? 1u : 0u;
+        }
+        const int any_both = __syncthreads_count(both != 0u);  // (the work order gives none: counted, not assumed)
+        if (tid == 0) {
+            stream_count[2] = static_cast<unsigned long long>(any_both);
         }
         sums[tid] = mine;
         __syncthreads();
@@ -6556,10 +6604,22 @@ void LaunchFactsStage(const TB& tb, const BB& bb, bool lean, unsigned fz, unsign
 }
 template <class TB, class BB>
 void LaunchSharedStages(const TB& tb, const BB& bb, bool lean, unsigned fz, unsigned z, unsigned gx, unsigned gy,
-                        bool recompute, bool streamed, unsigned descs, hipStream_t stream, const StageEvents& ev) {
+                        bool recompute, bool streamed, bool regular, unsigned descs, hipStream_t stream,
+                        const StageEvents& ev) {
     // (descs: the trace grid -- the plan's room, or SharedTraceBlocks with the empty sweep)
     LaunchFactsStage(tb, bb, lean, fz, gx, gy, stream, ev);
-    if (recompute) {
+    if (regular) {  // one launch, as ever: the same grid on the kernel without the position table
+        using RF = RegularFrames<TB>;
+        const RF rf{tb};
+        const dim3 grid(descs, 1, z), block(kWave * kCullWaves);
+        if (recompute) {
+            Launch(TraceCullKernel<RF, true, true>, grid, block, stream, ev.begin, ev.end, rf);
+        } else if (streamed) {
+            Launch(TraceCullKernel<RF, false, true, true>, grid, block, stream, ev.begin, ev.end, rf);
+        } else {
+            Launch(TraceCullKernel<RF, false, true>, grid, block, stream, ev.begin, ev.end, rf);
+        }
+    } else if (recompute) {
         Launch(TraceCullKernel<TB, true, true>, dim3(descs, 1, z), dim3(kWave * kCullWaves), stream, ev.begin, ev.end, tb);
     } else if (streamed) {
         Launch(TraceCullKernel<TB, false, true, true>, dim3(descs, 1, z), dim3(kWave * kCullWaves), stream, ev.begin,
@@ -6585,7 +6645,31 @@ BinParams FactsBinParams(const TraceParams& p, TileFacts* facts) {
     b.exp = p.exp;
     return b;
 }
+
+// A pin's summary (render.h LaunchFactsSummary): one block ANDs the three facts over the tiles.
+constexpr int kSummaryBlock = 256;
+__global__ __launch_bounds__(kSummaryBlock) void FactsSummaryKernel(const TileFacts* __restrict__ facts, unsigned tiles,
+                                                                    unsigned* __restrict__ word) {
+    constexpr unsigned kAll = kFactRegular | kFactUsable | kFactInRange;
+    unsigned mine = kAll;
+    for (unsigned t = threadIdx.x; t < tiles; t += kSummaryBlock) {
+        mine &= facts[t].flags;
+    }
+    const int all = __syncthreads_and(mine == kAll);
+    if (threadIdx.x == 0) {
+        *word = kFactsSummaryDone | (all != 0 ? kFactsSummaryRegular : 0u);
+    }
+}
 }  // namespace
+
+hipError_t LaunchFactsSummary(const void* d_facts, std::size_t tiles, unsigned* d_word, hipStream_t stream) {
+    if (d_facts == nullptr || d_word == nullptr || tiles == 0 || tiles > 0xFFFFFFFFull) {
+        return hipErrorInvalidValue;
+    }
+    hipLaunchKernelGGL(FactsSummaryKernel, dim3(1), dim3(kSummaryBlock), 0, stream, static_cast<const TileFacts*>(d_facts),
+                       static_cast<unsigned>(tiles), d_word);
+    return hipGetLastError();
+}
 
 hipError_t LaunchTileFacts(const BandArgs& band, void* d_facts, bool lean, hipStream_t stream) {
     if (band.offsets == nullptr || d_facts == nullptr || band.width == 0 || band.height == 0 || band.row_begin != 0 ||
@@ -6680,6 +6764,11 @@ hipError_t LaunchSharedCullFrames(const CullFrame* frames, std::size_t count, co
             ++fz;
         }
     }
+    if (setup.regular_trace && (fz != 0u || (group != 0u && setup.full_empty_descs != 0u))) {
+        // The regular kernel has no position table and no `todo` loop: every frame brings facts the
+        // caller knows to be regular and valid, and no sweep block has a FULL descriptor to trace.
+        return hipErrorInvalidValue;
+    }
     const unsigned z = static_cast<unsigned>(count);
     const unsigned gx = static_cast<unsigned>(tp[0].tiles_x), gy = tp[0].tiles / gx;
     const bool streamed = setup.stream != nullptr && !setup.recompute;
@@ -6690,7 +6779,7 @@ hipError_t LaunchSharedCullFrames(const CullFrame* frames, std::size_t count, co
     blocks = group != 0u ? std::max(setup.list_descs, 1u) : blocks;
 #endif
     if (!use_table) {
-        LaunchSharedStages(tb, bb, lean, fz, z, gx, gy, setup.recompute, streamed, blocks, stream, ev);
+        LaunchSharedStages(tb, bb, lean, fz, z, gx, gy, setup.recompute, streamed, setup.regular_trace, blocks, stream, ev);
         return hipGetLastError();
     }
     if (table->host_device != nullptr) {
@@ -6712,7 +6801,7 @@ hipError_t LaunchSharedCullFrames(const CullFrame* frames, std::size_t count, co
     unsigned char* dev = static_cast<unsigned char*>(table->device);
     const BinTable bt{(ConstantPtr<BinParams>)(dev + lay.bin)};
     const TraceTable tt{(ConstantPtr<TraceParams>)(dev + lay.trace)};
-    LaunchSharedStages(tt, bt, lean, fz, z, gx, gy, setup.recompute, streamed, blocks, stream, ev);
+    LaunchSharedStages(tt, bt, lean, fz, z, gx, gy, setup.recompute, streamed, setup.regular_trace, blocks, stream, ev);
     return hipGetLastError();
 }
 

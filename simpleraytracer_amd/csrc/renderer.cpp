@@ -184,8 +184,14 @@ DeviceScene::~DeviceScene() {
     (void)hipFree(m_setup);
     (void)hipFree(m_stream);
     m_pins.Clear();
-    for (void* facts : m_pins.TakeRetired()) {
-        (void)hipFree(facts);
+    for (const PinTable::Buffers& b : m_pins.TakeRetired()) {
+        ReleasePinBuffers(b);
+    }
+    for (void* e : m_free_pin_events) {
+        (void)hipEventDestroy(static_cast<hipEvent_t>(e));
+    }
+    for (void* chunk : m_pin_word_chunks) {
+        (void)hipHostFree(chunk);
     }
     for (CullArena& a : m_arenas) {
         (void)hipFree(a.work);
@@ -1054,6 +1060,18 @@ int FactsKernelFromEnv() {
 // SRT_FACTS_PINS = 1 (default) | 0, read per call: whether a whole-frame trace on the shared setup
 // reads the stored facts of its pinned offsets buffers (DeviceScene::PinOffsets); 0: it computes
 // every frame's facts as if nothing were pinned -- the same frames, the A/B leg of a measurement.
+// SRT_TRACE_POS = auto (default) | table, read per call: whether a shared launch whose frames are
+// all pinned with an all-regular summary may run the trace kernel without the position table
+// (renderer.h PinOffsets). table: always the general kernel -- the same frames, the A/B leg.
+bool TracePosAutoFromEnv() {
+    const char* e = std::getenv("SRT_TRACE_POS");
+    const std::string v = e == nullptr || *e == '\0' ? "auto" : e;
+    if (v != "auto" && v != "table") {
+        throw std::runtime_error("SRT_TRACE_POS must be auto or table, got '" + v + "'");
+    }
+    return v == "auto";
+}
+
 bool FactsPinsFromEnv() {
     const char* e = std::getenv("SRT_FACTS_PINS");
     const std::string v = e == nullptr || *e == '\0' ? "1" : e;
@@ -1122,11 +1140,12 @@ void DeviceScene::LogSetupStats() const {
     std::fprintf(stderr,
                  "srt setup: scene %p builds %llu shared_frames %llu per_frame_frames %llu stream_frames %llu "
                  "stream_records %llu empty_descs %llu sweep_blocks %llu facts_fill_frames %llu "
-                 "lean_facts_frames %llu pinned_frames %llu facts_launches %llu\n",
+                 "lean_facts_frames %llu pinned_frames %llu facts_launches %llu regular_launches %llu\n",
                  static_cast<const void*>(this), m_setup_stats.builds, m_setup_stats.shared_frames,
                  m_setup_stats.per_frame_frames, m_setup_stats.stream_frames, m_setup_stats.stream_records,
                  m_setup_stats.empty_descs, m_setup_stats.sweep_blocks, m_setup_stats.facts_fill_frames,
-                 m_setup_stats.lean_facts_frames, m_setup_stats.pinned_frames, m_setup_stats.facts_launches);
+                 m_setup_stats.lean_facts_frames, m_setup_stats.pinned_frames, m_setup_stats.facts_launches,
+                 m_setup_stats.regular_launches);
     std::fflush(stderr);
 }
 
@@ -1137,6 +1156,7 @@ void DeviceScene::TraceShared(const float* const* d_offsets, float* const* d_rgb
     // the facts kernels' own measurements and tests), so such a call computes its facts too.
     const int want = FactsKernelFromEnv();
     const bool use_pins = FactsPinsFromEnv() && want < 0 && !m_pins.empty();  // (junk is an error, pins or none)
+    const bool pos_auto = TracePosAutoFromEnv();
     OrderAfterPrevious(stream);
     // The frame slots' own state (tile facts, split key slices, arrival counters) lives in the cull
     // work of the whole-frame shape; no edge slots: the records are the setup's.
@@ -1192,6 +1212,14 @@ void DeviceScene::TraceShared(const float* const* d_offsets, float* const* d_rgb
         }
         setup.lean_facts = want < 0 ? reused : want == 1;
     }
+    // A regular launch: RGBA frames that all bring the stored facts of a pin whose summary is known
+    // to be all regular and valid (a summary still unknown is not waited for: the general kernel
+    // gives the same bits), on a plan none of whose sweep blocks can have a descriptor to trace.
+    bool regular = pos_auto && unpinned == 0 && d_ids == nullptr && d_rgba != nullptr && setup.full_empty_descs == 0;
+    for (std::size_t f = 0; f < frames && regular; ++f) {
+        regular = PinSummary(d_offsets[f], false) == PinTable::kRegular;
+    }
+    setup.regular_trace = regular;
     // (the last trace's grid: sweep blocks per frame, 0 with the sweep off)
     m_setup_stats.sweep_blocks =
         setup.sweep ? SharedTraceBlocks(setup.descs, setup.list_descs, setup.empty_descs, setup.empty_group) - setup.list_descs
@@ -1214,6 +1242,7 @@ void DeviceScene::TraceShared(const float* const* d_offsets, float* const* d_rgb
     m_setup_stats.lean_facts_frames += setup.lean_facts || (setup.sweep && setup.facts_fill) ? unpinned : 0;
     m_setup_stats.pinned_frames += frames - unpinned;
     m_setup_stats.facts_launches += unpinned != 0 ? 1 : 0;
+    m_setup_stats.regular_launches += regular ? 1 : 0;
     LogSetupStats();
     RecordOrder(stream);
 }
@@ -1231,29 +1260,47 @@ void DeviceScene::PinOffsets(const float* d_offsets, hipStream_t stream) {
     }
     // A launch of one frame brings its own buffer: the block kernel, unless the env names one.
     const int want = FactsKernelFromEnv();
-    void* facts = m_pins.Find(d_offsets);
-    const bool fresh = facts == nullptr;
+    PinTable::Buffers buf = m_pins.FindBuffers(d_offsets);
+    const bool fresh = buf.facts == nullptr;
+    const std::size_t tiles = CullTiles(m_width, m_height);
     if (fresh) {
         if (m_pins.full()) {
             throw std::runtime_error("PinOffsets: at most " + std::to_string(PinTable::kMaxPins) +
                                      " pinned buffers per scene (unpin one first)");
         }
-        facts = DeviceAlloc<unsigned char>(CullTiles(m_width, m_height) * 16, "hipMalloc(pinned facts)");
+        buf = NewPinBuffers(tiles);
+    } else {
+        // A pin again rewrites the facts: their summary is unknown from here on, before the launch
+        // is queued, and is read again only after the event recorded below -- a later record of the
+        // same event, so that hipEventQuery speaks of the new facts alone.
+        m_pins.MarkPending(d_offsets);
     }
     OrderAfterPrevious(stream);  // (a pin again: earlier traces read the buffer this launch rewrites)
     const BandArgs band{d_offsets, nullptr, m_width, m_height, 0, m_height};
-    const hipError_t launched = LaunchTileFacts(band, facts, want == 1, stream);
+    hipError_t launched = LaunchTileFacts(band, buf.facts, want == 1, stream);
+    if (launched == hipSuccess) {
+        void* d_word = nullptr;
+        launched = hipHostGetDevicePointer(&d_word, buf.word, 0);
+        if (launched == hipSuccess) {
+            launched = LaunchFactsSummary(buf.facts, tiles, static_cast<unsigned*>(d_word), stream);
+        }
+        if (launched == hipSuccess) {
+            launched = hipEventRecord(static_cast<hipEvent_t>(buf.event), stream);
+        }
+    }
     RecordOrder(stream);
     if (launched != hipSuccess) {
-        // Facts that were not computed must not be read: the pin is gone (a fresh buffer was never
+        // Facts that were not computed must not be read, nor a summary whose event was not recorded
+        // (the event's earlier record would answer for it): the pin is gone (a fresh buffer was never
         // visible to any launch; a standing one may be read by queued traces: retired, released later).
         if (fresh) {
-            (void)hipFree(facts);
+            (void)hipStreamSynchronize(stream);  // (what was queued may write the buffers)
+            ReleasePinBuffers(buf);
         } else {
             m_pins.Remove(d_offsets);
         }
     } else if (fresh) {
-        m_pins.Insert(d_offsets, facts);
+        m_pins.Insert(d_offsets, buf);
     }
     HipCheck(launched, "pinned facts launch");
     ++m_setup_stats.facts_launches;
@@ -1266,6 +1313,38 @@ void DeviceScene::UnpinOffsets(const float* d_offsets) {
 }
 
 std::size_t DeviceScene::pinned() const { return m_pins.size(); }
+
+PinTable::Summary DeviceScene::PinSummary(const void* key, bool wait) const {
+    const PinTable::Summary known = m_pins.summary(key);
+    const PinTable::Buffers buf = m_pins.FindBuffers(key);
+    if (known != PinTable::kUnknown || buf.event == nullptr || buf.word == nullptr) {
+        return known;
+    }
+    // The event's newest record stands behind the summary launch of the facts now in the buffer
+    // (PinOffsets): completed means the word is theirs.
+    const hipEvent_t event = static_cast<hipEvent_t>(buf.event);
+    if (wait) {
+        HipCheck(hipEventSynchronize(event), "hipEventSynchronize(pin summary)");
+    } else {
+        const hipError_t q = hipEventQuery(event);
+        if (q == hipErrorNotReady) {
+            (void)hipGetLastError();  // (not an error: nothing of it is left for the next launch's check)
+            return PinTable::kUnknown;
+        }
+        HipCheck(q, "hipEventQuery(pin summary)");
+    }
+    const unsigned word = *static_cast<const volatile unsigned*>(buf.word);
+    const bool regular = (word & kFactsSummaryDone) != 0u && (word & kFactsSummaryRegular) != 0u;
+    const PinTable::Summary s = regular ? PinTable::kRegular : PinTable::kOther;
+    m_pins.SetSummary(key, m_pins.generation(key), s);
+    return s;
+}
+
+void DeviceScene::ResolvePinSummaries() {
+    for (const void* key : m_pins.Pending()) {
+        PinSummary(key, true);
+    }
+}
 
 // Calls on one scene form one chain (OrderAfterPrevious), so the newest order event stands for all
 // of the scene's work so far.
@@ -1286,8 +1365,47 @@ void DeviceScene::ReleaseRetiredPins() {
         return;
     }
     WaitForPrevious();  // (throws: the buffers stay retired, and are freed with the scene at the latest)
-    for (void* facts : m_pins.TakeRetired()) {
-        (void)hipFree(facts);
+    for (const PinTable::Buffers& b : m_pins.TakeRetired()) {
+        ReleasePinBuffers(b);
+    }
+}
+
+// A pin's buffers (pin_table.h Buffers): the facts, and a summary word and an event from the scene's
+// free lists (renderer.h). The word is zero: nothing says "done" before the pin's own summary launch.
+PinTable::Buffers DeviceScene::NewPinBuffers(std::size_t tiles) {
+    if (m_free_pin_words.empty()) {
+        // Page-locked and mapped: the summary kernel stores the word over the bus, the host reads it
+        // once the pin's event has completed.
+        void* chunk = nullptr;
+        HipCheck(hipHostMalloc(&chunk, PinTable::kMaxPins * sizeof(unsigned), hipHostMallocMapped),
+                 "hipHostMalloc(pin summary words)");
+        m_pin_word_chunks.push_back(chunk);
+        for (std::size_t i = 0; i < PinTable::kMaxPins; ++i) {
+            m_free_pin_words.push_back(static_cast<unsigned*>(chunk) + i);
+        }
+    }
+    if (m_free_pin_events.empty()) {
+        hipEvent_t event = nullptr;
+        HipCheck(hipEventCreateWithFlags(&event, hipEventDisableTiming), "hipEventCreate(pin summary)");
+        m_free_pin_events.push_back(event);
+    }
+    PinTable::Buffers b;
+    b.facts = DeviceAlloc<unsigned char>(tiles * 16, "hipMalloc(pinned facts)");  // (throws: the lists keep theirs)
+    b.word = m_free_pin_words.back();
+    m_free_pin_words.pop_back();
+    b.event = m_free_pin_events.back();
+    m_free_pin_events.pop_back();
+    *static_cast<unsigned*>(b.word) = 0u;
+    return b;
+}
+
+void DeviceScene::ReleasePinBuffers(const PinTable::Buffers& b) {
+    (void)hipFree(b.facts);
+    if (b.word != nullptr) {
+        m_free_pin_words.push_back(b.word);
+    }
+    if (b.event != nullptr) {
+        m_free_pin_events.push_back(b.event);
     }
 }
 
@@ -1329,13 +1447,14 @@ CullSetup DeviceScene::EnsureSetup(unsigned descs, hipStream_t stream) const {
                  "cull setup launch");
         // The stream's length and the plan's list and empty descriptor counts are known only from
         // the built plan: one host read per build (never per frame), with a stream or without.
-        unsigned long long plan[2] = {0, 0};
+        unsigned long long plan[3] = {0, 0, 0};
         HipCheck(LaunchStreamPlan(setup, stream), "record stream plan launch");
         HipCheck(hipMemcpyAsync(plan, setup.stream_count, sizeof(plan), hipMemcpyDeviceToHost, stream),
                  "hipMemcpyAsync(plan counts)");
         HipCheck(hipStreamSynchronize(stream), "hipStreamSynchronize(plan counts)");
         m_list_descs = static_cast<unsigned>(plan[1]);
         m_empty_descs = static_cast<unsigned>(plan[1] >> 32);
+        m_full_empty_descs = static_cast<unsigned>(plan[2]);
         if (want_stream) {
             // Over the cap, this setup's frames keep the indexed path.
             const unsigned long long records = plan[0];
@@ -1363,6 +1482,7 @@ CullSetup DeviceScene::EnsureSetup(unsigned descs, hipStream_t stream) const {
     setup.stream = m_stream_on ? m_stream : nullptr;
     setup.list_descs = m_list_descs;
     setup.empty_descs = m_empty_descs;
+    setup.full_empty_descs = m_full_empty_descs;
     return setup;
 }
 

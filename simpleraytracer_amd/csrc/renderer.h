@@ -127,7 +127,18 @@ public:
     // Bands, SRT_SETUP=frame, the other variants, SRT_EMPTY_FILL=facts and an explicit
     // SRT_FACTS_KERNEL=lean|block (which asks for that facts kernel in the launch) compute their own
     // facts whatever is pinned; env SRT_FACTS_PINS=0 (read per call; default 1) makes every trace do so.
+    // A pin also learns its summary: whether every tile of the buffer is regular, usable and in range
+    // (render.h LaunchFactsSummary, queued behind the facts launch; PinOffsets stays asynchronous).
+    // It is unknown until that work has completed -- a trace finds out with hipEventQuery, without
+    // waiting --, and a pin again makes it unknown before the new facts launch is queued. A launch
+    // whose frames are all pinned with a known all-regular summary runs the trace kernel without the
+    // position table (a regular launch: render.h CullSetup::regular_trace; counted in
+    // SetupStats::regular_launches); any other launch runs the general kernel: the same bits. Env
+    // SRT_TRACE_POS = auto (default) | table, read per call: table never takes the regular form.
     void PinOffsets(const float* d_offsets, hipStream_t stream);
+    // Waits for the summaries of the standing pins that are still unknown (a caller outside its timed
+    // region, such as FrameEngine::SetInputs: the launches that follow then find them known).
+    void ResolvePinSummaries();
     // Forgets the pin of d_offsets (not pinned: nothing). Waits for the scene's previous work, which
     // may read the facts, before it frees them.
     void UnpinOffsets(const float* d_offsets);
@@ -342,6 +353,8 @@ public:
         // the facts launches issued: one per shared launch with an unpinned frame, one per PinOffsets.
         unsigned long long pinned_frames = 0;
         unsigned long long facts_launches = 0;
+        // Shared launches that ran the regular trace kernel (every frame pinned, all-regular summary).
+        unsigned long long regular_launches = 0;
     };
     SetupStats setup_stats() const { return m_setup_stats; }
 
@@ -400,13 +413,28 @@ private:
     mutable std::size_t m_stream_records = 0;
     mutable bool m_stream_on = false;
     mutable unsigned m_list_descs = 0, m_empty_descs = 0;  // the standing setup's plan (render.h CullSetup)
+    mutable unsigned m_full_empty_descs = 0;                // (its stream_count[2]: bars regular launches)
     mutable bool m_setup_pending = true;
     mutable SetupKey m_setup_key{};
     mutable SetupStats m_setup_stats{};
     void LogSetupStats() const;
     // Pinned offsets: pointer -> facts buffer (CullTiles(W, H) x 16 B each, hipMalloc'ed here). A
-    // removed pin's buffer is freed by ReleaseRetiredPins, after the scene's previous work.
-    PinTable m_pins;
+    // removed pin's buffer is freed by ReleaseRetiredPins, after the scene's previous work. With each
+    // facts buffer go the pin's summary word (page-locked, mapped) and the event recorded behind the
+    // launch that writes it. mutable: a trace (const) records a summary it finds completed.
+    mutable PinTable m_pins;
+    // The words and events are recycled: page-locked memory is allocated a chunk of kMaxPins words at
+    // a time (hipHostMalloc and hipHostFree per pin doubled SetInputs' time), an event is created
+    // when none is free; both go back to the free lists when a pin's buffers are released and are
+    // destroyed with the scene.
+    std::vector<void*> m_pin_word_chunks;
+    std::vector<void*> m_free_pin_words;
+    std::vector<void*> m_free_pin_events;
+    PinTable::Buffers NewPinBuffers(std::size_t tiles);      // throws; nothing is left allocated then
+    void ReleasePinBuffers(const PinTable::Buffers& b);      // after the work that uses them
+    // The summary of `key`'s pin: known, or read now if its event has completed (wait: after waiting
+    // for it); kUnknown otherwise, and for a key that is not pinned.
+    PinTable::Summary PinSummary(const void* key, bool wait) const;
     void WaitForPrevious() const;  // the host waits for the scene's last call
     void ReleaseRetiredPins();
     // Whether a binned cull trace of this band runs on the shared setup (env SRT_SETUP).
