@@ -16,7 +16,7 @@ HIPFLAGS := --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -ffp-contract=off -fno-s
             -fvisibility=hidden -DRADEONPROML_BUILD -Iinclude -Wall -Wno-unused-result
 LDFLAGS  := -shared -L/opt/rocm/lib -lrccl -Wl,-rpath,/opt/rocm/lib -Wl,--no-undefined
 
-OBJS := $(BUILD)/render.o $(BUILD)/spatial.o $(BUILD)/rays.o $(BUILD)/visibility.o $(BUILD)/radiance.o $(BUILD)/renderer.o $(BUILD)/engine.o $(BUILD)/comm.o $(BUILD)/cpu_render.o \
+OBJS := $(BUILD)/render.o $(BUILD)/outputs.o $(BUILD)/query.o $(BUILD)/spatial.o $(BUILD)/rays.o $(BUILD)/visibility.o $(BUILD)/radiance.o $(BUILD)/renderer.o $(BUILD)/engine.o $(BUILD)/comm.o $(BUILD)/cpu_render.o \
         $(BUILD)/scene.o $(BUILD)/image.o $(BUILD)/model.o $(BUILD)/context.o $(BUILD)/srt_api.o
 
 HEADERS := $(wildcard $(CSRC)/*.h) include/model_runner.h include/srt_render.h include/srt_query.h include/srt_gbuffer.h \
@@ -29,8 +29,12 @@ DIAG_BUILD := build/diag
 DIAG_LIB   := simpleraytracer_amd/lib_diag/libModelRunner.so
 DIAG_OBJS  := $(patsubst $(BUILD)/%,$(DIAG_BUILD)/%,$(OBJS))
 
-.PHONY: all oracle ref clean diag exp
+.PHONY: all oracle ref clean diag exp print-hipflags
 all: $(LIB) bin/test_app
+
+# The device compile flags, for tools that compile a unit the way this file does (tools/compare_kernels.py).
+print-hipflags:
+	@echo $(HIPFLAGS)
 
 $(BUILD)/%.o: $(CSRC)/%.hip $(HEADERS)
 	@mkdir -p $(BUILD)
@@ -73,10 +77,12 @@ EXP_NAME  ?= default
 EXP_FLAGS ?=
 EXP_BUILD := build/exp/$(EXP_NAME)
 EXP_LIB   := simpleraytracer_amd/lib_exp/$(EXP_NAME)/libModelRunner.so
+# The flags reach the render kernel units (render, outputs, query); the other objects are the product's.
+EXP_UNITS := render outputs query
 exp:
 	@mkdir -p $(EXP_BUILD) $(dir $(EXP_LIB))
-	$(HIPCC) $(HIPFLAGS) $(EXP_FLAGS) -c $(CSRC)/render.hip -o $(EXP_BUILD)/render.o
-	$(HIPCC) --offload-arch=$(ARCH) $(EXP_BUILD)/render.o $(filter-out $(BUILD)/render.o,$(OBJS)) -o $(EXP_LIB) $(LDFLAGS)
+	for u in $(EXP_UNITS); do $(HIPCC) $(HIPFLAGS) $(EXP_FLAGS) -c $(CSRC)/$$u.hip -o $(EXP_BUILD)/$$u.o || exit 1; done
+	$(HIPCC) --offload-arch=$(ARCH) $(EXP_UNITS:%=$(EXP_BUILD)/%.o) $(filter-out $(EXP_UNITS:%=$(BUILD)/%.o),$(OBJS)) -o $(EXP_LIB) $(LDFLAGS)
 
 oracle:
 	$(MAKE) -C oracle

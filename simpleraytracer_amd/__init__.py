@@ -2,7 +2,7 @@
 ml* C ABI of the reference's libModelRunner.so.
 
 Layers:
-  csrc/        HIP kernels (render.hip) + C++ host objects (Context/Image/Model/Renderer)
+  csrc/        HIP kernels (render.hip: the trace; outputs.hip, query.hip, rays.hip, ...) + C++ host objects (Context/Image/Model/Renderer)
   _native.py   ctypes binding of lib/libModelRunner.so
   runner.py    Python mirror of the ml* API (Context, Model, Image, render())
   device.py    scene files + device-level stages on caller buffers (DeviceScene)

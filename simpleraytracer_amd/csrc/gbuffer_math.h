@@ -1,5 +1,5 @@
 // The surface attributes of one (image position, triangle) pair: the G-buffer's per-pair arithmetic
-// (render.hip GBufferKernel; DESIGN.md section 2 "Surface attributes"). Host and device share it
+// (outputs.hip GBufferKernel; DESIGN.md section 2 "Surface attributes"). Host and device share it
 // (cpu_render.cpp HostGBuffer, the host answer rtgPointsHost), so both evaluate the same float
 // expressions: explicit fma, no contraction, IEEE divide and square root.
 //

@@ -1,5 +1,5 @@
 // The over-composite of a pixel's depth layers: the per-pixel arithmetic of CompositeKernel
-// (render.hip; DESIGN.md section 2 "Composite"). Host and device share it (cpu_render.cpp
+// (query.hip; DESIGN.md section 2 "Composite"). Host and device share it (cpu_render.cpp
 // HostComposite, the host answer rtkCompositeHost), so both evaluate the same float expressions.
 //
 // Every operation this header adds is float32 with separate multiply and add -- no fma, no

@@ -45,7 +45,7 @@ constexpr float kScreenBoxRange = 4.0f;
 // q = v * kQuantScale, lo rounded down and hi up, clamped to [-32767, 32767].
 constexpr float kQuantScale = 4096.0f;
 
-// Cull records (render.hip CullRecord): 64 B per record, at the record's rank in the scene's
+// Cull records (trace_device.h CullRecord): 64 B per record, at the record's rank in the scene's
 // spatial order, after the quantized boxes.
 // Floats per record in the edge allocation: 10 (tiles) + 4 (screen box) + 2 (quantized box)
 // + 16 (cull record). (Shading computes a hit triangle's normal from its vertices: no per-frame
@@ -186,7 +186,7 @@ struct CullBins {
     unsigned capacity;
     std::size_t tiles;
     bool plan = true;      // (re)build the slot's work plan with this frame (else the trace uses the last one)
-    // Records recomputed by the trace (render.hip TraceRecords<true>): the bin launch writes a 16-B
+    // Records recomputed by the trace (trace_device.h TraceRecords<true>): the bin launch writes a 16-B
     // screen box per position instead of the 64-B cull record, the trace rebuilds the record from the
     // scene's 48-B spatial inputs. Same frame bit for bit; trades bin-launch bytes for trace VALU, so
     // it pays where the bin launch is on the critical path (one frame queue, one-frame launches).
@@ -411,7 +411,7 @@ constexpr unsigned kFactsSummaryDone = 0x80000000u;
 constexpr unsigned kFactsSummaryRegular = 1u;
 hipError_t LaunchFactsSummary(const void* d_facts, std::size_t tiles, unsigned* d_word, hipStream_t stream);
 
-// Point queries (render.hip QueryKernel): the closest hit at `count` arbitrary image positions
+// Point queries (query.hip QueryKernel): the closest hit at `count` arbitrary image positions
 // (fx, fy) of the frame -- the quantity ray generation produces, nothing about pixels: ids[i] = the
 // hit record's id or -1, t[i] = its t = vol / det or +inf, the lexicographic (t, id) minimum, bit
 // for bit what the traces compute for a ray at that position. how[i] (null: not stored): 0 = answered
@@ -431,7 +431,7 @@ hipError_t LaunchQuery(const CullSetup* setup, std::uint64_t n, const Frame& fra
                        std::size_t height, const float* d_svertices, const float* d_edges, const QueryArgs& args,
                        hipStream_t stream);
 
-// Depth layers (render.hip LayersKernel; DESIGN.md section 2 "Layers"): at every position the
+// Depth layers (query.hip LayersKernel; DESIGN.md section 2 "Layers"): at every position the
 // `layers` (1 .. kMaxLayers) lexicographically smallest (t, id) keys among the records passing the
 // exact test, front to back: ids[k * E + i] = layer k's id at element i of E, or -1, t[...] = its t
 // or +inf (t null: not stored). Layer 0 is LaunchQuery's answer. how[i] as QueryArgs::how.
@@ -455,7 +455,7 @@ hipError_t LaunchLayers(const CullSetup* setup, std::uint64_t n, const Frame& fr
                         std::size_t height, const float* d_svertices, const float* d_edges, const LayersArgs& args,
                         hipStream_t stream);
 
-// Composite (render.hip CompositeKernel; layers_math.h; DESIGN.md section 2 "Composite"): one RGBA
+// Composite (query.hip CompositeKernel; layers_math.h; DESIGN.md section 2 "Composite"): one RGBA
 // pixel from `layers` id planes of a band -- each layer shaded as LaunchShade shades it and
 // composited front to back under the per-triangle opacity table; alpha = 1 - the transmittance
 // left. Reads the shading table and the opacity table only. The composite of a pixel stops at its
@@ -598,7 +598,7 @@ hipError_t LaunchLitSurface(const float* d_vertices, const float* d_shade, std::
                             const float background[3], const LightingLight* lights, std::size_t count,
                             const LightingArgs& args, const LitSurface& surface, hipStream_t stream);
 
-// G-buffer (render.hip GBufferKernel): the surface attributes of (image position, triangle id)
+// G-buffer (outputs.hip GBufferKernel): the surface attributes of (image position, triangle id)
 // pairs of the frame -- depth, barycentrics, normal + shading cosine, albedo + id (gbuffer_math.h;
 // DESIGN.md section 2 "Surface attributes") -- from hit ids, a deferred pass like LaunchShade with
 // more outputs. The record of an id is recomputed from the scene's vertices (ComputeEdges under
@@ -626,7 +626,7 @@ struct GBufferArgs {
 hipError_t LaunchGBuffer(const float* d_vertices, const float* d_shade, std::uint64_t n, const Frame& frame,
                          const float background[3], const GBufferArgs& args, hipStream_t stream);
 
-// Vertex attributes (render.hip SurfaceKernel / InterpolateKernel): what the surface looks like at
+// Vertex attributes (outputs.hip SurfaceKernel / InterpolateKernel): what the surface looks like at
 // (image position, triangle id) pairs -- a smooth normal, a UV, a textured albedo and the shaded
 // pixel (surface_math.h; DESIGN.md section 2 "Vertex attributes") -- from hit ids and the caller's
 // per-triangle corner tables, a deferred pass like LaunchGBuffer. The weights come from the record
@@ -675,7 +675,7 @@ struct InterpolateArgs {
 hipError_t LaunchInterpolate(const float* d_vertices, std::uint64_t n, const Frame& frame, const InterpolateArgs& args,
                              hipStream_t stream);
 
-// Resolve (render.hip ResolveKernel): one RGBA pixel from `samples` (sample offset, hit id) planes
+// Resolve (outputs.hip ResolveKernel): one RGBA pixel from `samples` (sample offset, hit id) planes
 // of a band -- every sample shaded as LaunchShade shades it, summed in ascending order and divided
 // by the count; alpha = the share of samples that hit (samples_math.h; DESIGN.md section 2
 // "Resolve"). Reads the shading table only. An id outside [0, n) is a miss and reads nothing

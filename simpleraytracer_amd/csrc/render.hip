@@ -6,7 +6,7 @@
 #include "render.h"
 #include "gbuffer_math.h"
 #include "hits_math.h"
-#include "layers_math.h"
+#include "candidate_walk.h"
 #include "lighting_math.h"
 #include "material_math.h"
 #include "radiance.h"
@@ -17,7 +17,7 @@
 #include "shading_normal.h"
 #include "shadow_math.h"
 #include "surface_math.h"
-#include "tile_lookup.h"
+#include "trace_device.h"
 #include "visibility_device.h"
 
 #include <hip/hip_ext.h>
@@ -65,99 +65,8 @@ constexpr int kDiagOrderRow = 60000, kDiagBinRow = 61000;
 
 namespace {
 
-constexpr int kWave = 64;
 constexpr int kLdsWaves = 4;     // waves per block in the LDS variant
 constexpr int kRowsPerLane = 8;  // rays per lane (LDS / scalar variants): one column, 8 rows
-
-// Cull record (the binned cull path's copy of one edge record, 64 B, stored at the record's
-// rank in the scene's spatial order): a = (c0A, cxA, cyA, c0B), b = (cxB, cyB, c0C, cxC),
-// x = (cyC, vol, id bits, 0), sb = screen box.
-struct CullRecord {
-    float4 a, b, x, sb;
-};
-static_assert(sizeof(CullRecord) == kCullRecordBytes, "render.h kCullRecordBytes");
-
-// Per-tile facts the cull trace and the bin kernel share (TileInfoKernel), 32 B.
-struct TileInfo {
-    float4 box;         // (xlo, xhi, ylo, yhi) of the tile's ray positions (NaN positions drop out)
-    float ox, oy;       // sample offset of the tile's first ray
-    unsigned regular;   // every ray of the tile has offset (ox, oy), bit for bit
-    unsigned usable;    // box within the screen-box range (else the tile streams every record)
-};
-
-// Per-tile facts of one frame on the shared setup (render.h CullSetup; TileFactsKernel),
-// 16 B: what a trace block still needs from its own frame's offsets. The tile box is not among
-// them: the shared lists were binned against the analytic box, which contains the tile's rays
-// exactly when every offset of the tile lies in [0, 1] (kFactInRange).
-constexpr unsigned kFactRegular = 1u;  // every ray of the tile has offset (ox, oy), bit for bit
-constexpr unsigned kFactUsable = 2u;   // the tile's ray box lies within the screen-box range
-constexpr unsigned kFactInRange = 4u;  // every offset of the tile lies in [0, 1] (NaN: outside)
-struct TileFacts {
-    float ox, oy;  // sample offset of the tile's first ray
-    unsigned flags;
-    unsigned pad;
-};
-
-struct TraceParams {
-    const float4* __restrict__ edges;
-    const float4* __restrict__ screen_boxes;
-    const uint2* __restrict__ qboxes;
-    const float* __restrict__ vertices;
-    const float4* __restrict__ shade;  // per triangle: (shading normal, |normal|), (albedo, 0) -- ShadeTableKernel
-    const float2* __restrict__ offsets;
-    float4* __restrict__ out;
-    int* __restrict__ out_ids;  // non-null: store the hit id per pixel (-1 = miss) instead of RGBA
-    unsigned char* __restrict__ out_packed;  // non-null: store packed ids (render.h PackedIds) instead
-    int id_planes;             // packed ids: bit planes above the low 16 bits
-    unsigned id_words;         // packed ids: 64-bit words per row and plane
-    unsigned id_low_row_bytes; // packed ids: the row's u16 values (padded to 8 B), then its plane words
-    unsigned id_row_bytes;     // packed ids: bytes per row
-    unsigned id_tile_row_bytes;  // packed ids: bytes per tile row (its rows, then its tiles' offsets)
-    int out_frame_rows;  // RGBA out is a whole frame: band row y stores at its frame row (render.h BandArgs)
-    unsigned n_pad;   // records in the edge buffer (multiple of kPadTriangles)
-    unsigned n;       // records in the scene
-    int tiles_x;         // cull tiles per tile row of the band
-    unsigned tiles;      // cull tiles of the band
-    unsigned n_tiles; // tiles holding at least one real record (>= 1)
-    int width;
-    int row_count;
-    int row_begin;
-    int row_interleave;  // band = frame tile rows row_begin / kTileRows + k * row_interleave (1: contiguous rows)
-    // Cull variant with bins (render.h CullBins); tile_info == null: no bins, every tile
-    // computes its own ray box and streams every record.
-    const TileInfo* __restrict__ tile_info;   // per tile: ray box, uniform offset (TileInfoKernel)
-    const TileFacts* __restrict__ tile_facts; // shared setup: this frame's per-tile facts (work, lists: the setup's)
-    const CullRecord* __restrict__ cull;     // cull records in spatial order (the lists hold positions)
-    const unsigned* __restrict__ order;       // spatial-order position -> record id
-    const float* __restrict__ svertices;      // vertices by spatial-order position (binned trace: records recomputed)
-    const uint4* __restrict__ work;           // tile parts (2 x uint4 each), most work first (BuildWorkOrder)
-    const unsigned* __restrict__ work_count;  // [0]: tile parts listed
-    unsigned long long* __restrict__ split_keys;  // key slices of split parts: one per split slot, kBlockRows x 64 each
-    unsigned* __restrict__ arrive;            // per split part (its first slot): chunks finished (self-resetting)
-    const unsigned* __restrict__ bin_lists;   // per tile: candidate positions (PrepareBinKernel)
-    const unsigned* __restrict__ bin_counts;  // per tile: list length; [tiles]: large-list length (this frame's)
-    unsigned* __restrict__ bin_counts_next;   // the slot's other count buffer: reset by the trace for its next frame
-    const unsigned* __restrict__ large_list;  // ids of records binned to every tile
-    const unsigned* __restrict__ range_tag;   // = gen: some sample offset of this frame lies outside [0, 1]
-    const CullRecord* __restrict__ stream;    // shared setup's record stream (render.h; TraceCullKernel<.., STREAM>)
-    const unsigned* __restrict__ empty_map;   // shared setup: per tile, non-zero = statically empty (render.h CullSetup)
-    unsigned gen;                              // frame number of the scene (never 0)
-    unsigned fused;                            // bins from the analytic tile bounds (BinParams::fused)
-    unsigned plan_only;  // the work list is the slot's plan (no order launch for this frame): read the bins
-    unsigned bin_capacity;
-    unsigned list_descs;   // shared setup: the plan's descriptors that are not statically empty (they come first)
-    unsigned empty_descs;  // shared setup: its statically empty descriptors (they follow)
-    unsigned empty_group;  // shared setup: empty descriptors per sweep block (TraceCullKernel); 0: one block each
-    unsigned facts_fill;   // shared setup, sweep on: the facts launch stores the valid empty tiles' misses (TileFactsKernel)
-    unsigned exp;                                // diagnostic build: experiment bits (env SRT_EXP), 0 in the product
-    float wf;
-    float hf;
-    float base[3];
-    float du[3];
-    float dv[3];
-    float bg[3];
-    float eye[3];  // ray origin (the 16-bit id decode recomputes candidate records)
-};
 
 // Frames of one batched launch: block (x, y, z) works on frame z. Up to kMaxBatch frames carry
 // their parameters in the kernel-argument segment (FrameArgs); larger launches (up to
@@ -197,22 +106,6 @@ struct PrepareParams {
     float dv[3];
     unsigned exp;  // diagnostic build: experiment bits (env SRT_EXP), 0 in the product
 };
-
-// One edge record as the trace kernels consume it.
-struct Record {
-    float c0A, cxA, cyA, c0B, cxB, cyB, c0C, cxC, cyC;
-};
-
-__device__ __forceinline__ float Dot3(float ax, float ay, float az, float bx, float by, float bz) {
-    return fmaf(az, bz, fmaf(ay, by, ax * bx));
-}
-
-__device__ __forceinline__ void Cross3(float ax, float ay, float az, float bx, float by, float bz, float& cx,
-                                       float& cy, float& cz) {
-    cx = ay * bz - az * by;
-    cy = az * bx - ax * bz;
-    cz = ax * by - ay * bx;
-}
 
 // Plane addresses of record j of the tile starting at `tile` (render.h "tile-planar").
 __device__ __forceinline__ const float* Plane2(const float4* tile) {
@@ -308,50 +201,6 @@ __device__ __forceinline__ unsigned PackI16(int low, int high) {
 // E(fx, fy) = n . (base + fx du + fy dv): c = (c0A, cxA, cyA, c0B, cxB, cyB, c0C, cxC, cyC).
 // Disabled (padding, degenerate, plane through the eye): NaN record, empty screen box.
 // v = the triangle's 9 vertex coordinates.
-// The edge coefficients and vol alone (ComputeRecord without the screen box), under the frame
-// (origin, base, du, dv); returns false for a disabled record (c, vol NaN). One definition for the
-// record pass and the 16-bit id decode, so both see the same bits.
-__device__ __forceinline__ bool ComputeEdges(const float* origin, const float* base, const float* du, const float* dv,
-                                             const float* __restrict__ v, bool real, float c[9], float& vol) {
-    const float qnan = __builtin_nanf("");
-    bool disabled = !real;
-    vol = qnan;
-    if (!disabled) {
-        const float ax = v[0] - origin[0], ay = v[1] - origin[1], az = v[2] - origin[2];
-        const float bx = v[3] - origin[0], by = v[4] - origin[1], bz = v[5] - origin[2];
-        const float cx = v[6] - origin[0], cy = v[7] - origin[1], cz = v[8] - origin[2];
-        float n[9];
-        Cross3(bx, by, bz, cx, cy, cz, n[0], n[1], n[2]);
-        Cross3(cx, cy, cz, ax, ay, az, n[3], n[4], n[5]);
-        Cross3(ax, ay, az, bx, by, bz, n[6], n[7], n[8]);
-        vol = Dot3(ax, ay, az, n[0], n[1], n[2]);
-        disabled = !(std::isfinite(vol) && vol != 0.f);
-        if (!disabled) {
-            if (vol < 0.f) {
-#pragma unroll
-                for (int k = 0; k < 9; ++k) {
-                    n[k] = -n[k];
-                }
-                vol = -vol;
-            }
-#pragma unroll
-            for (int e = 0; e < 3; ++e) {
-                const float nx = n[3 * e], ny = n[3 * e + 1], nz = n[3 * e + 2];
-                c[3 * e + 0] = Dot3(nx, ny, nz, base[0], base[1], base[2]);
-                c[3 * e + 1] = Dot3(nx, ny, nz, du[0], du[1], du[2]);
-                c[3 * e + 2] = Dot3(nx, ny, nz, dv[0], dv[1], dv[2]);
-            }
-        }
-    }
-    if (disabled) {
-#pragma unroll
-        for (int k = 0; k < 9; ++k) {
-            c[k] = qnan;
-        }
-        vol = qnan;
-    }
-    return !disabled;
-}
 
 __device__ __forceinline__ void ComputeRecord(const PrepareParams& p, const float* __restrict__ v, bool real, float c[9],
                                               float& vol, float4& sb) {
@@ -446,15 +295,6 @@ __device__ __forceinline__ void PrepareRecord(const PrepareParams& p, unsigned i
 __global__ __launch_bounds__(256) void PrepareKernel(PrepareParams p) {
     PrepareRecord(p, blockIdx.x * blockDim.x + threadIdx.x);
 }
-
-// Per-lane ray state: R rays sharing one image column.
-template <int R>
-struct Rays {
-    float fx[R];
-    float fy[R];
-    float bt[R];  // closest t so far (+inf = none)
-    int bi[R];    // closest triangle id (-1 = miss)
-};
 
 // Axis-aligned box in image-position space (fx, fy) containing a set of rays.
 struct Box {
@@ -605,14 +445,6 @@ __device__ __forceinline__ float4 ShadePixel(const TraceParams& p, float fx, flo
 // instruction), or only its hit id (out_ids: deferred shading by ShadeIdsKernel, bit-identical).
 // Nontemporal (`global_store ... nt`): the frame never reads its framebuffer back, and streaming
 // it past the L2 keeps the cull records, lists and tables resident (+7.8 % at C3).
-typedef float F4 __attribute__((ext_vector_type(4)));
-// A nontemporal float4 store the compiler cannot merge: after ShadeIdsKernel's grid was compacted
-// (its store no longer behind a row test), clang sank the two stores of ShadeRecord's hit / miss
-// paths into one and dropped `nt` on the way (97 -> 112 us per 8-frame launch of a P = 8
-// compositor; a branch-free ShadeRecord kept `nt` but shaded every miss: 104 us).
-__device__ __forceinline__ void StoreNontemporal(F4* at, F4 v) {
-    asm volatile("global_store_dwordx4 %0, %1, off nt" ::"v"(at), "v"(v) : "memory");
-}
 __device__ __forceinline__ void StoreRgba(const TraceParams& p, int x, int y, const float4& v) {
     const size_t rgba_at = p.out_frame_rows != 0
                                ? static_cast<size_t>(FrameRow(p.row_begin, p.row_interleave, y)) * p.width + x
@@ -697,12 +529,6 @@ constexpr int kShadeThreads = SRT_SHADE_THREADS;
 #define SRT_SHADE_ROWS 4
 #endif
 constexpr int kShadeRows = SRT_SHADE_ROWS;
-
-// (t, id) packed so that unsigned order is lexicographic order: t >= 0 here (vol > 0,
-// det > 0), so its bit pattern orders like the value.
-__device__ __forceinline__ unsigned long long HitKey(float t, int id) {
-    return (static_cast<unsigned long long>(__float_as_uint(t)) << 32) | static_cast<unsigned>(id);
-}
 
 // Quotient of small unsigned integers, exact for y < 2^21 and any d >= 1: |fl(y + 1/2) * rcp(d) - (y +
 // 1/2) / d| <= (y + 1/2) / d * 1.5 * 2^-23 (v_rcp_f32 within 1 ulp, one rounding of the product), below
@@ -866,579 +692,6 @@ __global__ __launch_bounds__(kShadeThreads) void ShadeIdsKernel(TraceParams p, c
             StoreNontemporal(reinterpret_cast<F4*>(p.out + g * pixels + static_cast<size_t>(y) * p.width + x),
                              F4{v.x, v.y, v.z, v.w});
         }
-    }
-}
-
-// ---------------------------------------------------------------------------------------
-// G-buffer (render.h LaunchGBuffer; DESIGN.md section 5 "G-buffer"): the surface attributes of
-// (position, hit id) pairs -- ShadeIdsKernel's deferred pass with more outputs. POINTS: element k's
-// position is read from `where`; else element (x, y) is pixel (x, row_begin + y) of the frame and its
-// position is ray generation's expression of its sample offset (as ShadeIdsKernel). The elements
-// form rows of `width` (points: one row of count); a block takes kGBufferThreads * PPT consecutive
-// elements of one row, a thread PPT of them kGBufferThreads apart, so every wave instruction loads
-// and stores consecutive elements. Three phases with no control flow that depends on loaded data
-// between the loads: (1) every element's id and position, (2) every element's gather -- the
-// triangle's 9 vertex floats (skipped when neither depth nor bary is asked for) and its shading
-// table row (skipped without normal and albedo), an id outside the scene gathers triangle 0's,
-// unused --, (3) the arithmetic (ComputeEdges + gbuffer_math.h) and the nontemporal stores of the
-// planes asked for (uniform branches). No LDS, no atomics, no scratch.
-// Elements per thread, measured at C3 (1 / 2 / 4 / 8: DESIGN.md; profiles/gbuffer/): a launch that
-// needs one of the two gathers is fastest with 4 (depth only 23.1 / 18.9 / 15.4 / 17.7 us), one that
-// needs both with 8 (all planes 35.8 / 35.0 / 33.3 / 28.8 us: 184 VGPRs, two waves per SIMD, and
-// twice the loads in flight per wave). SRT_GBUFFER_PIXELS, SRT_GBUFFER_PIXELS_BOTH: measurement builds.
-// ---------------------------------------------------------------------------------------
-#ifndef SRT_GBUFFER_PIXELS
-#define SRT_GBUFFER_PIXELS 4
-#endif
-#ifndef SRT_GBUFFER_PIXELS_BOTH
-#define SRT_GBUFFER_PIXELS_BOTH 8
-#endif
-constexpr int kGBufferPixels = SRT_GBUFFER_PIXELS;           // elements per thread, one gather
-constexpr int kGBufferPixelsBoth = SRT_GBUFFER_PIXELS_BOTH;  // ... both gathers
-constexpr int kGBufferThreads = 256;
-typedef float F2 __attribute__((ext_vector_type(2)));
-struct GBufferParams {
-    const float* __restrict__ vertices;
-    const float4* __restrict__ shade;
-    const float2* __restrict__ where;  // positions (POINTS) or sample offsets
-    const int* __restrict__ ids;
-    float* __restrict__ depth;
-    F2* __restrict__ bary;
-    F4* __restrict__ normal;
-    F4* __restrict__ albedo;
-    unsigned n;
-    unsigned width;   // elements per row
-    unsigned chunks;  // blocks per row
-    unsigned row_begin;
-    float wf, hf;
-    float eye[3], base[3], du[3], dv[3], bg[3];
-};
-
-template <bool POINTS, int PPT>
-__global__ __launch_bounds__(kGBufferThreads) void GBufferKernel(const GBufferParams q) {
-    const unsigned row = POINTS ? 0u : blockIdx.x / q.chunks;  // (uniform: scalar)
-    const unsigned chunk = blockIdx.x - row * q.chunks;
-    const unsigned x0 = chunk * (kGBufferThreads * PPT) + threadIdx.x;
-    const size_t row_at = static_cast<size_t>(row) * q.width;
-    const bool edges = q.depth != nullptr || q.bary != nullptr;
-    const bool table = q.normal != nullptr || q.albedo != nullptr;
-    // (1) An element past the row loads the row's last one and is not stored.
-    int code[PPT];
-    float2 w[PPT];
-#pragma unroll
-    for (int k = 0; k < PPT; ++k) {
-        const unsigned x = min(x0 + k * kGBufferThreads, q.width - 1u);
-        code[k] = __builtin_nontemporal_load(q.ids + row_at + x);
-        w[k] = q.where[row_at + x];
-    }
-    // (2)
-    int hit[PPT];
-    float v[PPT][9];
-    float4 nr[PPT], al[PPT];
-#pragma unroll
-    for (int k = 0; k < PPT; ++k) {
-        hit[k] = static_cast<unsigned>(code[k]) < q.n ? code[k] : -1;
-#pragma unroll
-        for (int j = 0; j < 9; ++j) {
-            v[k][j] = 0.f;
-        }
-        nr[k] = al[k] = float4{};
-    }
-    if (q.n != 0u) {  // (an empty scene has no triangle 0)
-        if (edges) {
-#pragma unroll
-            for (int k = 0; k < PPT; ++k) {
-                const float* at = q.vertices + 9ull * static_cast<unsigned>(max(hit[k], 0));
-#pragma unroll
-                for (int j = 0; j < 9; ++j) {
-                    v[k][j] = at[j];
-                }
-            }
-        }
-        if (table) {
-#pragma unroll
-            for (int k = 0; k < PPT; ++k) {
-                const float4* sr = q.shade + 2ull * static_cast<unsigned>(max(hit[k], 0));
-                nr[k] = sr[0];
-                al[k] = sr[1];
-            }
-        }
-    }
-    // (3)
-#pragma unroll
-    for (int k = 0; k < PPT; ++k) {
-        const unsigned x = x0 + k * kGBufferThreads;
-        if (x >= q.width) {
-            continue;
-        }
-        float fx = w[k].x, fy = w[k].y;
-        if constexpr (!POINTS) {
-            fx = (static_cast<float>(x) + w[k].x) / q.wf;
-            fy = (static_cast<float>(q.row_begin + row) + w[k].y) / q.hf;
-        }
-        GBufferTexel o = GBufferMiss(q.bg);
-        if (hit[k] >= 0) {
-            float c[9], vol;
-            ComputeEdges(q.eye, q.base, q.du, q.dv, v[k], true, c, vol);
-            o = GBufferHit(c, vol, q.base, q.du, q.dv, fx, fy, hit[k], nr[k].x, nr[k].y, nr[k].z, nr[k].w, al[k].x,
-                           al[k].y, al[k].z);
-        }
-        const size_t at = row_at + x;
-        if (q.depth != nullptr) {
-            __builtin_nontemporal_store(o.depth, q.depth + at);
-        }
-        if (q.bary != nullptr) {
-            __builtin_nontemporal_store(F2{o.w1, o.w2}, q.bary + at);
-        }
-        if (q.normal != nullptr) {
-            StoreNontemporal(q.normal + at, F4{o.nx, o.ny, o.nz, o.cosv});
-        }
-        if (q.albedo != nullptr) {
-            StoreNontemporal(q.albedo + at, F4{o.r, o.g, o.b, o.a});
-        }
-    }
-}
-
-// ---------------------------------------------------------------------------------------
-// Vertex attributes (render.h LaunchSurface / LaunchInterpolate; DESIGN.md section 5 "Vertex
-// attributes"): what the surface looks like at (position, hit id) pairs -- GBufferKernel's deferred
-// pass with the caller's per-triangle corner tables interpolated at the hit point and a texture
-// looked up there. Element mapping as GBufferKernel's: a block takes kSurfaceThreads * PPT
-// consecutive elements of one row, a thread PPT of them kSurfaceThreads apart. Four phases with no
-// control flow that depends on loaded data between a phase's loads: (1) every element's id and
-// position, (2) every element's by-id gathers, each behind a uniform branch on what the call
-// needs -- the vertex row (36 B: the weights), the shading table row (32 B: the geometric normal
-// and the scene's albedo), the normals row (36 B), the uvs row (24 B); an id outside the scene
-// gathers triangle 0's, unused --, (3) the weights (ComputeEdges + surface_math.h), the uv and the
-// texel gathers (four float4 taps, one with the nearest filter: the second dependent chain; the
-// taps are in range whatever the uv, surface_math.h), (4) the arithmetic and the nontemporal
-// stores of the planes asked for. No LDS, no atomics, no scratch.
-// Elements per thread, measured at C3 with random tables (1 / 2 / 4: DESIGN.md; profiles/surface/):
-// normal + albedo 50.3 / 49.4 / 50.0 us with a 64 KB texture, 93.1 / 98.9 / 96.2 us with a 16 MB one --
-// the pass is bound by its two dependent round trips, not by chains per wave or waves; 2 keeps 5 waves
-// per SIMD at 94 VGPRs. SRT_SURFACE_PIXELS: measurement builds.
-// ---------------------------------------------------------------------------------------
-#ifndef SRT_SURFACE_PIXELS
-#define SRT_SURFACE_PIXELS 2
-#endif
-constexpr int kSurfacePixels = SRT_SURFACE_PIXELS;
-constexpr int kSurfaceThreads = 256;
-constexpr int kInterpolatePixels = 4;  // (GBufferKernel's figure for one 36 B gather plus one more row)
-struct SurfaceParams {
-    const float* __restrict__ vertices;
-    const float4* __restrict__ shade;
-    const float2* __restrict__ where;  // positions (POINTS) or sample offsets
-    const int* __restrict__ ids;
-    const float* __restrict__ normals;
-    const float* __restrict__ uvs;
-    const float4* __restrict__ texture;
-    F4* __restrict__ normal;
-    F4* __restrict__ albedo;
-    F4* __restrict__ rgba;
-    F2* __restrict__ uv;
-    unsigned n;
-    unsigned width;   // elements per row
-    unsigned chunks;  // blocks per row
-    unsigned row_begin;
-    int tw, th;
-    unsigned flags;
-    float wf, hf;
-    float eye[3], base[3], du[3], dv[3], bg[3];
-};
-
-template <bool POINTS, int PPT>
-__global__ __launch_bounds__(kSurfaceThreads) void SurfaceKernel(const SurfaceParams q) {
-    const unsigned row = POINTS ? 0u : blockIdx.x / q.chunks;  // (uniform: scalar)
-    const unsigned chunk = blockIdx.x - row * q.chunks;
-    const unsigned x0 = chunk * (kSurfaceThreads * PPT) + threadIdx.x;
-    const size_t row_at = static_cast<size_t>(row) * q.width;
-    // What the call needs (uniform).
-    const bool out_n = q.normal != nullptr || q.rgba != nullptr;
-    const bool out_a = q.albedo != nullptr || q.rgba != nullptr;
-    const bool smooth = q.normals != nullptr && out_n;
-    const bool textured = q.texture != nullptr && out_a;
-    const bool modulate = (q.flags & kSurfaceModulate) != 0u;
-    const bool clamp = (q.flags & kSurfaceWrapClamp) != 0u;
-    const bool nearest = (q.flags & kSurfaceFilterNearest) != 0u;
-    const bool coords = q.uvs != nullptr && (q.uv != nullptr || textured);
-    const bool weights = smooth || coords;
-    const bool table = (out_n && !smooth) || (out_a && (!textured || modulate));
-    // (1) An element past the row loads the row's last one and is not stored.
-    int code[PPT];
-    float2 w[PPT];
-#pragma unroll
-    for (int k = 0; k < PPT; ++k) {
-        const unsigned x = min(x0 + k * kSurfaceThreads, q.width - 1u);
-        code[k] = __builtin_nontemporal_load(q.ids + row_at + x);
-        w[k] = q.where[row_at + x];
-    }
-    // (2)
-    int hit[PPT];
-    float v[PPT][9], cn[PPT][9], ct[PPT][6];
-    float4 nr[PPT], al[PPT];
-#pragma unroll
-    for (int k = 0; k < PPT; ++k) {
-        hit[k] = static_cast<unsigned>(code[k]) < q.n ? code[k] : -1;
-#pragma unroll
-        for (int j = 0; j < 9; ++j) {
-            v[k][j] = cn[k][j] = 0.f;
-        }
-#pragma unroll
-        for (int j = 0; j < 6; ++j) {
-            ct[k][j] = 0.f;
-        }
-        nr[k] = al[k] = float4{};
-    }
-    if (q.n != 0u) {  // (an empty scene has no triangle 0)
-        if (weights) {
-#pragma unroll
-            for (int k = 0; k < PPT; ++k) {
-                const float* at = q.vertices + 9ull * static_cast<unsigned>(max(hit[k], 0));
-#pragma unroll
-                for (int j = 0; j < 9; ++j) {
-                    v[k][j] = at[j];
-                }
-            }
-        }
-        if (table) {
-#pragma unroll
-            for (int k = 0; k < PPT; ++k) {
-                const float4* sr = q.shade + 2ull * static_cast<unsigned>(max(hit[k], 0));
-                nr[k] = sr[0];
-                al[k] = sr[1];
-            }
-        }
-        if (smooth) {
-#pragma unroll
-            for (int k = 0; k < PPT; ++k) {
-                const float* at = q.normals + 9ull * static_cast<unsigned>(max(hit[k], 0));
-#pragma unroll
-                for (int j = 0; j < 9; ++j) {
-                    cn[k][j] = at[j];
-                }
-            }
-        }
-        if (coords) {
-#pragma unroll
-            for (int k = 0; k < PPT; ++k) {
-                const float* at = q.uvs + 6ull * static_cast<unsigned>(max(hit[k], 0));
-#pragma unroll
-                for (int j = 0; j < 6; ++j) {
-                    ct[k][j] = at[j];
-                }
-            }
-        }
-    }
-    // (3)
-    float fx[PPT], fy[PPT];
-    SurfaceWeights bw[PPT];
-    float tu[PPT], tv[PPT], ta[PPT], tb[PPT];
-    float4 t00[PPT], t01[PPT], t10[PPT], t11[PPT];
-#pragma unroll
-    for (int k = 0; k < PPT; ++k) {
-        fx[k] = w[k].x;
-        fy[k] = w[k].y;
-        if constexpr (!POINTS) {
-            const unsigned x = min(x0 + k * kSurfaceThreads, q.width - 1u);
-            fx[k] = (static_cast<float>(x) + w[k].x) / q.wf;
-            fy[k] = (static_cast<float>(q.row_begin + row) + w[k].y) / q.hf;
-        }
-        bw[k] = SurfaceWeights{0.f, 0.f, 0.f};
-        if (weights) {
-            float c[9], vol;
-            ComputeEdges(q.eye, q.base, q.du, q.dv, v[k], true, c, vol);
-            bw[k] = SurfaceBary(c, fx[k], fy[k]);
-        }
-        tu[k] = tv[k] = 0.f;  // (without a uvs table: (0, 0))
-        if (coords) {
-            tu[k] = SurfaceMix(bw[k], ct[k][0], ct[k][2], ct[k][4]);
-            tv[k] = SurfaceMix(bw[k], ct[k][1], ct[k][3], ct[k][5]);
-        }
-        ta[k] = tb[k] = 0.f;
-        t00[k] = t01[k] = t10[k] = t11[k] = float4{};
-    }
-    if (textured) {
-        if (nearest) {
-#pragma unroll
-            for (int k = 0; k < PPT; ++k) {
-                const int i = SurfaceNearest(SurfaceWrap(tu[k], clamp), q.tw);
-                const int j = SurfaceNearest(SurfaceWrap(tv[k], clamp), q.th);
-                t00[k] = q.texture[static_cast<size_t>(j) * static_cast<unsigned>(q.tw) + static_cast<unsigned>(i)];
-            }
-        } else {
-#pragma unroll
-            for (int k = 0; k < PPT; ++k) {
-                const SurfaceTaps sx = SurfaceBilinear(SurfaceWrap(tu[k], clamp), q.tw, clamp);
-                const SurfaceTaps sy = SurfaceBilinear(SurfaceWrap(tv[k], clamp), q.th, clamp);
-                const float4* top = q.texture + static_cast<size_t>(sy.i0) * static_cast<unsigned>(q.tw);
-                const float4* bot = q.texture + static_cast<size_t>(sy.i1) * static_cast<unsigned>(q.tw);
-                t00[k] = top[sx.i0];
-                t01[k] = top[sx.i1];
-                t10[k] = bot[sx.i0];
-                t11[k] = bot[sx.i1];
-                ta[k] = sx.a;
-                tb[k] = sy.a;
-            }
-        }
-    }
-    // (4)
-#pragma unroll
-    for (int k = 0; k < PPT; ++k) {
-        const unsigned x = x0 + k * kSurfaceThreads;
-        if (x >= q.width) {
-            continue;
-        }
-        F4 on{0.f, 0.f, 0.f, 1.f}, oa{q.bg[0], q.bg[1], q.bg[2], -1.f};
-        F2 ouv{0.f, 0.f};
-        if (hit[k] >= 0) {
-            if (smooth) {
-                const SurfaceNormal s = SurfaceSmoothNormal(
-                    SurfaceMix(bw[k], cn[k][0], cn[k][3], cn[k][6]), SurfaceMix(bw[k], cn[k][1], cn[k][4], cn[k][7]),
-                    SurfaceMix(bw[k], cn[k][2], cn[k][5], cn[k][8]), q.base, q.du, q.dv, fx[k], fy[k]);
-                on = F4{s.x, s.y, s.z, s.cosv};
-            } else {
-                const float none[9] = {};  // (the geometric normal needs no edge record)
-                const GBufferTexel g = GBufferHit(none, 0.f, q.base, q.du, q.dv, fx[k], fy[k], hit[k], nr[k].x, nr[k].y,
-                                                  nr[k].z, nr[k].w, al[k].x, al[k].y, al[k].z);
-                on = F4{g.nx, g.ny, g.nz, g.cosv};
-            }
-            float r = al[k].x, g = al[k].y, b = al[k].z;
-            if (textured) {
-                float tr = t00[k].x, tg = t00[k].y, tbl = t00[k].z;
-                if (!nearest) {
-                    tr = SurfaceLerp(SurfaceLerp(t00[k].x, t01[k].x, ta[k]), SurfaceLerp(t10[k].x, t11[k].x, ta[k]), tb[k]);
-                    tg = SurfaceLerp(SurfaceLerp(t00[k].y, t01[k].y, ta[k]), SurfaceLerp(t10[k].y, t11[k].y, ta[k]), tb[k]);
-                    tbl = SurfaceLerp(SurfaceLerp(t00[k].z, t01[k].z, ta[k]), SurfaceLerp(t10[k].z, t11[k].z, ta[k]), tb[k]);
-                }
-                r = modulate ? tr * r : tr;
-                g = modulate ? tg * g : tg;
-                b = modulate ? tbl * b : tbl;
-            }
-            oa = F4{r, g, b, static_cast<float>(hit[k])};
-            ouv = F2{tu[k], tv[k]};
-        }
-        const size_t at = row_at + x;
-        if (q.normal != nullptr) {
-            StoreNontemporal(q.normal + at, on);
-        }
-        if (q.albedo != nullptr) {
-            StoreNontemporal(q.albedo + at, oa);
-        }
-        if (q.rgba != nullptr) {
-            StoreNontemporal(q.rgba + at, F4{oa.x * on.w, oa.y * on.w, oa.z * on.w, oa.w});
-        }
-        if (q.uv != nullptr) {
-            __builtin_nontemporal_store(ouv, q.uv + at);
-        }
-    }
-}
-
-// The interpolation of one corner table of C floats per corner: SurfaceKernel's phases (1), (2)
-// with the vertex row and the table's row (12 C bytes), and the weights and the mix.
-struct InterpolateParams {
-    const float* __restrict__ vertices;
-    const float2* __restrict__ where;
-    const int* __restrict__ ids;
-    const float* __restrict__ table;
-    float* __restrict__ out;
-    unsigned n;
-    unsigned width;
-    unsigned chunks;
-    unsigned row_begin;
-    float wf, hf;
-    float eye[3], base[3], du[3], dv[3];
-};
-
-template <bool POINTS, int C>
-__global__ __launch_bounds__(kSurfaceThreads) void InterpolateKernel(const InterpolateParams q) {
-    constexpr int PPT = kInterpolatePixels;
-    const unsigned row = POINTS ? 0u : blockIdx.x / q.chunks;  // (uniform: scalar)
-    const unsigned chunk = blockIdx.x - row * q.chunks;
-    const unsigned x0 = chunk * (kSurfaceThreads * PPT) + threadIdx.x;
-    const size_t row_at = static_cast<size_t>(row) * q.width;
-    int code[PPT];
-    float2 w[PPT];
-#pragma unroll
-    for (int k = 0; k < PPT; ++k) {
-        const unsigned x = min(x0 + k * kSurfaceThreads, q.width - 1u);
-        code[k] = __builtin_nontemporal_load(q.ids + row_at + x);
-        w[k] = q.where[row_at + x];
-    }
-    int hit[PPT];
-    float v[PPT][9], a[PPT][3 * C];
-#pragma unroll
-    for (int k = 0; k < PPT; ++k) {
-        hit[k] = static_cast<unsigned>(code[k]) < q.n ? code[k] : -1;
-#pragma unroll
-        for (int j = 0; j < 9; ++j) {
-            v[k][j] = 0.f;
-        }
-#pragma unroll
-        for (int j = 0; j < 3 * C; ++j) {
-            a[k][j] = 0.f;
-        }
-    }
-    if (q.n != 0u) {
-#pragma unroll
-        for (int k = 0; k < PPT; ++k) {
-            const float* at = q.vertices + 9ull * static_cast<unsigned>(max(hit[k], 0));
-            const float* ta = q.table + static_cast<size_t>(3 * C) * static_cast<unsigned>(max(hit[k], 0));
-#pragma unroll
-            for (int j = 0; j < 9; ++j) {
-                v[k][j] = at[j];
-            }
-#pragma unroll
-            for (int j = 0; j < 3 * C; ++j) {
-                a[k][j] = ta[j];
-            }
-        }
-    }
-#pragma unroll
-    for (int k = 0; k < PPT; ++k) {
-        const unsigned x = x0 + k * kSurfaceThreads;
-        if (x >= q.width) {
-            continue;
-        }
-        float fx = w[k].x, fy = w[k].y;
-        if constexpr (!POINTS) {
-            fx = (static_cast<float>(x) + w[k].x) / q.wf;
-            fy = (static_cast<float>(q.row_begin + row) + w[k].y) / q.hf;
-        }
-        float o[C];
-#pragma unroll
-        for (int c = 0; c < C; ++c) {
-            o[c] = 0.f;
-        }
-        if (hit[k] >= 0) {
-            float e[9], vol;
-            ComputeEdges(q.eye, q.base, q.du, q.dv, v[k], true, e, vol);
-            const SurfaceWeights bw = SurfaceBary(e, fx, fy);
-#pragma unroll
-            for (int c = 0; c < C; ++c) {
-                o[c] = SurfaceMix(bw, a[k][c], a[k][C + c], a[k][2 * C + c]);
-            }
-        }
-        float* at = q.out + (row_at + x) * C;
-        if constexpr (C == 4) {
-            StoreNontemporal(reinterpret_cast<F4*>(at), F4{o[0], o[1], o[2], o[3]});
-        } else if constexpr (C == 2) {
-            __builtin_nontemporal_store(F2{o[0], o[1]}, reinterpret_cast<F2*>(at));
-        } else {
-#pragma unroll
-            for (int c = 0; c < C; ++c) {
-                __builtin_nontemporal_store(o[c], at + c);
-            }
-        }
-    }
-}
-
-// ---------------------------------------------------------------------------------------
-// Resolve (render.h LaunchResolve; DESIGN.md section 5 "Multi-sample frames"): one RGBA pixel from
-// S sample planes -- S hit ids and S sample offsets per pixel in, the mean of the S shaded samples
-// and the coverage out (samples_math.h), instead of S RGBA frames written, read back and averaged.
-// The 2 x kMaxSamples plane pointers are kernel arguments. Element mapping as GBufferKernel's: a
-// block takes kResolveThreads consecutive pixels of one band row, a thread one pixel, so every wave
-// instruction loads consecutive ids and offsets and stores consecutive pixels. The samples are
-// taken in groups of G, each group in three phases with no control flow that depends on loaded data
-// between its loads: (1) the group's ids and offsets, (2) the group's shading table rows (an id
-// outside the scene gathers row 0, unused), (3) the arithmetic, strictly in ascending s. A thread
-// has G dependent chains (id -> table row) in flight. The samples that do not fill a group of G are
-// taken in groups of G / 2, G / 4, ... 1 (S = 9, G = 8: a group of 8 and one of 1; loading a padded
-// last group's planes twice cost S = 1 at G = 4 27.0 us against 19.4 at G = 1). No LDS, no atomics,
-// no scratch.
-// G, measured at C3 (1 / 2 / 4 / 8: DESIGN.md; profiles/samples/): 8 is fastest from S = 8 on (S = 8
-// 68.5 / 59.2 / 55.9 / 52.8 us, S = 16 128.0 / 106.9 / 103.2 / 99.4 us: 106 VGPRs, four waves per SIMD,
-// twice the loads in flight per wave), 4 below it (S = 4 40.7 / 35.9 / 33.4 / 36.5 us: 62 VGPRs, eight
-// waves, and no group of 8 to fill). SRT_RESOLVE_GROUP, SRT_RESOLVE_GROUP_LONG: measurement builds.
-// ---------------------------------------------------------------------------------------
-#ifndef SRT_RESOLVE_GROUP
-#define SRT_RESOLVE_GROUP 4
-#endif
-#ifndef SRT_RESOLVE_GROUP_LONG
-#define SRT_RESOLVE_GROUP_LONG 8
-#endif
-constexpr int kResolveGroup = SRT_RESOLVE_GROUP;           // samples per group, S < kResolveLong
-constexpr int kResolveGroupLong = SRT_RESOLVE_GROUP_LONG;  // ... S >= kResolveLong
-constexpr unsigned kResolveLong = 8;
-constexpr int kResolveThreads = 256;
-static_assert(kResolveGroup >= 1 && (kResolveGroup & (kResolveGroup - 1)) == 0 && kResolveGroupLong >= 1 &&
-                  (kResolveGroupLong & (kResolveGroupLong - 1)) == 0,
-              "groups halve down to 1");
-struct ResolveParams {
-    const float2* offsets[kMaxSamples];
-    const int* ids[kMaxSamples];
-    const float4* __restrict__ shade;
-    F4* __restrict__ out;
-    unsigned n;
-    unsigned samples;
-    unsigned width;
-    unsigned chunks;  // blocks per row
-    unsigned row_begin;
-    float wf, hf;
-    float base[3], du[3], dv[3], bg[3];
-};
-
-// The samples [s0, ...) of pixel (x, y) (its planes' element `at`) join acc in groups of G while G
-// of them are left, then in groups of G / 2, ... 1; s0 ends at q.samples.
-template <int G>
-__device__ __forceinline__ void ResolveGroups(const ResolveParams& q, size_t at, unsigned x, unsigned y, unsigned& s0,
-                                              ResolveAcc& acc) {
-    for (; s0 + G <= q.samples; s0 += G) {  // (uniform)
-        // (1)
-        int code[G];
-        float2 o[G];
-#pragma unroll
-        for (int k = 0; k < G; ++k) {
-            code[k] = __builtin_nontemporal_load(q.ids[s0 + k] + at);
-            o[k] = q.offsets[s0 + k][at];
-        }
-        // (2)
-        int hit[G];
-        float4 nr[G], al[G];
-#pragma unroll
-        for (int k = 0; k < G; ++k) {
-            hit[k] = static_cast<unsigned>(code[k]) < q.n ? code[k] : -1;
-            nr[k] = al[k] = float4{};
-        }
-        if (q.n != 0u) {  // (an empty scene has no row 0)
-#pragma unroll
-            for (int k = 0; k < G; ++k) {
-                const float4* sr = q.shade + 2ull * static_cast<unsigned>(max(hit[k], 0));
-                nr[k] = sr[0];
-                al[k] = sr[1];
-            }
-        }
-        // (3)
-#pragma unroll
-        for (int k = 0; k < G; ++k) {
-            ResolveRgb c{q.bg[0], q.bg[1], q.bg[2]};
-            if (hit[k] >= 0) {
-                float fx, fy;
-                ResolvePosition(x, y, o[k].x, o[k].y, q.wf, q.hf, fx, fy);
-                c = ResolveShadeHit(q.base, q.du, q.dv, fx, fy, nr[k].x, nr[k].y, nr[k].z, nr[k].w, al[k].x, al[k].y,
-                                    al[k].z);
-            }
-            ResolveAdd(acc, s0 + k, c, hit[k] >= 0);
-        }
-    }
-    if constexpr (G > 1) {
-        ResolveGroups<G / 2>(q, at, x, y, s0, acc);
-    }
-}
-
-template <int G>
-__global__ __launch_bounds__(kResolveThreads) void ResolveKernel(const ResolveParams q) {
-    const unsigned row = blockIdx.x / q.chunks;  // (uniform: scalar)
-    const unsigned chunk = blockIdx.x - row * q.chunks;
-    const unsigned x = chunk * kResolveThreads + threadIdx.x;
-    // A pixel past the row loads the row's last one and is not stored.
-    const size_t at = static_cast<size_t>(row) * q.width + min(x, q.width - 1u);
-    ResolveAcc acc{};
-    unsigned s0 = 0;
-    ResolveGroups<G>(q, at, x, q.row_begin + row, s0, acc);
-    if (x < q.width) {
-        const ResolveTexel t = ResolveFinish(acc, q.samples);
-        __builtin_nontemporal_store(F4{t.r, t.g, t.b, t.a}, q.out + at);
     }
 }
 
@@ -1634,86 +887,9 @@ __device__ __forceinline__ bool QBoxOverlaps(const QBox& b, unsigned qx, unsigne
     return ((__builtin_bit_cast(unsigned, sx) | __builtin_bit_cast(unsigned, sy)) & 0x80008000u) == 0u;
 }
 
-// Exact test of one record against every ray of the lane (records in any order): the
-// lexicographic minimum of (t, id) equals the ascending-id strict-< result of TestTriangle
-// (smallest t; among equal t the lowest id).
-template <int R, bool SHARED>
-__device__ __forceinline__ void ExactTestAnyOrder(Rays<R>& s, const Record& q, float vol, int id) {
-    float gA[R], gB[R], gC[R];
-    if constexpr (SHARED) {
-        const float a = fmaf(s.fx[0], q.cxA, q.c0A), b = fmaf(s.fx[0], q.cxB, q.c0B),
-                    c = fmaf(s.fx[0], q.cxC, q.c0C);
-#pragma unroll
-        for (int r = 0; r < R; ++r) {
-            gA[r] = a;
-            gB[r] = b;
-            gC[r] = c;
-        }
-    } else {
-#pragma unroll
-        for (int r = 0; r < R; ++r) {
-            gA[r] = fmaf(s.fx[r], q.cxA, q.c0A);
-            gB[r] = fmaf(s.fx[r], q.cxB, q.c0B);
-            gC[r] = fmaf(s.fx[r], q.cxC, q.c0C);
-        }
-    }
-    float e[R][3];
-    float m[R];
-#pragma unroll
-    for (int r = 0; r < R; ++r) {
-        e[r][0] = fmaf(s.fy[r], q.cyA, gA[r]);
-        e[r][1] = fmaf(s.fy[r], q.cyB, gB[r]);
-        e[r][2] = fmaf(s.fy[r], q.cyC, gC[r]);
-        m[r] = fminf(fminf(e[r][0], e[r][1]), e[r][2]);
-    }
-    float mm = m[0];
-#pragma unroll
-    for (int r = 1; r < R; ++r) {
-        mm = fmaxf(mm, m[r]);
-    }
-    if (mm >= 0.f) {
-#pragma unroll
-        for (int r = 0; r < R; ++r) {
-            if (e[r][0] >= 0.f && e[r][1] >= 0.f && e[r][2] >= 0.f) {
-                const float det = (e[r][0] + e[r][1]) + e[r][2];
-                if (det > 0.f) {
-                    const float t = vol / det;
-                    if (t < s.bt[r] || (t == s.bt[r] && id < s.bi[r])) {
-                        s.bt[r] = t;
-                        s.bi[r] = id;
-                    }
-                }
-            }
-        }
-    }
-}
-
-// The exact test of one record at one position as "passes, t" (the id is the caller's): the test
-// ExactTestAnyOrder<1, false> makes before it compares with its running minimum -- the same fmaf
-// chain, conditions and division, so the same bits -- for a kernel that keeps more than a minimum
-// (LayersKernel). A hit with t = +inf or NaN does not pass: the traces' strict < from +inf never
-// takes one either. Stated beside ExactTestAnyOrder rather than inside it, on measurement (DESIGN.md
-// section 5 "Depth layers"): calling a shared "passes, t" piece from ExactTestAnyOrder's loop body
-// changed the scalar register allocation of QueryKernel and ShadowKernel, and running
-// ExactTestAnyOrder from an empty state here cost LayersKernel 8 to 20 %.
-__device__ __forceinline__ bool ExactTestOne(float fx, float fy, const Record& q, float vol, float& t) {
-    const float e0 = fmaf(fy, q.cyA, fmaf(fx, q.cxA, q.c0A));
-    const float e1 = fmaf(fy, q.cyB, fmaf(fx, q.cxB, q.c0B));
-    const float e2 = fmaf(fy, q.cyC, fmaf(fx, q.cxC, q.c0C));
-    if (e0 >= 0.f && e1 >= 0.f && e2 >= 0.f) {
-        const float det = (e0 + e1) + e2;
-        if (det > 0.f) {
-            t = vol / det;
-            return t < __builtin_inff();
-        }
-    }
-    return false;
-}
-
 // Cull tile = 64 columns x kTileRows rows of rays (the bins); trace block = one part of it,
 // 64 columns x kBlockRows rows: kCullWaves waves, each 64 columns x kCullR rows (lane =
 // column).
-constexpr int kTileRows = kCullTileRows;
 #ifndef SRT_BLOCK_ROWS
 #define SRT_BLOCK_ROWS 16
 #endif
@@ -1788,7 +964,6 @@ static_assert(sizeof(CullSharedT<false>) + sizeof(float2) * kBlockRows * kWave =
 static_assert(sizeof(float2) * kWave * kCullWaves <= sizeof(float4) * 2 * kPacketBatch, "PacketTables scratch");
 static_assert((kPacketBatch + kStreamStep) * 4 <= sizeof(float4) * 3 * kPacketBatch, "stream ids alias the planes");
 constexpr int kFlushBatches = (kPacketBatch + kStreamStep - 1 + kPacketBatch - 1) / kPacketBatch;  // per flush
-
 
 // Candidate source of a block: LIST = positions [begin, end) of the tile's virtual list (its
 // bin list, then the large list of records binned to every tile); FULL = every record.
@@ -3262,50 +2437,6 @@ std::size_t OrderLdsBytes(int tiles) { return static_cast<std::size_t>(tiles) * 
 #define SRT_TRACE_OCC 6
 #endif
 
-// Where a trace block's candidate records come from. RC = false: the 64-B cull record by position
-// (written by the record pass: LaunchPrepare, or the bin kernel of a stored-record launch).
-// RC = true (a binned launch with CullBins::recompute): the bin kernel writes only the screen box
-// by position, and the trace recomputes the edge coefficients and vol from the vertices by position
-// with the record pass's own ComputeEdges under the same frame vectors -- the same bits -- and
-// takes the id from the spatial order (a padding position is its own id, >= n: a disabled record).
-struct RawRecord {
-    float v[9];
-    unsigned id;
-    float4 sb;
-};
-template <bool RC>
-struct TraceRecords {
-    using Raw = CullRecord;
-    static __device__ __forceinline__ Raw Load(const TraceParams& p, unsigned pos) { return p.cull[pos]; }
-    static __device__ __forceinline__ CullRecord Make(const TraceParams&, const Raw& r) { return r; }
-};
-template <>
-struct TraceRecords<true> {
-    using Raw = RawRecord;
-    static __device__ __forceinline__ Raw Load(const TraceParams& p, unsigned pos) {
-        Raw r;
-        const bool real = pos < p.n;
-        const float4* v = reinterpret_cast<const float4*>(p.svertices + static_cast<size_t>(kSpatialStride) * (real ? pos : 0u));
-        const float4 v0 = v[0], v1 = v[1], v2 = v[2];
-        r.v[0] = v0.x, r.v[1] = v0.y, r.v[2] = v0.z, r.v[3] = v0.w;
-        r.v[4] = v1.x, r.v[5] = v1.y, r.v[6] = v1.z, r.v[7] = v1.w;
-        r.v[8] = v2.x;
-        r.id = real ? __float_as_uint(v2.y) : pos;
-        r.sb = p.screen_boxes[pos];
-        return r;
-    }
-    static __device__ __forceinline__ CullRecord Make(const TraceParams& p, const Raw& r) {
-        float c[9], vol;
-        ComputeEdges(p.eye, p.base, p.du, p.dv, r.v, r.id < p.n, c, vol);
-        CullRecord cr;
-        cr.a = make_float4(c[0], c[1], c[2], c[3]);
-        cr.b = make_float4(c[4], c[5], c[6], c[7]);
-        cr.x = make_float4(c[8], vol, __uint_as_float(r.id), 0.f);
-        cr.sb = r.sb;
-        return cr;
-    }
-};
-
 // SHARED: the frame runs on the scene's shared setup (render.h CullSetup): p.work is the setup's
 // plan, whose descriptors hold the tile's candidate count, list length, chunking, and the FULL
 // (unusable analytic box, overflowed list) and empty flags; p.bin_lists, p.large_list and the
@@ -4077,403 +3208,6 @@ __global__ __launch_bounds__(kCullThreads, kTraceOcc<Frames>) void TraceCullKern
     }
 #endif
 #undef SRT_DIAG_END
-}
-
-// ---------------------------------------------------------------------------------------
-// The candidate walk (DESIGN.md section 5 "Point queries"): every record that can pass the exact
-// test at one position of a prepared frame, visited by the LANES lanes that share the position.
-// The query, layers, shadow, omni-shadow and lighting kernels all answer "what does this position
-// see" with it, so their exactness rests on this one argument.
-// The setup's lists were binned against the analytic tile boxes, and that binning is about boxes,
-// not pixel grids: BoxMayHit bounds the edge functions at every (fx, fy) of the box, and a record's
-// screen box contains every position with |fx|, |fy| <= kScreenBoxRange at which its float test can
-// pass. So a position inside a usable tile box passes the exact test of no record outside that
-// tile's list and the large list (listed: entries [0, cnt) of the tile's list, then the large
-// list's). A position outside [0, 1]^2 (NaN included), a tile whose list overflowed or whose box is
-// not ScreenBoxUsable, and a frame without a setup (tile_info null) stream every record instead:
-// positions [0, stream_end), pad records included (disabled: they pass nowhere).
-// FindCandidates serves TraceParams and LightFrame through their common field names and copies each
-// field it uses into a local once: a frame selected per lane is read with vector loads from the
-// argument segment, a uniform one with scalar loads.
-// WalkCandidates: the lanes stride the candidates (a coalesced 4-B entry load, then each lane
-// gathers its record), AHEAD candidates per lane and round, so a round has that many dependent
-// load pairs in flight: AHEAD entries, AHEAD record loads, AHEAD tests. A lane past the end repeats
-// the last candidate (no divergent tail), so `test` must be idempotent: a (t, id) minimum and
-// KeyList::Insert are. stop() is evaluated once per round, by every lane of the group alike;
-// returns whether it ended the walk.
-// ---------------------------------------------------------------------------------------
-struct Candidates {
-    const unsigned* list;        // the tile's list
-    const unsigned* large_list;
-    unsigned cnt;                // entries of the tile's list
-    unsigned total;              // candidates: cnt + the large list's entries, or stream_end
-    bool listed;                 // from the lists; else streamed
-    __device__ __forceinline__ unsigned Entry(unsigned k) const {
-        if (!listed) {
-            return k;
-        }
-        const unsigned* at = k < cnt ? list + k : large_list + (k - cnt);
-        return *at;
-    }
-};
-
-template <class F>
-__device__ __forceinline__ Candidates FindCandidates(const F& f, int tiles_y, unsigned stream_end, float fx, float fy) {
-    Candidates c{nullptr, nullptr, 0u, stream_end, false};
-    int col = 0, row = 0;
-    const TileInfo* tile_info = f.tile_info;
-    const int tiles_x = f.tiles_x;
-    if (tile_info != nullptr && TileOfPosition(fx, fy, f.wf, f.hf, kCullTileCols, kTileRows, tiles_x, tiles_y, col, row)) {
-        const unsigned tile = static_cast<unsigned>(row) * static_cast<unsigned>(tiles_x) + static_cast<unsigned>(col);
-        const unsigned* counts = f.bin_counts;
-        const unsigned capacity = f.bin_capacity;
-        c.cnt = counts[tile];
-        const unsigned large = counts[f.tiles];
-        c.list = f.bin_lists + static_cast<size_t>(tile) * capacity;
-        c.large_list = f.large_list;
-        c.listed = c.cnt <= capacity && tile_info[tile].usable != 0u;
-        c.total = c.listed ? c.cnt + large : stream_end;
-    }
-    return c;
-}
-
-template <int LANES, int AHEAD, class Raw, class Load, class Test, class Stop>
-__device__ __forceinline__ bool WalkCandidates(const Candidates& c, unsigned lane, Load load, Test test, Stop stop) {
-    for (unsigned base = 0u; base < c.total; base += AHEAD * LANES) {
-        unsigned pos[AHEAD];
-        Raw raw[AHEAD];
-#pragma unroll
-        for (int a = 0; a < AHEAD; ++a) {
-            pos[a] = c.Entry(min(base + a * LANES + lane, c.total - 1u));
-        }
-#pragma unroll
-        for (int a = 0; a < AHEAD; ++a) {
-            raw[a] = load(pos[a]);
-        }
-#pragma unroll
-        for (int a = 0; a < AHEAD; ++a) {
-            test(raw[a]);
-        }
-        if (stop()) {
-            return true;
-        }
-    }
-    return false;
-}
-
-// ---------------------------------------------------------------------------------------
-// Point queries (render.h LaunchQuery; DESIGN.md section 5 "Point queries"): the closest hit at
-// arbitrary image positions of the prepared frame, answered from the shared setup's lists by the
-// candidate walk above.
-// A group of kQueryLanes lanes per query runs the trace kernels' exact test on the candidates
-// (ExactTestAnyOrder, one ray) and reduces the (t, id) key with shuffles -- no LDS, no atomics, no
-// cross-block traffic; a repeated last candidate changes no minimum. The kernel is bound by the
-// latency of its chain of dependent loads (position -> tile counts -> list entries -> records), not
-// by bandwidth or VALU, so fewer, fuller waves win: 16 lanes x 2 candidates measured best of
-// 64 / 32 / 16 / 8 lanes and 1 / 2 / 4 candidates at C3 (profiles/query/).
-// SRT_QUERY_LANES, SRT_QUERY_AHEAD: measurement builds.
-// ---------------------------------------------------------------------------------------
-#ifndef SRT_QUERY_LANES
-#define SRT_QUERY_LANES 16
-#endif
-constexpr int kQueryLanes = SRT_QUERY_LANES;  // lanes per query (a divisor of the wave)
-#ifndef SRT_QUERY_AHEAD
-#define SRT_QUERY_AHEAD 2
-#endif
-constexpr int kQueryAhead = SRT_QUERY_AHEAD;  // candidates per lane and round
-constexpr int kQueryThreads = 256;
-constexpr int kQueryBlock = kQueryThreads / kQueryLanes;  // queries per block
-static_assert(kQueryLanes >= 2 && kWave % kQueryLanes == 0, "a query's lanes share a wave");
-struct QueryParams {
-    TraceParams rec;  // the records (TraceRecords), the frame vectors, the setup's tiles, lists and counts
-    const float2* __restrict__ positions;
-    int* __restrict__ ids;
-    float* __restrict__ t;
-    unsigned char* __restrict__ how;  // null: not stored
-    unsigned count;
-    unsigned stream_end;  // records of a streamed query: positions [0, stream_end)
-    int tiles_y;
-};
-
-template <bool RC>
-__global__ __launch_bounds__(kQueryThreads) void QueryKernel(const QueryParams q) {
-    const TraceParams& p = q.rec;
-    using Recs = TraceRecords<RC>;
-    const unsigned lane = threadIdx.x & (kQueryLanes - 1);
-    unsigned group = threadIdx.x / kQueryLanes;
-    if constexpr (kQueryLanes == kWave) {  // wave-uniform: the query's facts load through the scalar cache
-        group = static_cast<unsigned>(__builtin_amdgcn_readfirstlane(static_cast<int>(group)));
-    }
-    const unsigned query = blockIdx.x * kQueryBlock + group;
-    if (query >= q.count) {
-        return;
-    }
-    const float2 f = q.positions[query];
-    Rays<1> s;
-    s.fx[0] = f.x;
-    s.fy[0] = f.y;
-    s.bt[0] = __builtin_inff();
-    s.bi[0] = -1;
-    const Candidates cand = FindCandidates(p, q.tiles_y, q.stream_end, f.x, f.y);
-    auto test = [&](const typename Recs::Raw& raw) {
-        const CullRecord r = Recs::Make(p, raw);
-        const Record rec{r.a.x, r.a.y, r.a.z, r.a.w, r.b.x, r.b.y, r.b.z, r.b.w, r.x.x};
-        ExactTestAnyOrder<1, false>(s, rec, r.x.y, static_cast<int>(__float_as_uint(r.x.z)));
-    };
-    WalkCandidates<kQueryLanes, kQueryAhead, typename Recs::Raw>(
-        cand, lane, [&](unsigned pos) { return Recs::Load(p, pos); }, test, [] { return false; });
-    // The lanes' (t, id) minimum; a miss is (+inf, -1), above every hit's key (a hit's t < +inf).
-    unsigned long long key = HitKey(s.bt[0], s.bi[0]);
-#pragma unroll
-    for (int o = 1; o < kQueryLanes; o <<= 1) {
-        const unsigned lo = static_cast<unsigned>(__shfl_xor(static_cast<int>(key), o));
-        const unsigned hi = static_cast<unsigned>(__shfl_xor(static_cast<int>(key >> 32), o));
-        const unsigned long long other = static_cast<unsigned long long>(hi) << 32 | lo;
-        key = other < key ? other : key;
-    }
-    if (lane == 0u) {
-        q.ids[query] = static_cast<int>(static_cast<unsigned>(key));
-        q.t[query] = __uint_as_float(static_cast<unsigned>(key >> 32));
-        if (q.how != nullptr) {
-            q.how[query] = cand.listed ? 0 : 1;
-        }
-    }
-}
-
-// ---------------------------------------------------------------------------------------
-// Depth layers (render.h LaunchLayers; DESIGN.md section 5 "Depth layers"): the K lexicographically
-// smallest (t, id) keys among the records that pass the exact test at an image position, K <=
-// kMaxLayers -- QueryKernel keeping K keys instead of one: the candidate walk visits every record
-// that can pass at the position, so the K smallest keys over it are the K smallest over all records.
-// The mapping is QueryKernel's (a group of kLayersLanes lanes per position). POINTS: position i is read
-// from `where`; else element (x, y) is pixel (x, row_begin + y) of the frame and its position ray
-// generation's expression of its sample offset (GBufferKernel's convention, buffers band-local).
-// Each lane keeps its CAP smallest keys sorted in registers (KeyList: compile-time indices only, no
-// scratch); an insertion drops a key that is not below the lane's CAP-th and one that the lane holds
-// already, so a repeated candidate changes nothing. (A record cannot arrive twice by way of the
-// lists: PrepareBinKernel puts a record whose tile range exceeds kLargeTiles on the large list and
-// any other on tile lists, never both, and on a tile's list once.) The group then merges in K
-// rounds: a shuffle-reduced minimum of the lanes' heads, stored by lane 0 as layer k, and every lane
-// whose head equals it pops it -- a key held by two lanes (the repeated last candidate) leaves both.
-// An empty slot is the all-ones key, above every hit's, and stored as (-1, +inf). No LDS, no
-// atomics; the setup is read, never written.
-// CAP is 2, 4 or 8 (K rounded up): the list costs 2 CAP VGPRs and the insertion ~3 CAP VALU
-// instructions per passing candidate, so K <= 2 does not pay for 8 slots.
-// Lanes per position, measured at C3 (8 / 16 / 32 lanes x 1 / 2 / 4 candidates: DESIGN.md;
-// profiles/layers/): as for the query, 8 lanes win on coherent positions (K = 8: 609 us against 796)
-// and lose on shuffled ones (K = 1: 1 265 us against 1 138). A frame's pixels are coherent by
-// construction, arbitrary positions are not: frame mode takes 8 lanes, point mode 16.
-// SRT_LAYERS_LANES, SRT_LAYERS_FRAME_LANES, SRT_LAYERS_AHEAD: measurement builds.
-// ---------------------------------------------------------------------------------------
-#ifndef SRT_LAYERS_LANES
-#define SRT_LAYERS_LANES 16
-#endif
-#ifndef SRT_LAYERS_FRAME_LANES
-#define SRT_LAYERS_FRAME_LANES 8
-#endif
-constexpr int kLayersLanes = SRT_LAYERS_LANES;             // lanes per position (a divisor of the wave), point mode
-constexpr int kLayersFrameLanes = SRT_LAYERS_FRAME_LANES;  // ... frame mode
-#ifndef SRT_LAYERS_AHEAD
-#define SRT_LAYERS_AHEAD 2
-#endif
-constexpr int kLayersAhead = SRT_LAYERS_AHEAD;  // candidates per lane and round
-constexpr int kLayersThreads = 256;
-constexpr int LayersLanes(bool points) { return points ? kLayersLanes : kLayersFrameLanes; }
-static_assert(kLayersLanes >= 2 && kWave % kLayersLanes == 0 && kLayersFrameLanes >= 2 && kWave % kLayersFrameLanes == 0,
-              "a position's lanes share a wave");
-constexpr unsigned long long kNoKey = ~0ull;  // an empty slot: above every HitKey (t < +inf)
-struct LayersParams {
-    TraceParams rec;  // as QueryParams::rec
-    const float2* __restrict__ where;  // positions (POINTS) or the band's sample offsets
-    int* __restrict__ ids;             // layers x (rows x width), layer-major
-    float* __restrict__ t;             // the same shape, or null: not stored
-    unsigned char* __restrict__ how;   // rows x width, or null: not stored
-    unsigned layers;
-    unsigned width;   // elements per row (POINTS: the count, one row)
-    unsigned chunks;  // blocks per row
-    unsigned row_begin;
-    size_t plane;  // elements per layer plane
-    float wf, hf;
-    unsigned stream_end;
-    int tiles_y;
-};
-
-// A lane's CAP smallest keys, ascending; empty slots hold kNoKey.
-template <int CAP>
-struct KeyList {
-    unsigned long long k[CAP];
-    __device__ __forceinline__ void Clear() {
-#pragma unroll
-        for (int j = 0; j < CAP; ++j) {
-            k[j] = kNoKey;
-        }
-    }
-    // Idempotent: a key the list holds, and one not below its last, change nothing.
-    __device__ __forceinline__ void Insert(unsigned long long key) {
-        bool held = false;
-#pragma unroll
-        for (int j = 0; j < CAP; ++j) {
-            held |= k[j] == key;
-        }
-        key = held ? kNoKey : key;  // (kNoKey is below no slot)
-#pragma unroll
-        for (int j = CAP - 1; j >= 1; --j) {
-            k[j] = key < k[j - 1] ? k[j - 1] : (key < k[j] ? key : k[j]);
-        }
-        k[0] = key < k[0] ? key : k[0];
-    }
-    __device__ __forceinline__ void Pop() {
-#pragma unroll
-        for (int j = 0; j + 1 < CAP; ++j) {
-            k[j] = k[j + 1];
-        }
-        k[CAP - 1] = kNoKey;
-    }
-};
-
-template <bool RC, bool POINTS, int CAP>
-__global__ __launch_bounds__(kLayersThreads) void LayersKernel(const LayersParams q) {
-    const TraceParams& p = q.rec;
-    using Recs = TraceRecords<RC>;
-    constexpr int kLanes = LayersLanes(POINTS);
-    constexpr int kBlock = kLayersThreads / kLanes;  // positions per block
-    const unsigned lane = threadIdx.x & (kLanes - 1);
-    unsigned group = threadIdx.x / kLanes;
-    if constexpr (kLanes == kWave) {
-        group = static_cast<unsigned>(__builtin_amdgcn_readfirstlane(static_cast<int>(group)));
-    }
-    const unsigned row = POINTS ? 0u : blockIdx.x / q.chunks;  // (uniform: scalar)
-    const unsigned chunk = blockIdx.x - row * q.chunks;
-    const unsigned x = chunk * kBlock + group;
-    if (x >= q.width) {
-        return;
-    }
-    const size_t at = static_cast<size_t>(row) * q.width + x;
-    float2 f = q.where[at];
-    if constexpr (!POINTS) {
-        f.x = (static_cast<float>(x) + f.x) / q.wf;
-        f.y = (static_cast<float>(q.row_begin + row) + f.y) / q.hf;
-    }
-    const Candidates cand = FindCandidates(p, q.tiles_y, q.stream_end, f.x, f.y);
-    KeyList<CAP> keys;
-    keys.Clear();
-    auto test = [&](const typename Recs::Raw& raw) {
-        const CullRecord r = Recs::Make(p, raw);
-        const Record rec{r.a.x, r.a.y, r.a.z, r.a.w, r.b.x, r.b.y, r.b.z, r.b.w, r.x.x};
-        float t;
-        if (ExactTestOne(f.x, f.y, rec, r.x.y, t)) {
-            keys.Insert(HitKey(t, static_cast<int>(__float_as_uint(r.x.z))));
-        }
-    };
-    WalkCandidates<kLanes, kLayersAhead, typename Recs::Raw>(
-        cand, lane, [&](unsigned pos) { return Recs::Load(p, pos); }, test, [] { return false; });
-    if (lane == 0u && q.how != nullptr) {
-        q.how[at] = cand.listed ? 0 : 1;
-    }
-#pragma unroll
-    for (int k = 0; k < CAP; ++k) {
-        if (static_cast<unsigned>(k) >= q.layers) {  // (uniform)
-            break;
-        }
-        unsigned long long key = keys.k[0];
-#pragma unroll
-        for (int o = 1; o < kLanes; o <<= 1) {
-            const unsigned lo = static_cast<unsigned>(__shfl_xor(static_cast<int>(key), o));
-            const unsigned hi = static_cast<unsigned>(__shfl_xor(static_cast<int>(key >> 32), o));
-            const unsigned long long other = static_cast<unsigned long long>(hi) << 32 | lo;
-            key = other < key ? other : key;
-        }
-        if (keys.k[0] == key) {  // (every holder; kNoKey: nothing is left, the pop changes nothing)
-            keys.Pop();
-        }
-        if (lane == 0u) {
-            const bool hit = key != kNoKey;
-            const size_t out = static_cast<size_t>(k) * q.plane + at;
-            q.ids[out] = hit ? static_cast<int>(static_cast<unsigned>(key)) : -1;
-            if (q.t != nullptr) {
-                q.t[out] = hit ? __uint_as_float(static_cast<unsigned>(key >> 32)) : __builtin_inff();
-            }
-        }
-    }
-}
-
-// ---------------------------------------------------------------------------------------
-// Composite (render.h LaunchComposite; DESIGN.md section 5 "Depth layers"): one RGBA pixel from K
-// layer id planes -- the front-to-back over-composite of the layers' shades under a per-triangle
-// opacity table (layers_math.h), a deferred pass shaped like ResolveKernel: a block takes
-// kCompositeThreads consecutive pixels of one band row, a thread one pixel. Two phases with no
-// control flow that depends on loaded data between the loads: (1) the pixel's offset and its K ids
-// (plane stride `plane`), (2) every layer's shading table row and opacity (an id outside the scene
-// gathers row 0 and opacity[0], unused); then the arithmetic, front to back, stopping at the first
-// id outside the scene. Neither reads nor builds a cull setup. No LDS, no atomics, no scratch.
-// ---------------------------------------------------------------------------------------
-constexpr int kCompositeThreads = 256;
-struct CompositeParams {
-    const float2* __restrict__ offsets;
-    const int* __restrict__ ids;  // layers planes of `plane` elements
-    const float* __restrict__ opacity;
-    const float4* __restrict__ shade;
-    F4* __restrict__ out;
-    size_t plane;
-    unsigned n;
-    unsigned width;
-    unsigned chunks;  // blocks per row
-    unsigned row_begin;
-    float wf, hf;
-    float base[3], du[3], dv[3], bg[3];
-};
-
-template <int K>
-__global__ __launch_bounds__(kCompositeThreads) void CompositeKernel(const CompositeParams q) {
-    const unsigned row = blockIdx.x / q.chunks;  // (uniform: scalar)
-    const unsigned chunk = blockIdx.x - row * q.chunks;
-    const unsigned x = chunk * kCompositeThreads + threadIdx.x;
-    // A pixel past the row loads the row's last one and is not stored.
-    const size_t at = static_cast<size_t>(row) * q.width + min(x, q.width - 1u);
-    // (1)
-    const float2 o = q.offsets[at];
-    int code[K];
-#pragma unroll
-    for (int k = 0; k < K; ++k) {
-        code[k] = __builtin_nontemporal_load(q.ids + static_cast<size_t>(k) * q.plane + at);
-    }
-    // (2)
-    int hit[K];
-    float4 nr[K], al[K];
-    float a[K];
-#pragma unroll
-    for (int k = 0; k < K; ++k) {
-        hit[k] = static_cast<unsigned>(code[k]) < q.n ? code[k] : -1;
-        nr[k] = al[k] = float4{};
-        a[k] = 0.f;
-    }
-    if (q.n != 0u) {  // (an empty scene has no row 0)
-#pragma unroll
-        for (int k = 0; k < K; ++k) {
-            const unsigned id = static_cast<unsigned>(max(hit[k], 0));
-            const float4* sr = q.shade + 2ull * id;
-            nr[k] = sr[0];
-            al[k] = sr[1];
-            a[k] = q.opacity[id];
-        }
-    }
-    float fx, fy;
-    ResolvePosition(x, q.row_begin + row, o.x, o.y, q.wf, q.hf, fx, fy);
-    CompositeAcc acc = CompositeStart();
-    bool open = true;  // no id outside the scene so far
-#pragma unroll
-    for (int k = 0; k < K; ++k) {
-        open = open && hit[k] >= 0;
-        if (open) {
-            const ResolveRgb c = ResolveShadeHit(q.base, q.du, q.dv, fx, fy, nr[k].x, nr[k].y, nr[k].z, nr[k].w, al[k].x,
-                                                 al[k].y, al[k].z);
-            CompositeAdd(acc, a[k], c);
-        }
-    }
-    if (x < q.width) {
-        const ResolveTexel t = CompositeFinish(acc, q.bg);
-        __builtin_nontemporal_store(F4{t.r, t.g, t.b, t.a}, q.out + at);
-    }
 }
 
 // ---------------------------------------------------------------------------------------
@@ -5744,26 +4478,6 @@ hipError_t DiagRead(void* host, std::size_t bytes) {
 #endif
 
 namespace {
-// Carve-up of a scene's edge allocation (render.h kEdgeFloatsPerTriangle): tile-planar edge
-// records, screen boxes, quantized boxes, cull records, shading normals.
-struct EdgeLayout {
-    float4* tiles;
-    float4* screen_boxes;
-    uint2* qboxes;
-    CullRecord* cull;
-};
-EdgeLayout EdgeBuffers(const float* d_edges, std::uint64_t n) {
-    EdgeLayout e;
-    const std::uint64_t n_pad = PaddedTriangleCount(n);
-    e.tiles = reinterpret_cast<float4*>(const_cast<float*>(d_edges));
-    e.screen_boxes = e.tiles + n_pad / kTileTriangles * kTileFloat4;
-    e.qboxes = reinterpret_cast<uint2*>(e.screen_boxes + n_pad);
-    e.cull = reinterpret_cast<CullRecord*>(e.qboxes + n_pad);
-    return e;
-}
-}  // namespace
-
-namespace {
 PrepareParams MakePrepareParams(const float* d_vertices, const unsigned* d_rank, std::uint64_t n, const Frame& frame,
                                 float* d_edges) {
     PrepareParams p{};
@@ -6309,17 +5023,6 @@ CullSetup CullSetupLayout(void* base, std::uint64_t n, std::size_t width, std::s
     return s;
 }
 
-namespace {
-EdgeLayout SetupRecords(const CullSetup& s) {
-    EdgeLayout e{};
-    e.tiles = nullptr;  // the tile-planar records belong to the lds / scalar variants (edge slot 0)
-    e.screen_boxes = static_cast<float4*>(s.screen_boxes);
-    e.qboxes = static_cast<uint2*>(s.qboxes);
-    e.cull = static_cast<CullRecord*>(s.cull);
-    return e;
-}
-}  // namespace
-
 hipError_t LaunchCullSetup(const CullSetup& s, std::uint64_t n, const Frame& frame, std::size_t width,
                            std::size_t height, const unsigned* d_order, const float* d_svertices, hipStream_t stream) {
     if (width == 0 || height == 0 || !CullBinnable(width, height) || d_order == nullptr || d_svertices == nullptr ||
@@ -6805,177 +5508,6 @@ hipError_t LaunchSharedCullFrames(const CullFrame* frames, std::size_t count, co
     return hipGetLastError();
 }
 
-// One record source per launch: the kernel's template argument.
-template <class P>
-static hipError_t LaunchBySource(bool recompute, void (*recomputed)(P), void (*stored)(P), dim3 grid, int threads,
-                                 hipStream_t stream, const P& q) {
-    hipLaunchKernelGGL(recompute ? recomputed : stored, grid, dim3(threads), 0, stream, q);
-    return hipGetLastError();
-}
-
-// The records a point query (or a shadow test) reads, as TraceParams: the setup's, or -- setup ==
-// null -- the scene's spatial inputs for TraceRecords<true>. Returns whether the records are
-// recomputed (the kernel's RC).
-static bool QueryRecords(TraceParams& p, int& tiles_y, const CullSetup* setup, std::uint64_t n, const Frame& frame,
-                         std::size_t width, std::size_t height, const float* d_svertices, const float* d_edges) {
-    // Without a setup the records are recomputed from the scene's spatial inputs; TraceRecords<true>
-    // also loads the position's screen box, which the exact test does not use: the scene's edge
-    // allocation has room for one per padded record, so the address is valid whatever it holds.
-    const EdgeLayout e = setup != nullptr ? SetupRecords(*setup) : EdgeBuffers(d_edges, n);
-    p.screen_boxes = e.screen_boxes;
-    p.cull = e.cull;
-    p.svertices = d_svertices;
-    p.n = static_cast<unsigned>(n);
-    p.n_pad = static_cast<unsigned>(PaddedTriangleCount(n));
-    for (int k = 0; k < 3; ++k) {
-        p.base[k] = frame.base[k];
-        p.du[k] = frame.du[k];
-        p.dv[k] = frame.dv[k];
-        p.eye[k] = frame.origin[k];
-    }
-    bool recompute = true;
-    tiles_y = 0;
-    if (setup != nullptr) {
-        recompute = setup->recompute;
-        p.tile_info = static_cast<const TileInfo*>(setup->tile_info);
-        p.bin_lists = setup->lists;
-        p.bin_counts = setup->counts;
-        p.large_list = setup->large_list;
-        p.bin_capacity = setup->capacity;
-        p.tiles_x = static_cast<int>((width + kWave - 1) / kWave);
-        tiles_y = static_cast<int>((height + kTileRows - 1) / kTileRows);
-        p.tiles = static_cast<unsigned>(setup->tiles);
-        p.wf = static_cast<float>(width);
-        p.hf = static_cast<float>(height);
-    }
-    return recompute;
-}
-
-hipError_t LaunchQuery(const CullSetup* setup, std::uint64_t n, const Frame& frame, std::size_t width,
-                       std::size_t height, const float* d_svertices, const float* d_edges, const QueryArgs& args,
-                       hipStream_t stream) {
-    if (args.count == 0) {
-        return hipSuccess;
-    }
-    if (args.positions == nullptr || args.ids == nullptr || args.t == nullptr || d_svertices == nullptr ||
-        d_edges == nullptr || args.count > 0xFFFFFFFFull - kQueryBlock ||
-        (setup != nullptr && (width == 0 || height == 0 || !CullBinnable(width, height) ||
-                              setup->tiles != CullTiles(width, height)))) {
-        return hipErrorInvalidValue;
-    }
-    QueryParams q{};
-    const bool recompute = QueryRecords(q.rec, q.tiles_y, setup, n, frame, width, height, d_svertices, d_edges);
-    const TraceParams& p = q.rec;
-    q.positions = reinterpret_cast<const float2*>(args.positions);
-    q.ids = args.ids;
-    q.t = args.t;
-    q.how = args.how;
-    q.count = static_cast<unsigned>(args.count);
-    q.stream_end = n == 0 ? 0u : p.n_pad;  // (an empty scene: every query misses)
-    const dim3 grid(static_cast<unsigned>((args.count + kQueryBlock - 1) / kQueryBlock));
-    return LaunchBySource(recompute, QueryKernel<true>, QueryKernel<false>, grid, kQueryThreads, stream, q);
-}
-
-hipError_t LaunchLayers(const CullSetup* setup, std::uint64_t n, const Frame& frame, std::size_t width,
-                        std::size_t height, const float* d_svertices, const float* d_edges, const LayersArgs& args,
-                        hipStream_t stream) {
-    // The elements: one row of `count` positions, or row_count rows of the frame's width.
-    const std::size_t row_width = args.points ? args.count : width;
-    const std::size_t rows = args.points ? 1 : args.row_count;
-    if (row_width == 0 || rows == 0) {
-        return hipSuccess;
-    }
-    const std::size_t block = static_cast<std::size_t>(kLayersThreads / LayersLanes(args.points));  // positions per block
-    const std::size_t chunks = (row_width + block - 1) / block;
-    if (args.where == nullptr || args.ids == nullptr || d_svertices == nullptr || d_edges == nullptr ||
-        args.layers == 0 || args.layers > static_cast<std::size_t>(kMaxLayers) || row_width > 0xFFFFFFFFull - block ||
-        rows > 0x7FFFFFFFull / chunks ||
-        (!args.points && (height == 0 || height > 0x7FFFFFFFull || args.row_begin > height ||
-                          args.row_count > height - args.row_begin)) ||
-        (setup != nullptr && (width == 0 || height == 0 || !CullBinnable(width, height) ||
-                              setup->tiles != CullTiles(width, height)))) {
-        return hipErrorInvalidValue;
-    }
-    LayersParams q{};
-    const bool recompute = QueryRecords(q.rec, q.tiles_y, setup, n, frame, width, height, d_svertices, d_edges);
-    q.where = reinterpret_cast<const float2*>(args.where);
-    q.ids = args.ids;
-    q.t = args.t;
-    q.how = args.how;
-    q.layers = static_cast<unsigned>(args.layers);
-    q.width = static_cast<unsigned>(row_width);
-    q.chunks = static_cast<unsigned>(chunks);
-    q.row_begin = static_cast<unsigned>(args.points ? 0 : args.row_begin);
-    q.plane = row_width * rows;
-    q.wf = static_cast<float>(width);
-    q.hf = static_cast<float>(height);
-    q.stream_end = n == 0 ? 0u : q.rec.n_pad;  // (an empty scene: every position has no layers)
-    const dim3 grid(static_cast<unsigned>(chunks * rows));
-    const auto launch = [&](auto kernel) { hipLaunchKernelGGL(kernel, grid, dim3(kLayersThreads), 0, stream, q); };
-    const auto source = [&](auto points, auto cap) {
-        constexpr bool kPoints = decltype(points)::value;
-        constexpr int kCap = decltype(cap)::value;
-        recompute ? launch(LayersKernel<true, kPoints, kCap>) : launch(LayersKernel<false, kPoints, kCap>);
-    };
-    const auto capacity = [&](auto points) {
-        if (args.layers <= 2) {
-            source(points, std::integral_constant<int, 2>{});
-        } else if (args.layers <= 4) {
-            source(points, std::integral_constant<int, 4>{});
-        } else {
-            source(points, std::integral_constant<int, 8>{});
-        }
-    };
-    args.points ? capacity(std::true_type{}) : capacity(std::false_type{});
-    return hipGetLastError();
-}
-
-template <int K>
-static void LaunchCompositeLayers(unsigned layers, dim3 grid, hipStream_t stream, const CompositeParams& q) {
-    if (layers == static_cast<unsigned>(K)) {
-        hipLaunchKernelGGL(CompositeKernel<K>, grid, dim3(kCompositeThreads), 0, stream, q);
-    } else if constexpr (K > 1) {
-        LaunchCompositeLayers<K - 1>(layers, grid, stream, q);
-    }
-}
-
-hipError_t LaunchComposite(const float* d_shade, std::uint64_t n, const Frame& frame, const float background[3],
-                           const CompositeArgs& args, hipStream_t stream) {
-    if (args.width == 0 || args.row_count == 0) {
-        return hipSuccess;
-    }
-    const std::size_t chunks = (args.width + kCompositeThreads - 1) / kCompositeThreads;
-    if (args.offsets == nullptr || args.ids == nullptr || args.rgba == nullptr || d_shade == nullptr ||
-        (n != 0 && args.opacity == nullptr) || args.layers == 0 || args.layers > static_cast<std::size_t>(kMaxLayers) ||
-        n > 0xFFFFFFFFull || args.width > 0xFFFFFFFFull - kCompositeThreads || args.height == 0 ||
-        args.row_begin > args.height || args.row_count > args.height - args.row_begin ||
-        args.height > 0x7FFFFFFFull || args.row_count > 0x7FFFFFFFull / chunks) {
-        return hipErrorInvalidValue;
-    }
-    CompositeParams q{};
-    q.offsets = reinterpret_cast<const float2*>(args.offsets);
-    q.ids = args.ids;
-    q.opacity = args.opacity;
-    q.shade = reinterpret_cast<const float4*>(d_shade);
-    q.out = reinterpret_cast<F4*>(args.rgba);
-    q.plane = args.width * args.row_count;
-    q.n = static_cast<unsigned>(n);
-    q.width = static_cast<unsigned>(args.width);
-    q.chunks = static_cast<unsigned>(chunks);
-    q.row_begin = static_cast<unsigned>(args.row_begin);
-    q.wf = static_cast<float>(args.width);
-    q.hf = static_cast<float>(args.height);
-    for (int k = 0; k < 3; ++k) {
-        q.base[k] = frame.base[k];
-        q.du[k] = frame.du[k];
-        q.dv[k] = frame.dv[k];
-        q.bg[k] = background[k];
-    }
-    LaunchCompositeLayers<kMaxLayers>(static_cast<unsigned>(args.layers), dim3(static_cast<unsigned>(chunks * args.row_count)),
-                                      stream, q);
-    return hipGetLastError();
-}
-
 // The view's part of a shadow launch (ShadowArgs, LightingArgs: the same band fields), `block`
 // pixels per block. False: a band or a buffer the launchers refuse.
 template <class Args>
@@ -7288,201 +5820,6 @@ hipError_t LaunchLitSurface(const float* d_vertices, const float* d_shade, std::
     }
     return LaunchBySource(recompute, LitSurfaceKernel<true>, LitSurfaceKernel<false>,
                           ViewBandGrid(s.lit.view, kLightingBlock), kLightingThreads, stream, s);
-}
-
-hipError_t LaunchGBuffer(const float* d_vertices, const float* d_shade, std::uint64_t n, const Frame& frame,
-                         const float background[3], const GBufferArgs& args, hipStream_t stream) {
-    const bool planes = args.depth != nullptr || args.bary != nullptr || args.normal != nullptr || args.albedo != nullptr;
-    if (args.width == 0 || args.row_count == 0 || !planes) {
-        return hipSuccess;
-    }
-    // Both gathers (the vertices for depth / bary, the shading table row for normal / albedo)?
-    const bool both = (args.depth != nullptr || args.bary != nullptr) && (args.normal != nullptr || args.albedo != nullptr);
-    const std::size_t block = static_cast<std::size_t>(kGBufferThreads) * (both ? kGBufferPixelsBoth : kGBufferPixels);
-    const std::size_t chunks = (args.width + block - 1) / block;
-    if (args.where == nullptr || args.ids == nullptr || d_shade == nullptr || (n != 0 && d_vertices == nullptr) ||
-        n > 0xFFFFFFFFull || args.width > 0xFFFFFFFFull - block || (args.points && args.row_count != 1) ||
-        (!args.points && (args.height == 0 || args.row_begin + args.row_count > args.height)) ||
-        args.row_count > 0x7FFFFFFFull / chunks) {
-        return hipErrorInvalidValue;
-    }
-    GBufferParams q{};
-    q.vertices = d_vertices;
-    q.shade = reinterpret_cast<const float4*>(d_shade);
-    q.where = reinterpret_cast<const float2*>(args.where);
-    q.ids = args.ids;
-    q.depth = args.depth;
-    q.bary = reinterpret_cast<F2*>(args.bary);
-    q.normal = reinterpret_cast<F4*>(args.normal);
-    q.albedo = reinterpret_cast<F4*>(args.albedo);
-    q.n = static_cast<unsigned>(n);
-    q.width = static_cast<unsigned>(args.width);
-    q.chunks = static_cast<unsigned>(chunks);
-    q.row_begin = static_cast<unsigned>(args.row_begin);
-    q.wf = static_cast<float>(args.width);
-    q.hf = static_cast<float>(args.height);
-    for (int k = 0; k < 3; ++k) {
-        q.eye[k] = frame.origin[k];
-        q.base[k] = frame.base[k];
-        q.du[k] = frame.du[k];
-        q.dv[k] = frame.dv[k];
-        q.bg[k] = background[k];
-    }
-    const dim3 grid(static_cast<unsigned>(chunks * args.row_count));
-    const auto launch = [&](auto kernel) { hipLaunchKernelGGL(kernel, grid, dim3(kGBufferThreads), 0, stream, q); };
-    if (args.points) {
-        both ? launch(GBufferKernel<true, kGBufferPixelsBoth>) : launch(GBufferKernel<true, kGBufferPixels>);
-    } else {
-        both ? launch(GBufferKernel<false, kGBufferPixelsBoth>) : launch(GBufferKernel<false, kGBufferPixels>);
-    }
-    return hipGetLastError();
-}
-
-hipError_t LaunchSurface(const float* d_vertices, const float* d_shade, std::uint64_t n, const Frame& frame,
-                         const float background[3], const SurfaceArgs& args, hipStream_t stream) {
-    const bool planes = args.normal != nullptr || args.albedo != nullptr || args.rgba != nullptr || args.uv != nullptr;
-    if (args.width == 0 || args.row_count == 0 || !planes) {
-        return hipSuccess;
-    }
-    const std::size_t block = static_cast<std::size_t>(kSurfaceThreads) * kSurfacePixels;
-    const std::size_t chunks = (args.width + block - 1) / block;
-    const bool texture_ok = args.texture == nullptr ||
-                            (args.uvs != nullptr && args.tex_width >= 1 && args.tex_width <= kSurfaceMaxTexture &&
-                             args.tex_height >= 1 && args.tex_height <= kSurfaceMaxTexture);
-    if (args.where == nullptr || args.ids == nullptr || d_shade == nullptr || (n != 0 && d_vertices == nullptr) ||
-        n > 0xFFFFFFFFull || args.width > 0xFFFFFFFFull - block || (args.points && args.row_count != 1) ||
-        (!args.points && (args.height == 0 || args.row_begin + args.row_count > args.height)) ||
-        args.row_count > 0x7FFFFFFFull / chunks || !texture_ok || (args.flags & ~kSurfaceFlags) != 0u) {
-        return hipErrorInvalidValue;
-    }
-    SurfaceParams q{};
-    q.vertices = d_vertices;
-    q.shade = reinterpret_cast<const float4*>(d_shade);
-    q.where = reinterpret_cast<const float2*>(args.where);
-    q.ids = args.ids;
-    q.normals = args.normals;
-    q.uvs = args.uvs;
-    q.texture = reinterpret_cast<const float4*>(args.texture);
-    q.normal = reinterpret_cast<F4*>(args.normal);
-    q.albedo = reinterpret_cast<F4*>(args.albedo);
-    q.rgba = reinterpret_cast<F4*>(args.rgba);
-    q.uv = reinterpret_cast<F2*>(args.uv);
-    q.n = static_cast<unsigned>(n);
-    q.width = static_cast<unsigned>(args.width);
-    q.chunks = static_cast<unsigned>(chunks);
-    q.row_begin = static_cast<unsigned>(args.row_begin);
-    q.tw = args.texture != nullptr ? static_cast<int>(args.tex_width) : 1;
-    q.th = args.texture != nullptr ? static_cast<int>(args.tex_height) : 1;
-    q.flags = args.flags;
-    q.wf = static_cast<float>(args.width);
-    q.hf = static_cast<float>(args.height);
-    for (int k = 0; k < 3; ++k) {
-        q.eye[k] = frame.origin[k];
-        q.base[k] = frame.base[k];
-        q.du[k] = frame.du[k];
-        q.dv[k] = frame.dv[k];
-        q.bg[k] = background[k];
-    }
-    const dim3 grid(static_cast<unsigned>(chunks * args.row_count));
-    if (args.points) {
-        hipLaunchKernelGGL((SurfaceKernel<true, kSurfacePixels>), grid, dim3(kSurfaceThreads), 0, stream, q);
-    } else {
-        hipLaunchKernelGGL((SurfaceKernel<false, kSurfacePixels>), grid, dim3(kSurfaceThreads), 0, stream, q);
-    }
-    return hipGetLastError();
-}
-
-hipError_t LaunchInterpolate(const float* d_vertices, std::uint64_t n, const Frame& frame, const InterpolateArgs& args,
-                             hipStream_t stream) {
-    if (args.width == 0 || args.row_count == 0) {
-        return hipSuccess;
-    }
-    const std::size_t block = static_cast<std::size_t>(kSurfaceThreads) * kInterpolatePixels;
-    const std::size_t chunks = (args.width + block - 1) / block;
-    if (args.where == nullptr || args.ids == nullptr || args.out == nullptr || (n != 0 && d_vertices == nullptr) ||
-        (n != 0 && args.table == nullptr) || args.channels < 1 ||
-        args.channels > static_cast<std::size_t>(kSurfaceMaxChannels) || n > 0xFFFFFFFFull ||
-        args.width > 0xFFFFFFFFull - block || (args.points && args.row_count != 1) ||
-        (!args.points && (args.height == 0 || args.row_begin + args.row_count > args.height)) ||
-        args.row_count > 0x7FFFFFFFull / chunks) {
-        return hipErrorInvalidValue;
-    }
-    InterpolateParams q{};
-    q.vertices = d_vertices;
-    q.where = reinterpret_cast<const float2*>(args.where);
-    q.ids = args.ids;
-    q.table = args.table;
-    q.out = args.out;
-    q.n = static_cast<unsigned>(n);
-    q.width = static_cast<unsigned>(args.width);
-    q.chunks = static_cast<unsigned>(chunks);
-    q.row_begin = static_cast<unsigned>(args.row_begin);
-    q.wf = static_cast<float>(args.width);
-    q.hf = static_cast<float>(args.height);
-    for (int k = 0; k < 3; ++k) {
-        q.eye[k] = frame.origin[k];
-        q.base[k] = frame.base[k];
-        q.du[k] = frame.du[k];
-        q.dv[k] = frame.dv[k];
-    }
-    const dim3 grid(static_cast<unsigned>(chunks * args.row_count));
-    const auto launch = [&](auto kernel) { hipLaunchKernelGGL(kernel, grid, dim3(kSurfaceThreads), 0, stream, q); };
-    switch (args.channels * 2 + (args.points ? 1 : 0)) {
-        case 2: launch(InterpolateKernel<false, 1>); break;
-        case 3: launch(InterpolateKernel<true, 1>); break;
-        case 4: launch(InterpolateKernel<false, 2>); break;
-        case 5: launch(InterpolateKernel<true, 2>); break;
-        case 6: launch(InterpolateKernel<false, 3>); break;
-        case 7: launch(InterpolateKernel<true, 3>); break;
-        case 8: launch(InterpolateKernel<false, 4>); break;
-        default: launch(InterpolateKernel<true, 4>); break;
-    }
-    return hipGetLastError();
-}
-
-hipError_t LaunchResolve(const float* d_shade, std::uint64_t n, const Frame& frame, const float background[3],
-                         const ResolveArgs& args, hipStream_t stream) {
-    if (args.width == 0 || args.row_count == 0) {
-        return hipSuccess;
-    }
-    const std::size_t chunks = (args.width + kResolveThreads - 1) / kResolveThreads;
-    if (args.offsets == nullptr || args.ids == nullptr || args.rgba == nullptr || d_shade == nullptr ||
-        args.samples == 0 || args.samples > static_cast<std::size_t>(kMaxSamples) || n > 0xFFFFFFFFull ||
-        args.width > 0xFFFFFFFFull - kResolveThreads || args.height == 0 || args.row_begin > args.height ||
-        args.row_count > args.height - args.row_begin || args.height > 0x7FFFFFFFull ||
-        args.row_count > 0x7FFFFFFFull / chunks) {
-        return hipErrorInvalidValue;
-    }
-    ResolveParams q{};
-    for (std::size_t s = 0; s < args.samples; ++s) {
-        if (args.offsets[s] == nullptr || args.ids[s] == nullptr) {
-            return hipErrorInvalidValue;
-        }
-        q.offsets[s] = reinterpret_cast<const float2*>(args.offsets[s]);
-        q.ids[s] = args.ids[s];
-    }
-    q.shade = reinterpret_cast<const float4*>(d_shade);
-    q.out = reinterpret_cast<F4*>(args.rgba);
-    q.n = static_cast<unsigned>(n);
-    q.samples = static_cast<unsigned>(args.samples);
-    q.width = static_cast<unsigned>(args.width);
-    q.chunks = static_cast<unsigned>(chunks);
-    q.row_begin = static_cast<unsigned>(args.row_begin);
-    q.wf = static_cast<float>(args.width);
-    q.hf = static_cast<float>(args.height);
-    for (int k = 0; k < 3; ++k) {
-        q.base[k] = frame.base[k];
-        q.du[k] = frame.du[k];
-        q.dv[k] = frame.dv[k];
-        q.bg[k] = background[k];
-    }
-    const dim3 grid(static_cast<unsigned>(chunks * args.row_count));
-    if (q.samples >= kResolveLong) {
-        hipLaunchKernelGGL(ResolveKernel<kResolveGroupLong>, grid, dim3(kResolveThreads), 0, stream, q);
-    } else {
-        hipLaunchKernelGGL(ResolveKernel<kResolveGroup>, grid, dim3(kResolveThreads), 0, stream, q);
-    }
-    return hipGetLastError();
 }
 
 hipError_t LaunchTrace(const float* d_edges, std::uint64_t n, const float* d_vertices, const float* d_shade,

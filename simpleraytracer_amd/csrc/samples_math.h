@@ -1,5 +1,5 @@
 // The resolve of a multi-sample pixel: the shade of one (image position, hit id) sample and the
-// accumulate / divide step (render.hip ResolveKernel; DESIGN.md section 2 "Resolve"). Host and
+// accumulate / divide step (outputs.hip ResolveKernel; DESIGN.md section 2 "Resolve"). Host and
 // device share it (cpu_render.cpp HostResolve, the host answer rtsResolveHost), so both evaluate
 // the same float expressions: explicit fma, no contraction, IEEE divide and square root.
 //

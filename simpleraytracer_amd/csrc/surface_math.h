@@ -1,5 +1,5 @@
 // Vertex attributes of one (image position, triangle) pair: perspective-correct weights, the
-// interpolation of per-corner tables, the smooth normal and the texture lookup (render.hip
+// interpolation of per-corner tables, the smooth normal and the texture lookup (outputs.hip
 // SurfaceKernel / InterpolateKernel; DESIGN.md section 2 "Vertex attributes"). Host and device
 // share it (cpu_render.cpp HostSurface / HostInterpolate, the host answers rtvSurfaceHost and
 // rtvInterpolateHost), so both evaluate the same float expressions.

@@ -1,5 +1,5 @@
 // The cull tile whose analytic box contains an image position: the point queries' lookup
-// (render.hip QueryKernel; DESIGN.md section 5 "Point queries"). Host and device share it (the
+// (query.hip QueryKernel; DESIGN.md section 5 "Point queries"). Host and device share it (the
 // host self-test rtqTileHost).
 //
 // Tile column c of a W-wide frame has the analytic box [fl(64 c / W), fl((64 c + 64) / W)] in fx,

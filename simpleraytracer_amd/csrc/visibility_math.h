@@ -42,7 +42,7 @@ __host__ __device__ inline float VisibilityDot3(float ax, float ay, float az, fl
 }
 
 // ShadowDepth of the triangle with vertex coordinates v[0..9) at (fx, fy) under the frame (origin,
-// base, du, dv): the edge record's expressions (render.hip ComputeEdges, cpu_render.cpp MakeRecord),
+// base, du, dv): the edge record's expressions (trace_device.h ComputeEdges, cpu_render.cpp MakeRecord),
 // so the traces' t. NaN for a disabled record (vol zero or not finite).
 __host__ __device__ inline float VisibilityDepth(const float origin[3], const float base[3], const float du[3],
                                                  const float dv[3], const float v[9], float fx, float fy) {

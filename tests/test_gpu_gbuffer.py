@@ -1,4 +1,4 @@
-"""G-buffer outputs on the device (include/srt_gbuffer.h rtgFrameAsync / rtgPointsAsync; render.hip
+"""G-buffer outputs on the device (include/srt_gbuffer.h rtgFrameAsync / rtgPointsAsync; outputs.hip
 GBufferKernel): depth, barycentrics, normal + shading cosine and albedo + id from hit ids.
 
 Expected values come from the oracle and numpy (tests/gbuffer_cases.py), never from the library:

@@ -1,5 +1,5 @@
 """Depth layers on the device (include/srt_layers.h rtkLayersAsync, rtkFrameAsync,
-rtkCompositeAsync; render.hip LayersKernel, CompositeKernel): the K nearest hits per position from
+rtkCompositeAsync; query.hip LayersKernel, CompositeKernel): the K nearest hits per position from
 the shared setup's per-tile lists, and their over-composite.
 
 Every layer comparison is exact -- ids equal, t equal on the uint32 view -- against the CPU oracle's

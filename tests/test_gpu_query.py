@@ -1,4 +1,4 @@
-"""Point queries on the device (include/srt_query.h rtqQueryAsync; render.hip QueryKernel): the
+"""Point queries on the device (include/srt_query.h rtqQueryAsync; query.hip QueryKernel): the
 closest hit at arbitrary image positions of the prepared frame, answered from the shared setup's
 per-tile lists.
 

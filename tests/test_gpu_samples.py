@@ -1,5 +1,5 @@
 """Multi-sample frames on the device (include/srt_samples.h rtsResolveAsync / rtsRenderAsync;
-render.hip ResolveKernel): S hit-id planes and S sample-offset planes in, one resolved RGBA pixel out.
+outputs.hip ResolveKernel): S hit-id planes and S sample-offset planes in, one resolved RGBA pixel out.
 
 Expected values come from S per-sample RGBA frames -- srtTraceAsync's, or the oracle's -- resolved in
 numpy (tests/samples_cases.py expected()), never from the resolve under test: bit-equal on the

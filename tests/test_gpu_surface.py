@@ -1,5 +1,5 @@
 """Vertex attributes on the device (include/srt_surface.h rtvSurfaceFrameAsync / rtvSurfacePointsAsync /
-rtvInterpolate*Async; render.hip SurfaceKernel, InterpolateKernel): smooth normals, UVs, textured
+rtvInterpolate*Async; outputs.hip SurfaceKernel, InterpolateKernel): smooth normals, UVs, textured
 albedo and the shaded pixel from hit ids and the caller's corner tables.
 
 Expected values come from the oracle and numpy (tests/surface_cases.py: the float32 restatement),
